@@ -8,16 +8,24 @@ log-softmax + argmax, producing uint8 label maps.  Frames shard across ranks (on
 per GPU, weak scaling, no collective on the data path; the only collectives are the
 timing barrier and the max-over-ranks of the elapsed time).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--dump-outputs DIR] [--full]
     torchrun --nproc-per-node N bench.py --gpus N ...
 
 `--gpus N` without a torchrun environment spawns the N rank processes itself (before any GPU
 call; one device each, RCCL rendezvous on 127.0.0.1); under torchrun WORLD_SIZE must equal N.
-The default bf16 line also carries `exact_mode` (the fp32-accurate split-bf16 engine),
-`exact_mode_fp32` (exact fp32 on the f32 MFMA) and `int8_mode` (config C5's W8A8): the other
-modes on the same weights and frames, timed in the same process (--exact-steps each), each with
-its own dominant-kernel roofline (HIP-event achieved rate, committed PMC traffic and MFMA-busy),
-time accounting (per-step spread, launch sum vs step) and parity vs the reference.
+
+A plain run does what the headline figure needs and nothing else: build the model and the
+frames, W warm-up steps, K timed steps, the result line.  `--dump-outputs DIR` also writes the
+label maps the last timed step returned as DIR/labels.npy (float32; the same arguments give the
+same frames and weights, so two builds can be compared output for output).
+
+`--full` adds every other measurement: HIP events around the launches (the dominant kernel's
+roofline with committed PMC traffic and MFMA-busy, the per-kernel and per-launch tables, time
+accounting with the per-step spread), the network roofline, `--host-frames`, the CPU baseline and
+parity vs the reference, and, on the default bf16 line, `exact_mode` (the fp32-accurate split-bf16
+engine), `exact_mode_fp32` (exact fp32 on the f32 MFMA) and `int8_mode` (config C5's W8A8): the
+other modes on the same weights and frames, timed in the same process (--exact-steps each), each
+with its own roofline, accounting and parity.
 
 Prints ONE JSON line (rank 0).
 """
@@ -48,6 +56,14 @@ def parse(argv=None):
     ap.add_argument("--precision", default="bf16", choices=["bf16", "fp32", "fp32x", "int8"],
                     help="int8: W8A8 for the cin >= 64 convs (config C5), scales calibrated on 2 "
                          "synthetic frames before the timed region")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the label maps the last timed step returned to DIR/labels.npy (float32; "
+                         "labels_rank<r>.npy per rank with --gpus > 1; a fixed seeded sample of the pixels when "
+                         "the full maps would exceed the size budget)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every other measurement (kernel events and rooflines, time accounting, "
+                         "--host-frames, the fp32x / fp32 / int8 sub-lines, CPU baseline, parity vs the "
+                         "reference); the options below that select among them need --full")
     ap.add_argument("--cpu-seconds", type=float, default=12.0, help="CPU-baseline sample budget")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-kernel-events", action="store_true")
@@ -68,7 +84,10 @@ def parse(argv=None):
     ap.add_argument("--stub-step", action="store_true",
                     help="test hook: no GPU; gloo ranks run a CPU stand-in step through the same launcher, "
                          "seeding, timing and max-over-ranks code (tests/test_bench_launcher.py)")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.host_frames and not args.full:
+        ap.error("--host-frames is a measurement of its own: add --full")
+    return args
 
 
 def spawn_ranks(n: int, argv, script: str | None = None) -> int:
@@ -190,6 +209,27 @@ def frame_seed(rank: int) -> int:
     return 1000 + rank
 
 
+DUMP_BUDGET = 48 * 10**6      # bytes of array data --dump-outputs writes per run, all ranks together
+DUMP_SEED = 20240
+
+
+def dump_outputs(dirname, name, array, world=1, rank=0, budget=DUMP_BUDGET):
+    """--dump-outputs: `array` (what the last timed step returned, on the host) as float32 in
+    DIR/<name>.npy (<name>_rank<r>.npy when several ranks write).  An array above this rank's
+    share of the budget is written as a 1-D sample: the elements at DUMP_SEED's sorted random
+    flat indices, the same for every run of the same shape.  Returns the file's path."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    a = np.asarray(array)
+    keep = budget // (4 * world)
+    if a.size > keep:
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(a.size, size=keep, replace=False))
+        a = a.reshape(-1)[idx]
+    path = os.path.join(dirname, (name if world == 1 else f"{name}_rank{rank}") + ".npy")
+    np.save(path, a.astype(np.float32))
+    return path
+
+
 def stub_main(args, world, rank):
     """CPU stand-in for the GPU step (test hook): gloo ranks, per-rank seeded uint8 frames of the
     requested shape, a reduction over them as the 'step'; same timing and JSON fields."""
@@ -200,14 +240,17 @@ def stub_main(args, world, rank):
         dist.init_process_group("gloo")
     g = torch.Generator().manual_seed(frame_seed(rank))
     frames = torch.randint(0, 256, (args.batch, args.height, args.width, 3), dtype=torch.uint8, generator=g)
-    acc = [0.0]
+    acc, last = [0.0], [None]
 
     def step(timed):
-        acc[0] += float(frames.float().mean())
+        last[0] = frames.float().mean(dim=(1, 2, 3))     # the stand-in's output: one mean per frame
+        acc[0] += float(last[0].mean())
 
     for _ in range(args.warmup):
         step(False)
     el, own = timed_region(step, args.steps, world, dev)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, "frame_means", last[0].numpy(), world, rank)
     per = gather_ranks([frame_seed(rank), float(frames.long().sum()), own], world, dev)
     if rank == 0:
         print(json.dumps({"metric": METRIC, "value": world * args.batch * args.steps / el, "unit": "frames/s",
@@ -350,8 +393,27 @@ def parity_vs_ref(args, model, frames, ref_labels, dev, precision=None):
             "reference": "oracle/drn_oracle.py fp32 torch-CPU forward, same weights and frames"}
 
 
+def measure_plain(model, frames, steps, warmup, world, dev):
+    """The headline figure and nothing else: `warmup` untimed seg_video steps of `model` over
+    `frames` (resident in HBM; the last one inside timed_region, ahead of its opening sync), then
+    `steps` timed ones, with no HIP events and no instrumented steps.  Returns the job time and
+    the label maps the last timed step returned."""
+    from drnmi.drnseg import INFO_MEAN, INFO_STD
+    last = [None]
+
+    def step(timed):
+        # the public API a seg_video user calls: DRNSeg.segment -> torch.ops.drnmi.segment
+        last[0] = model.segment(frames, INFO_MEAN, INFO_STD, False)
+
+    model.timing_hook = None
+    for _ in range(max(warmup - 1, 0)):
+        step(False)
+    el, own = timed_region(step, steps, world, dev, lead=(lambda: step(False)) if warmup >= 1 else None)
+    return {"el": el, "own": own, "last": last[0]}
+
+
 def measure(args, model, frames, steps, warmup, world, dev, kernel_events=True):
-    """Time `steps` seg_video steps of `model` over `frames` (resident in HBM) after `warmup`
+    """--full: time `steps` seg_video steps of `model` over `frames` (resident in HBM) after `warmup`
     untimed ones.  Returns the job time and the dominant kernel's per-launch HIP-event record
     (timed region) plus a per-kernel table (one fully instrumented step after it)."""
     import ctypes
@@ -415,6 +477,7 @@ def measure(args, model, frames, steps, warmup, world, dev, kernel_events=True):
     events = []
     pool = [torch.cuda.Event(enable_timing=True) for _ in range(2 * len(names) * max(steps, 2))]
     watch = [None]        # None: every launch; else only launches of this kernel name
+    last = [None]         # what the latest step returned (--dump-outputs)
 
     def hook(i, nd, before):
         if watch[0] is not None and names[i] != watch[0]:
@@ -426,7 +489,8 @@ def measure(args, model, frames, steps, warmup, world, dev, kernel_events=True):
     def step(timed, x=frames):
         # the public API a seg_video user calls: DRNSeg.segment -> torch.ops.drnmi.segment
         model.timing_hook = hook if (timed and kernel_events) else None
-        return model.segment(x, INFO_MEAN, INFO_STD, False)
+        last[0] = model.segment(x, INFO_MEAN, INFO_STD, False)
+        return last[0]
 
     launches = []         # (node index, seconds) of the last collect(), in launch order
 
@@ -461,6 +525,7 @@ def measure(args, model, frames, steps, warmup, world, dev, kernel_events=True):
     watch[0] = dominant
     marks = [torch.cuda.Event(enable_timing=True) for _ in range(steps + 1)]
     el, own = timed_region(step, steps, world, dev, marks, lead=(lambda: step(False)) if warmup >= 2 else None)
+    timed_out = last[0]
     timed_per = collect()
     spread = step_spread(marks)
     # per-kernel table: one fully instrumented step after the timed region
@@ -495,7 +560,8 @@ def measure(args, model, frames, steps, warmup, world, dev, kernel_events=True):
     if dominant in timed_per:
         per[dominant] = timed_per[dominant]
     model.timing_hook = None
-    return {"el": el, "own": own, "plan": plan, "names": names, "density": density, "per": per,
+    last[0] = None
+    return {"el": el, "own": own, "last": timed_out, "plan": plan, "names": names, "density": density, "per": per,
             "dominant": dominant, "timed": timed_per.get(dominant), "step": step, "layers": layers,
             "accounting": accounting}
 
@@ -588,9 +654,15 @@ def main(argv=None):
     B, H, W = args.batch, args.height, args.width
     g = torch.Generator(device=dev).manual_seed(frame_seed(rank))
     frames = torch.randint(0, 256, (B, H, W, 3), dtype=torch.uint8, device=dev, generator=g)
-    m = measure(args, model, frames, args.steps, args.warmup, world, dev, not args.no_kernel_events)
-    el, names, density = m["el"], m["names"], m["density"]
-    host = host_frames_run(args, model, m["step"], world, dev) if args.host_frames else None
+    if args.full:
+        m = measure(args, model, frames, args.steps, args.warmup, world, dev, not args.no_kernel_events)
+    else:
+        m = measure_plain(model, frames, args.steps, args.warmup, world, dev)
+    el = m["el"]
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, "labels", m["last"].cpu().numpy(), world, rank)
+    m["last"] = None
+    host = host_frames_run(args, model, m["step"], world, dev) if args.full and args.host_frames else None
     per_rank = gather_ranks([frame_seed(rank), m["own"]], world, dev)
 
     total_frames = world * B * args.steps
@@ -618,8 +690,22 @@ def main(argv=None):
         out["per_rank"] = [{"rank": r, "frame_seed": int(v[0]), "frames": B * args.steps, "seconds": round(v[1], 6)}
                            for r, v in enumerate(per_rank)]
     if args.prune:
-        sparse = [i for i, nm in enumerate(names) if nm.startswith("conv_big_kernel") and nm.endswith("true>")]
         out["config"]["workload"] = out["config"]["workload"].replace("dense inference", f"{args.prune} pruned inference")
+    if args.full:
+        full_report(args, out, m, model, frames, host, n_pruned if args.prune else 0, world, rank, dev)
+    if rank == 0:
+        print(json.dumps(out), flush=True)
+    if world > 1:
+        dist.destroy_process_group()
+
+
+def full_report(args, out, m, model, frames, host, n_pruned, world, rank, dev):
+    """--full: everything the result line carries beyond the headline figure, added to `out`."""
+    import torch
+    from drnmi.drnseg import build
+    B, names, density = args.batch, m["names"], m["density"]
+    if args.prune:
+        sparse = [i for i, nm in enumerate(names) if nm.startswith("conv_big_kernel") and nm.endswith("true>")]
         out["config"]["block_sparse"] = {"pruned_layers": n_pruned, "sparse_launches": len(sparse),
                                          "mean_weight_density_of_sparse_launches":
                                              round(sum(density[i] for i in sparse) / max(len(sparse), 1), 4),
@@ -670,10 +756,6 @@ def main(argv=None):
             out["parity_vs_ref"] = parity_vs_ref(args, model, bframes, blabels, dev)
             for prec, (line, xm) in exact.items():
                 line["parity_vs_ref"] = parity_vs_ref(args, xm, bframes, blabels, dev, prec)
-    if rank == 0:
-        print(json.dumps(out), flush=True)
-    if world > 1:
-        dist.destroy_process_group()
 
 
 SUB_MODES = (

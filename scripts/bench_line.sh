@@ -4,7 +4,7 @@ set -u
 R=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$R/gpurun_out/$1; TAG=$2; shift 2
 mkdir -p $OUT
-timeout -k 10 300 python -u $R/bench.py "$@" > $OUT/bench_$TAG.json 2> $OUT/bench_$TAG.err || { echo "bench $TAG failed"; tail -5 $OUT/bench_$TAG.err; exit 1; }
+timeout -k 10 300 python -u $R/bench.py --full "$@" > $OUT/bench_$TAG.json 2> $OUT/bench_$TAG.err || { echo "bench $TAG failed"; tail -5 $OUT/bench_$TAG.err; exit 1; }
 python3 - "$OUT/bench_$TAG.json" <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

@@ -12,7 +12,7 @@ rc=$?; echo "pytest rc=$rc" >> $OUT/pytest_gpu.log; tail -3 $OUT/pytest_gpu.log
 [ $rc -ne 0 ] && exit $rc
 timeout -k 10 200 python -u -c "import sys; sys.path.insert(0,'$R'); import __graft_entry__ as g; g.smoke()" > $OUT/smoke.log 2>&1 || { echo smoke failed; tail -5 $OUT/smoke.log; exit 1; }
 tail -1 $OUT/smoke.log
-b() { local name=$1; shift; timeout -k 10 300 python -u $R/bench.py "$@" > $OUT/bench_$name.json 2> $OUT/bench_$name.err || { echo "bench $name failed"; tail -5 $OUT/bench_$name.err; exit 1; }; }
+b() { local name=$1; shift; timeout -k 10 300 python -u $R/bench.py --full "$@" > $OUT/bench_$name.json 2> $OUT/bench_$name.err || { echo "bench $name failed"; tail -5 $OUT/bench_$name.err; exit 1; }; }
 b bf16
 b fp32 --precision fp32 --steps 5 --warmup 2 --no-cpu-baseline
 b fp32x --precision fp32x --steps 5 --warmup 2

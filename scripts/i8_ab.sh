@@ -8,7 +8,7 @@ mkdir -p $OUT
 for rep in 1 2; do
 for c in $CFGS; do
   v1=$(echo $c | sed 's/.*V1=\([-0-9]*\).*/\1/'); v3=$(echo $c | sed 's/.*V3=\([-0-9]*\).*/\1/')
-  DRNMI_I8_V1=$v1 DRNMI_I8_V3=$v3 timeout -k 10 200 python -u $R/bench.py --precision int8 --no-cpu-baseline \
+  DRNMI_I8_V1=$v1 DRNMI_I8_V3=$v3 timeout -k 10 200 python -u $R/bench.py --full --precision int8 --no-cpu-baseline \
       --no-exact-mode "$@" > $OUT/b_${c}_$rep.json 2>/dev/null || exit 1
   python3 -c "
 import json; d=json.loads(open('$OUT/b_${c}_$rep.json').read().strip().splitlines()[-1])

@@ -12,8 +12,8 @@ for rep in 0 1 2; do
   for k in $(seq 0 $((N - 1))); do
     L=${LIBS[$(( (k + rep) % N ))]}
     tag=${L%.so}
-    if [ "$L" = "main" ]; then timeout -k 10 150 python3 bench.py $ARGS > $O/${tag}_$rep.json 2>/dev/null || exit 1
-    else DRNMI_LIB=$R/diag/$L timeout -k 10 150 python3 bench.py $ARGS > $O/${tag}_$rep.json 2>/dev/null || exit 1; fi
+    if [ "$L" = "main" ]; then timeout -k 10 150 python3 bench.py --full $ARGS > $O/${tag}_$rep.json 2>/dev/null || exit 1
+    else DRNMI_LIB=$R/diag/$L timeout -k 10 150 python3 bench.py --full $ARGS > $O/${tag}_$rep.json 2>/dev/null || exit 1; fi
   done
 done
 python3 - $O "${LIBS[@]}" <<'PY'

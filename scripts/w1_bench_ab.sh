@@ -5,8 +5,8 @@ set -u
 R=${GRAFT_REPO_ROOT:-$(pwd)}
 O=$R/gpurun_out/$1; mkdir -p $O
 for i in 1 2 3; do
-  timeout -k 10 120 python3 bench.py --steps 40 --no-cpu-baseline --no-exact-mode > $O/w1_$i.json 2>/dev/null || exit 1
-  DRNMI_LIB=$R/diag/libdrnmi_stag.so timeout -k 10 120 python3 bench.py --steps 40 --no-cpu-baseline --no-exact-mode > $O/stag_$i.json 2>/dev/null || exit 1
+  timeout -k 10 120 python3 bench.py --full --steps 40 --no-cpu-baseline --no-exact-mode > $O/w1_$i.json 2>/dev/null || exit 1
+  DRNMI_LIB=$R/diag/libdrnmi_stag.so timeout -k 10 120 python3 bench.py --full --steps 40 --no-cpu-baseline --no-exact-mode > $O/stag_$i.json 2>/dev/null || exit 1
 done
 python3 - $O <<'PY'
 import json, sys, glob

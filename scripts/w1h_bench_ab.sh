@@ -8,8 +8,8 @@ timeout -k 10 240 python -u -m pytest $R/tests/test_gpu_kernels.py -x -v --timeo
   -k "w1 or stag or fused_downsample" > $O/pytest.log 2>&1
 rc=$?; tail -2 $O/pytest.log; [ $rc -ne 0 ] && exit $rc
 run() {  # tag lib
-  if [ "$2" = "-" ]; then timeout -k 10 120 python3 bench.py --steps 40 --no-cpu-baseline --no-exact-mode > $O/$1.json 2>/dev/null
-  else DRNMI_LIB=$R/diag/$2 timeout -k 10 120 python3 bench.py --steps 40 --no-cpu-baseline --no-exact-mode > $O/$1.json 2>/dev/null; fi
+  if [ "$2" = "-" ]; then timeout -k 10 120 python3 bench.py --full --steps 40 --no-cpu-baseline --no-exact-mode > $O/$1.json 2>/dev/null
+  else DRNMI_LIB=$R/diag/$2 timeout -k 10 120 python3 bench.py --full --steps 40 --no-cpu-baseline --no-exact-mode > $O/$1.json 2>/dev/null; fi
 }
 # ABBA order, so neither library always runs on the warmer box
 for i in 1 2; do

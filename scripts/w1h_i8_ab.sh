@@ -8,7 +8,7 @@ O=$R/gpurun_out/$1; mkdir -p $O
 timeout -k 10 400 python -u -m pytest $R/tests/test_gpu_int8.py $R/tests/test_gpu_head_nhwc.py $R/tests/test_gpu_configs.py \
   -x -v --timeout 120 --timeout-method thread -k "int8 or i8 or c5" > $O/pytest.log 2>&1
 rc=$?; tail -2 $O/pytest.log; [ $rc -ne 0 ] && exit $rc
-ARGS="--precision int8 --steps 40 --no-cpu-baseline"
+ARGS="--full --precision int8 --steps 40 --no-cpu-baseline"
 run() {  # tag layer4
   if [ "$2" = "new" ]; then timeout -k 10 150 python3 bench.py $ARGS > $O/$1.json 2>/dev/null
   else DRNMI_LIB=$R/diag/libdrnmi_base.so timeout -k 10 150 python3 -c "

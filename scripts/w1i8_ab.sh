@@ -9,8 +9,8 @@ timeout -k 10 300 python -u -m pytest $R/tests/test_gpu_int8.py $R/tests/test_gp
   --timeout-method thread > $O/pytest.log 2>&1
 rc=$?; tail -2 $O/pytest.log; [ $rc -ne 0 ] && exit $rc
 run() {  # tag lib
-  if [ "$2" = "-" ]; then timeout -k 10 150 python3 bench.py --precision int8 --steps 40 --no-cpu-baseline > $O/$1.json 2>/dev/null
-  else DRNMI_LIB=$R/diag/$2 timeout -k 10 150 python3 bench.py --precision int8 --steps 40 --no-cpu-baseline > $O/$1.json 2>/dev/null; fi
+  if [ "$2" = "-" ]; then timeout -k 10 150 python3 bench.py --full --precision int8 --steps 40 --no-cpu-baseline > $O/$1.json 2>/dev/null
+  else DRNMI_LIB=$R/diag/$2 timeout -k 10 150 python3 bench.py --full --precision int8 --steps 40 --no-cpu-baseline > $O/$1.json 2>/dev/null; fi
 }
 for i in 1 2; do
   run w1_a$i - || exit 1; run base_a$i libdrnmi_base.so || exit 1

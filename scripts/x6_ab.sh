@@ -11,8 +11,8 @@ rc=$?; tail -2 $O/pytest.log; [ $rc -ne 0 ] && exit $rc
 timeout -k 10 120 python3 $R/scripts/x6_micro.py > $O/micro_new.log 2>&1 || exit 1
 DRNMI_LIB=$R/diag/libdrnmi_base.so timeout -k 10 120 python3 $R/scripts/x6_micro.py > $O/micro_base.log 2>&1 || exit 1
 for rep in 0 1; do
-  timeout -k 10 200 python3 bench.py --precision fp32x --steps 10 --warmup 3 --no-cpu-baseline > $O/x_new_$rep.json 2>/dev/null || exit 1
-  DRNMI_LIB=$R/diag/libdrnmi_base.so timeout -k 10 200 python3 bench.py --precision fp32x --steps 10 --warmup 3 --no-cpu-baseline > $O/x_base_$rep.json 2>/dev/null || exit 1
+  timeout -k 10 200 python3 bench.py --full --precision fp32x --steps 10 --warmup 3 --no-cpu-baseline > $O/x_new_$rep.json 2>/dev/null || exit 1
+  DRNMI_LIB=$R/diag/libdrnmi_base.so timeout -k 10 200 python3 bench.py --full --precision fp32x --steps 10 --warmup 3 --no-cpu-baseline > $O/x_base_$rep.json 2>/dev/null || exit 1
   DRNMI_LIB=$R/diag/libdrnmi_base.so timeout -k 10 200 python3 bench_finetune.py --precision fp32x --no-cpu-baseline > $O/ft_base_$rep.json 2>/dev/null || exit 1
   timeout -k 10 200 python3 bench_finetune.py --precision fp32x --no-cpu-baseline > $O/ft_new_$rep.json 2>/dev/null || exit 1
 done

@@ -31,10 +31,39 @@ def pytest_collection_modifyitems(config, items):
             it.add_marker(skip)
 
 
+class NpzParts:
+    """The arrays of stem.0.npz, stem.1.npz, ... (tests/golden/make_golden.py save_parts) as one
+    read-only mapping with np.load's behaviour: `key in parts`, `parts[key]` (a fresh array per
+    access), `parts.files`."""
+
+    def __init__(self, stem):
+        import glob
+        import numpy as np
+        paths = sorted(glob.glob(stem + ".*.npz"), key=lambda p: int(p[len(stem) + 1:-len(".npz")]))
+        if not paths:
+            raise FileNotFoundError(stem + ".*.npz")
+        self._where, self.files = {}, []
+        for p in paths:
+            z = np.load(p, allow_pickle=False)
+            for k in z.files:
+                if k in self._where:
+                    raise ValueError(f"{k} is in two parts of {stem}")
+                self._where[k] = z
+                self.files.append(k)
+
+    def __contains__(self, key):
+        return key in self._where
+
+    def __getitem__(self, key):
+        return self._where[key][key]
+
+    def keys(self):
+        return list(self.files)
+
+
 @pytest.fixture(scope="session")
 def golden_forward():
-    import numpy as np
-    return np.load(os.path.join(GOLDEN, "forward.npz"), allow_pickle=False)
+    return NpzParts(os.path.join(GOLDEN, "forward"))
 
 
 @pytest.fixture(scope="session")

@@ -5,7 +5,7 @@ never travels):   python tests/golden/make_golden.py [--reference /root/referenc
 
 What it records (all inputs are synthetic and seeded; weights come from
 drnmi.weights.synth_state_dict, which keys only on state_dict names):
-  forward.npz   reference lmodels/drnseg.DRNSeg (D-22) and drn.drn_d_38 / drn_d_54 wrapped
+  forward.N.npz reference lmodels/drnseg.DRNSeg (D-22) and drn.drn_d_38 / drn_d_54 wrapped
                 in the same seg/up head, fp32 CPU: logits, labels, log-probs (full or
                 subsampled), per-stage sums, plus the preprocessed input produced by the
                 reference data_transforms (PIL -> ToTensorVideoImage -> Normalize).
@@ -41,6 +41,35 @@ sys.path.insert(0, os.path.join(REPO, "video-seg-model-compress_amd"))
 from drnmi.weights import synth_frames, synth_state_dict  # noqa: E402
 
 SMALL_MASK = 1 << 16
+
+
+PART_LIMIT = 900 * 1024     # bytes per fixture file (no committed file may exceed 1 MiB)
+
+
+def save_parts(stem: str, arrays: dict) -> list:
+    """np.savez_compressed into stem.0.npz, stem.1.npz, ...: whole arrays in their order, a new
+    part whenever the next array would take the file past PART_LIMIT (tests/conftest.py reads the
+    parts back as one mapping).  Returns the paths written."""
+    import glob
+    import io
+    for old in glob.glob(stem + ".*.npz"):
+        os.remove(old)
+    parts, size = [{}], 0
+    for k, v in arrays.items():
+        buf = io.BytesIO()
+        np.savez_compressed(buf, **{k: v})
+        n = len(buf.getvalue())
+        if n > PART_LIMIT:
+            raise ValueError(f"{k}: {n} B compressed does not fit a {PART_LIMIT} B part")
+        if parts[-1] and size + n > PART_LIMIT:
+            parts.append({})
+            size = 0
+        parts[-1][k] = v
+        size += n
+    paths = [f"{stem}.{i}.npz" for i in range(len(parts))]
+    for path, part in zip(paths, parts):
+        np.savez_compressed(path, **part)
+    return paths
 
 
 def sha(arr: np.ndarray) -> str:
@@ -373,7 +402,7 @@ def main():
         os.chdir(tmp)      # reference pruners write progress files into cwd
         try:
             if args.only in ("", "forward"):
-                np.savez_compressed(os.path.join(HERE, "forward.npz"), **forward_cases())
+                save_parts(os.path.join(HERE, "forward"), forward_cases())
             if args.only in ("", "masks"):
                 np.savez_compressed(os.path.join(HERE, "masks.npz"), **mask_cases(tmp))
             if args.only in ("", "train"):

@@ -68,6 +68,49 @@ def test_single_rank_stub():
     assert d["n_gpus"] == 1 and len(d["per_rank"]) == 1
 
 
+def test_plain_run_is_the_default_and_host_frames_needs_full():
+    assert bench.parse([]).full is False and bench.parse([]).dump_outputs is None
+    assert bench.parse(["--full", "--host-frames"]).host_frames
+    with pytest.raises(SystemExit):
+        bench.parse(["--host-frames"])
+
+
+def test_dump_outputs_same_arguments_same_file(tmp_path, capsys):
+    """--dump-outputs writes what the last timed step returned as float32 .npy; a second run with
+    the same arguments writes the same bytes (same seeded frames), and --steps sets the number
+    of timed steps the line reports."""
+    import numpy as np
+    got = []
+    for d in ("a", "b"):
+        bench.main([*SMALL, "--dump-outputs", str(tmp_path / d)])
+        line = json.loads(capsys.readouterr().out.strip().splitlines()[-1])
+        assert line["steps"] == 3 and line["ms_per_step"] > 0
+        assert os.listdir(tmp_path / d) == ["frame_means.npy"]
+        got.append(np.load(tmp_path / d / "frame_means.npy"))
+    assert got[0].dtype == np.float32 and got[0].shape == (2,)
+    assert np.array_equal(got[0], got[1])
+    assert 100.0 < got[0].mean() < 155.0                             # means of uniform uint8 frames
+
+
+def test_dump_outputs_samples_above_the_budget(tmp_path):
+    """An array above the byte budget is written as a fixed sample: the same sorted flat indices
+    for every array of that shape, within the budget, each rank under its own name."""
+    import numpy as np
+    a = (np.arange(6000, dtype=np.int64) % 19).astype(np.uint8).reshape(3, 20, 100)
+    full = bench.dump_outputs(str(tmp_path), "labels", a, budget=4 * a.size)
+    assert os.path.basename(full) == "labels.npy"
+    assert np.array_equal(np.load(full), a.astype(np.float32))       # fits: whole array, its shape kept
+    p0 = bench.dump_outputs(str(tmp_path), "labels", a, world=2, rank=0, budget=8000)
+    p1 = bench.dump_outputs(str(tmp_path), "labels", a + 1, world=2, rank=1, budget=8000)
+    assert [os.path.basename(p) for p in (p0, p1)] == ["labels_rank0.npy", "labels_rank1.npy"]
+    s0, s1 = np.load(p0), np.load(p1)
+    assert s0.dtype == np.float32 and s0.shape == (1000,) and s0.nbytes + s1.nbytes <= 8000
+    assert np.array_equal(s1, s0 + 1)                                # the same elements of both arrays
+    flat = a.reshape(-1).astype(np.float32)
+    assert not np.array_equal(s0, flat[:1000]) and set(s0) <= set(flat)
+    assert bench.DUMP_BUDGET <= 64 * 10**6
+
+
 FT_SMALL = ["--stub-step", "--steps", "3", "--warmup", "1", "--batch", "2"]
 
 

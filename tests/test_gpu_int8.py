@@ -4,7 +4,7 @@ against oracle/int8_oracle.py, and the int8 network against the reference golden
 The reference has no quantisation code, so the int8 scheme is ours ("parity unpinned" vs the
 reference): the gates are (1) exact arithmetic parity of every int8 launch with the numpy
 restatement on the launch's own inputs, (2) label agreement of the int8 network with the
-reference fp32 forward (tests/golden/forward.npz).
+reference fp32 forward (tests/golden/forward.N.npz).
 """
 import ctypes
 
