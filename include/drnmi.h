@@ -236,9 +236,25 @@ int drnmi_weight_unit_mask(const void* wgt, int32_t dtype, int32_t rows_pad, int
  *   drnmi_quantize_i8: y[i] = clamp(rint(x[i] * inv_scale), -127, 127) over n elements
  *     (x BF16 or F32, n % 8 == 0; one fp32 multiply, round-half-even) -- the bf16 -> int8
  *     boundary in front of the first int8 conv.
- *   drnmi_absmax: *out = max |x[i]| (device float; calibration of the activation scales). */
+ *   drnmi_absmax: *out = max |x[i]| (device float; calibration of the activation scales).
+ *   drnmi_abs_histogram: the exact distribution of |x|, for scales other than absmax / 127 and
+ *     for calibration streamed over many batches.  hist is a device array of DRNMI_HIST_BINS
+ *     64-bit counters; x[i] (BF16 or F32, n % 8 == 0) adds 1 to bin
+ *     (bits((float)x[i]) & 0x7fffffff) >> 16.  For BF16 input that is one bin per representable
+ *     magnitude: bin b counts the elements whose |x| has the bf16 pattern b, +0 and -0 both in
+ *     bin 0, inf / NaN in bins 0x7f80 and up.  F32 input is binned by TRUNCATION to its top 16
+ *     bits (bin b counts |x| in [value(b), value(b + 1))), not by rounding to bf16.  The call
+ *     ACCUMULATES and never zeroes hist: zero it once, then stream any number of batches through
+ *     (64-bit counters do not wrap).  Percentile and MSE-optimal scales are derived from the
+ *     histogram on the host (drnmi/calibrate.py); the scales themselves are plain floats a
+ *     deployment stores next to its weights (DRNSeg.int8_state / load_int8_state, and
+ *     <checkpoint>.int8.json of drnmi/checkpoint.py), so no calibration frames are needed at
+ *     start-up.  NULL pointers, n % 8 != 0 or another dtype: DRNMI_EINVAL before any HIP call;
+ *     n == 0: DRNMI_OK, nothing launched. */
+#define DRNMI_HIST_BINS 32768
 int drnmi_quantize_i8(const void* x, int32_t dtype, int8_t* y, int64_t n, float inv_scale, void* stream);
 int drnmi_absmax(const void* x, int32_t dtype, int64_t n, float* out, void* stream);
+int drnmi_abs_histogram(const void* x, int32_t dtype, int64_t n, int64_t* hist, void* stream);
 
 /* Name of the kernel (template instance) drnmi_conv2d_bn_act would launch for these
  * arguments, e.g. "conv_big_kernel<3, 128, 2, 2>"; NULL if none.  No launch, no GPU needed.

@@ -6,8 +6,9 @@
 //   * activations: per-tensor symmetric int8 with a calibrated scale s (absmax / 127 over a
 //     calibration batch): q = clamp(rint(x * (1/s)), -127, 127).  The conv that produces an int8
 //     activation quantises in its epilogue; this file serves the bf16 -> int8 boundary (the first
-//     int8 layer's input) and the calibration absmax.
-// Both kernels are HBM-bound streams: 16-B loads per lane, grid-stride (no reuse to place).
+//     int8 layer's input), the calibration absmax and the calibration |x| histogram (from which
+//     drnmi/calibrate.py derives absmax, percentile or MSE-optimal scales over many batches).
+// All three kernels are HBM-bound streams: 16-B loads per lane, grid-stride (no reuse to place).
 #include "common.h"
 #include "kernels.h"
 
@@ -72,6 +73,96 @@ unsigned stream_blocks(int64_t n8) {
   return static_cast<unsigned>(b < 4096 ? (b > 0 ? b : 1) : 4096);
 }
 
+// Exact |x| histogram: element x adds 1 to bin (bits(float(x)) & 0x7fffffff) >> 16, one bin per
+// bf16 magnitude.  The same HBM-bound stream as absmax_kernel, counted in a workgroup-private LDS
+// table of DRNMI_HIST_BINS uint32 (128 KiB: one workgroup per CU, hence 1024 lanes in it, each
+// with four 16-B loads in flight) and flushed with one 64-bit global atomic per nonzero bin.
+//   * the grid is one workgroup per CU at most: the zeroing and the flush of the table are paid
+//     once per CU, and a workgroup's share of the elements, with it every LDS counter, stays
+//     below 2^32 for n < 2^39;
+//   * zeros (more than half of a post-ReLU tensor) never reach the LDS atomics: each lane counts
+//     them in a register, a wave adds its sum to bin 0 once;
+//   * a lane merges a run of equal bins among its 8 elements into one LDS add (a constant tensor
+//     costs one same-address add per lane and load instead of eight).
+constexpr int kHistThreads = 1024;
+constexpr int kHistUnroll = 4;
+constexpr size_t kHistLds = static_cast<size_t>(DRNMI_HIST_BINS) * sizeof(uint32_t);
+int g_hist_wgs = 0;                      // workgroups of a full grid (the device's CU count)
+
+template <typename T> __device__ __forceinline__ uint32_t abs_bin(T v);
+template <> __device__ __forceinline__ uint32_t abs_bin<bf16_t>(bf16_t v) { return v & 0x7fffu; }
+template <> __device__ __forceinline__ uint32_t abs_bin<float>(float v) { return (__float_as_uint(v) & 0x7fffffffu) >> 16; }
+
+template <typename T>
+__device__ __forceinline__ void count8(const Vec8<T>& v, uint32_t* bins, uint32_t& zeros) {
+  const T* e = reinterpret_cast<const T*>(&v);
+  uint32_t cur = 0, run = 0;             // pending run of one nonzero bin (cur == 0: none)
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    const uint32_t b = abs_bin<T>(e[j]);
+    if (b == 0) {
+      ++zeros;
+    } else if (b == cur) {
+      ++run;
+    } else {
+      if (cur != 0) atomicAdd(&bins[cur], run);
+      cur = b;
+      run = 1;
+    }
+  }
+  if (cur != 0) atomicAdd(&bins[cur], run);
+}
+
+template <typename T>
+__global__ void __launch_bounds__(kHistThreads) abs_histogram_kernel(const T* __restrict__ x, int64_t n8,
+                                                                     unsigned long long* __restrict__ hist) {
+  extern __shared__ uint32_t bins[];
+  for (int b = threadIdx.x * 4; b < DRNMI_HIST_BINS; b += kHistThreads * 4)
+    *reinterpret_cast<uint4*>(bins + b) = make_uint4(0, 0, 0, 0);
+  __syncthreads();
+  const int64_t stride = static_cast<int64_t>(gridDim.x) * blockDim.x;
+  int64_t i = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
+  uint32_t zeros = 0;
+  for (; i + (kHistUnroll - 1) * stride < n8; i += kHistUnroll * stride) {
+    Vec8<T> v[kHistUnroll];
+#pragma unroll
+    for (int u = 0; u < kHistUnroll; ++u) v[u] = Vec8<T>::load(x + (i + u * stride) * 8);
+#pragma unroll
+    for (int u = 0; u < kHistUnroll; ++u) count8<T>(v[u], bins, zeros);
+  }
+  for (; i < n8; i += stride) count8<T>(Vec8<T>::load(x + i * 8), bins, zeros);
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) zeros += static_cast<uint32_t>(__shfl_xor(static_cast<int>(zeros), o));
+  if ((threadIdx.x & 63) == 0 && zeros != 0) atomicAdd(&bins[0], zeros);
+  __syncthreads();
+  for (int b = threadIdx.x; b < DRNMI_HIST_BINS; b += kHistThreads) {
+    const uint32_t c = bins[b];
+    if (c != 0) atomicAdd(&hist[b], static_cast<unsigned long long>(c));
+  }
+}
+
+template <typename T>
+hipError_t launch_abs_histogram(const T* x, int64_t n8, int64_t* hist, hipStream_t s) {
+  static bool attr_set = false;          // > 64 KiB of dynamic LDS is an opt-in per kernel
+  if (!attr_set) {
+    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&abs_histogram_kernel<T>),
+                                             hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(kHistLds));
+    if (e != hipSuccess) return e;
+    attr_set = true;
+  }
+  if (g_hist_wgs == 0) {
+    int dev = 0, cus = 0;
+    if (hipGetDevice(&dev) != hipSuccess ||
+        hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0)
+      cus = 256;
+    g_hist_wgs = cus;
+  }
+  const int64_t b = (n8 + kHistThreads - 1) / kHistThreads;
+  hipLaunchKernelGGL(abs_histogram_kernel<T>, dim3(static_cast<unsigned>(b < g_hist_wgs ? b : g_hist_wgs)),
+                     dim3(kHistThreads), kHistLds, s, x, n8, reinterpret_cast<unsigned long long*>(hist));
+  return hipGetLastError();
+}
+
 }  // namespace
 }  // namespace drnmi
 
@@ -91,6 +182,15 @@ extern "C" int drnmi_quantize_i8(const void* x, int32_t dtype, int8_t* y, int64_
   else
     return DRNMI_EINVAL;
   return static_cast<int>(hipGetLastError());
+}
+
+extern "C" int drnmi_abs_histogram(const void* x, int32_t dtype, int64_t n, int64_t* hist, void* stream) {
+  if (x == nullptr || hist == nullptr || n < 0 || n % 8 != 0 || (dtype != DRNMI_BF16 && dtype != DRNMI_F32))
+    return DRNMI_EINVAL;
+  if (n == 0) return DRNMI_OK;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (dtype == DRNMI_BF16) return static_cast<int>(launch_abs_histogram(static_cast<const bf16_t*>(x), n / 8, hist, s));
+  return static_cast<int>(launch_abs_histogram(static_cast<const float*>(x), n / 8, hist, s));
 }
 
 extern "C" int drnmi_absmax(const void* x, int32_t dtype, int64_t n, float* out, void* stream) {

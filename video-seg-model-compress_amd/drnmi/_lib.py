@@ -12,6 +12,7 @@ from .build import LIB_PATH
 
 DRNMI_F32, DRNMI_BF16, DRNMI_U8, DRNMI_I64, DRNMI_I8, DRNMI_F32X3 = 0, 1, 2, 3, 4, 5
 ALGO_IGEMM, ALGO_PATCH = 0, 1
+HIST_BINS = 32768        # include/drnmi.h DRNMI_HIST_BINS
 
 _STATUS = {-1: "DRNMI_EINVAL (bad shape/stride/dtype)", -2: "DRNMI_ENOTSUP (no kernel for this config)"}
 
@@ -123,6 +124,7 @@ SIGNATURES = {
     "drnmi_weight_unit_mask": (ctypes.c_int, [_VP, _I32, _I32, _I32, _VP, _VP, _VP]),
     "drnmi_quantize_i8": (ctypes.c_int, [_VP, _I32, _VP, _I64, _F32, _VP]),
     "drnmi_absmax": (ctypes.c_int, [_VP, _I32, _I64, _VP, _VP]),
+    "drnmi_abs_histogram": (ctypes.c_int, [_VP, _I32, _I64, _VP, _VP]),
     "drnmi_version": (ctypes.c_char_p, []),
     "drnmi_abi_version": (ctypes.c_int32, []),
     "drnmi_conv_args_size": (ctypes.c_int64, []),

@@ -20,8 +20,8 @@ Differences by design:
     MFMA), "fp32x" (fp32-accurate arithmetic on the bf16 MFMA pipe: exact 3-way bf16 splits,
     6 products, for every conv with cin >= 32; parity gates as fp32, ~3x faster), "bf16"
     (perf mode, fp32 accumulation) or "int8" (W8A8 for the cin >= 64 convs,
-    config C5; needs calibrate_int8() first — the reference has no quantisation, so this
-    mode is ours) via set_precision().
+    config C5; needs calibrate_int8() or load_int8_state() first — the reference has no
+    quantisation, so this mode is ours) via set_precision().
   * segment(frames_u8) is the fused seg_video path (seg_video_old_no_plot.py:157-169:
     normalise -> model(img)[0] -> torch.max(final, 1)) producing uint8 labels without
     materialising the 19-plane log-prob tensor.
@@ -85,6 +85,9 @@ class DRNSeg(nn.Module):
         self.block_sparse = False    # opt-in: measured slower than dense below ~60 % zero units
         self._graph = lower_drnseg(self.layer, self.seg)
         self._act_scales = None      # int8: per-value activation scales (calibrate_int8)
+        self._int8_hists = None      # value -> |x| histogram of the last histogram calibration
+        self._int8_method = None     # how _act_scales were derived (int8_state)
+        self._int8_percentile = None
         self._packed = {}
         self._plans = {}
         self._pack_key = None
@@ -97,11 +100,13 @@ class DRNSeg(nn.Module):
     # copies and unpickled modules register a handle of their own: the handle keys the
     # torch.ops.drnmi.* state, and a copied integer would dispatch to the ORIGINAL model's
     # weights.  Packed weights and launch plans hold device pointers of this instance: not copied.
+    # The int8 activation scales travel with the copy; the calibration histograms behind them
+    # (256 KiB per activation) do not.
     def __getstate__(self):
         st = self.__dict__.copy()
         st.pop("_handle", None)
         st.update(_packed={}, _plans={}, _pack_key=None, _key_tensors=None, _key_ids=None, _key_dicts=[],
-                  timing_hook=None)
+                  timing_hook=None, _int8_hists=None)
         st.pop("_train_runner", None)
         return st
 
@@ -227,10 +232,23 @@ class DRNSeg(nn.Module):
         return self
 
     @torch.no_grad()
-    def calibrate_int8(self, frames_u8: torch.Tensor, mean=INFO_MEAN, std=INFO_STD, bgr: bool = False):
+    def calibrate_int8(self, frames_u8, mean=INFO_MEAN, std=INFO_STD, bgr: bool = False,
+                       method: str = "absmax", percentile: float = 99.99):
         """Per-tensor activation scales for precision "int8": the bf16 engine runs the
         calibration frames (uint8 [B,H,W,3] on the GPU) and every activation's scale is
-        absmax / 127 (drnmi_absmax on the HBM buffer).  Re-packs the int8 weights."""
+        absmax / 127 (drnmi_absmax on the HBM buffer).  Re-packs the int8 weights.
+
+        frames_u8 may also be an iterable of such batches (one shape; a DataLoader, a list), and
+        method "percentile" or "mse" (drnmi.calibrate.scale_from_histogram) picks a clip below
+        the maximum.  Anything but one tensor with method "absmax" accumulates an exact |x|
+        histogram per activation over all batches (drnmi_abs_histogram, 256 KiB each) and derives
+        the scales from it; the histograms stay available (int8_histograms, rescale_int8)."""
+        from .calibrate import METHODS
+        if method not in METHODS:
+            raise ValueError(f"method must be one of {METHODS}, got {method!r}")
+        if not (isinstance(frames_u8, torch.Tensor) and method == "absmax"):
+            batches = [frames_u8] if isinstance(frames_u8, torch.Tensor) else frames_u8
+            return self._calibrate_int8_hist(batches, mean, std, bgr, method, percentile)
         import ctypes
         prev = self.precision
         self.precision = "bf16"
@@ -253,11 +271,88 @@ class DRNSeg(nn.Module):
         finally:
             self.precision = prev
             self._plans = {k: p for k, p in self._plans.items() if not k[-1]}   # drop the keep_all plan
+        self._int8_hists = None
+        return self._install_act_scales(scales, "absmax", None)
+
+    def _install_act_scales(self, scales, method, percentile):
+        """New activation scales: the int8 pack and plans built on the old ones go."""
         self._act_scales = scales
+        self._int8_method, self._int8_percentile = method, percentile
         self._packed.pop("int8", None)
         self._plans = {k: p for k, p in self._plans.items() if k[0] != "int8"}
         self._pack_key = None
         return scales
+
+    def _int8_values(self):
+        """The graph values that carry an activation scale (all but the input and the logits)."""
+        return [v for v in self._graph.channels if v not in ("input", "logits")]
+
+    def _calibrate_int8_hist(self, batches, mean, std, bgr, method, percentile):
+        from .ops import abs_histogram
+        prev = self.precision
+        self.precision = "bf16"
+        hists, shape = {}, None
+        try:
+            for frames in batches:
+                if not isinstance(frames, torch.Tensor) or frames.dtype != torch.uint8 or frames.dim() != 4 \
+                        or frames.shape[3] != 3:
+                    raise ValueError("calibrate_int8 expects uint8 [B,H,W,3] batches")
+                if shape is None:
+                    shape = tuple(frames.shape)
+                elif tuple(frames.shape) != shape:
+                    raise ValueError(f"calibrate_int8: batches must share one shape, got {shape} and "
+                                     f"{tuple(frames.shape)}")
+                plan, stream = self._prepare(shape[0], shape[1], shape[2], frames.device, keep_all=True)
+                plan.ingest_u8(frames.contiguous(), mean, std, bgr, stream)
+                plan.run_backbone(stream)
+                for v in self._int8_values():
+                    hists[v] = abs_histogram(plan.bufs[v], hists.get(v))
+            if shape is None:
+                raise ValueError("calibrate_int8: no calibration batches")
+            hists = {v: h.cpu().numpy() for v, h in hists.items()}
+        finally:
+            self.precision = prev
+            self._plans = {k: p for k, p in self._plans.items() if not k[-1]}   # drop the keep_all plan
+        self._int8_hists = hists
+        return self.rescale_int8(method, percentile)
+
+    def int8_histograms(self):
+        """{value: int64 numpy [32768]} |x| histograms of the last histogram calibration
+        (drnmi.calibrate.bin_values() gives the bins' magnitudes), or None if there was none."""
+        return self._int8_hists
+
+    def rescale_int8(self, method: str, percentile: float = 99.99):
+        """Re-derive the activation scales from the stored histograms with another method, without
+        running frames again."""
+        from .calibrate import scale_from_histogram
+        if self._int8_hists is None:
+            raise RuntimeError("rescale_int8 needs the histograms of calibrate_int8(batches, method=...)")
+        scales = {v: scale_from_histogram(h, method, percentile) for v, h in self._int8_hists.items()}
+        return self._install_act_scales(scales, method, float(percentile) if method == "percentile" else None)
+
+    def int8_state(self) -> dict:
+        """The calibrated activation scales as plain data (JSON-safe: a Python float's repr
+        round-trips exactly), to store next to the weights; see load_int8_state."""
+        if self._act_scales is None:
+            raise RuntimeError("no int8 activation scales: call calibrate_int8 or load_int8_state first")
+        return {"version": 1, "method": self._int8_method, "percentile": self._int8_percentile,
+                "scales": {v: float(s) for v, s in self._act_scales.items()}}
+
+    def load_int8_state(self, state: dict) -> "DRNSeg":
+        """Install activation scales saved by int8_state(): no calibration frames needed."""
+        if not isinstance(state, dict) or state.get("version") != 1 or not isinstance(state.get("scales"), dict):
+            raise ValueError("not an int8 state of version 1")
+        scales, want = state["scales"], set(self._int8_values())
+        if set(scales) != want:
+            raise ValueError(f"int8 state does not match this model's activations: missing "
+                             f"{sorted(want - set(scales))}, unknown {sorted(set(scales) - want)}")
+        for v, s in scales.items():
+            if isinstance(s, bool) or not isinstance(s, (int, float)) or not math.isfinite(s) or not s > 0:
+                raise ValueError(f"int8 state: scale of {v!r} is {s!r}, not a finite positive number")
+        self._int8_hists = None
+        self._install_act_scales({v: float(scales[v]) for v in self._int8_values()}, state.get("method"),
+                                 state.get("percentile"))
+        return self
 
     def set_block_sparse(self, enabled: bool) -> "DRNSeg":
         """bf16: let pruned (all-zero) 16 x 32 weight units skip their MFMAs (opt-in; results are
@@ -327,7 +422,8 @@ class DRNSeg(nn.Module):
                             del self._plans[pkey]
             self._pack_key = key
         if self.precision == "int8" and self._act_scales is None:
-            raise RuntimeError("precision 'int8' needs activation scales: call calibrate_int8(frames) first")
+            raise RuntimeError("precision 'int8' needs activation scales: call calibrate_int8(frames) or "
+                               "load_int8_state(saved) first")
         pk = self._packed.get(self.precision)
         if pk is None:
             pk = PackedNet(self._graph, self.precision, device, block_sparse=self.block_sparse,

@@ -246,3 +246,22 @@ def argmax_nchw(x: torch.Tensor, label_dtype=torch.int64) -> torch.Tensor:
     _lib.check(_lib.load().drnmi_argmax_nchw_f32(x.contiguous().data_ptr(), n, c, h * w, lab.data_ptr(), code,
                                                  ctypes.c_void_p(_lib.stream_ptr(x.device))), "argmax_nchw")
     return lab
+
+
+def abs_histogram(x: torch.Tensor, hist: torch.Tensor | None = None) -> torch.Tensor:
+    """Exact |x| histogram of a bf16 / fp32 tensor (numel % 8 == 0) -> int64 [32768], one bin per
+    bf16 magnitude: bin (bits(float(x)) & 0x7fffffff) >> 16 (include/drnmi.h drnmi_abs_histogram).
+    hist=None allocates a zeroed histogram; a given one is accumulated into (streamed calibration)."""
+    if x.dtype not in (torch.bfloat16, torch.float32):
+        raise ValueError("abs_histogram expects a bf16 or fp32 tensor")
+    dev = x.device
+    if hist is None:
+        hist = torch.zeros(_lib.HIST_BINS, dtype=torch.int64, device=dev)
+    elif tuple(hist.shape) != (_lib.HIST_BINS,) or hist.dtype != torch.int64 or not hist.is_contiguous() \
+            or hist.device != dev:
+        raise ValueError(f"hist must be a contiguous int64 [{_lib.HIST_BINS}] tensor on {dev}")
+    code = _lib.DRNMI_BF16 if x.dtype == torch.bfloat16 else _lib.DRNMI_F32
+    x = x.contiguous()
+    _lib.check(_lib.load().drnmi_abs_histogram(x.data_ptr(), code, x.numel(), hist.data_ptr(),
+                                               ctypes.c_void_p(_lib.stream_ptr(dev))), "abs_histogram")
+    return hist
