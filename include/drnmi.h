@@ -361,6 +361,33 @@ int drnmi_resize_bilinear_f32(const float* src, int32_t planes, int32_t h, int32
 int drnmi_argmax_nchw_f32(const float* x, int32_t n, int32_t c, int64_t hw, void* labels, int32_t label_dtype,
                           void* stream);
 
+/* Label maps to pictures (csrc/render.hip): the palette colouring that ends every reference driver
+ * (CITYSCAPE_PALETTE[pred], seg_video_old_no_plot.py:166-170; save_colorful_images,
+ * semantic_seg.py:415-426) and the overlay of that colour image on the input frame (the
+ * seg_video*.py variants, alpha = 0.6).  One streaming kernel on the caller's stream, no
+ * allocation (graph-capturable); it serves every precision and head path.
+ *   labels: [n][lh][lw] uint8 or int64 (label_dtype, the codes of drnmi_up8_labels_nhwc);
+ *   palette: device uint8 [P][3] RGB, 1 <= P <= 256; out: uint8 [n][oh][ow][3], oh <= lh, ow <= lw;
+ *   frames: uint8 [n][oh][ow][3], or NULL for the colour image alone (out == frames is allowed).
+ * Exact integer arithmetic:
+ *   crop    output pixel (y, x) takes label (y, x): the top-left oh x ow of the label map.  The
+ *           ConvTranspose2d head (k16, s8, p4) keeps output pixel (y, x) over input pixel (y, x);
+ *           the extra rows / columns of a 300 -> 304 map come from the stride ceil chain and have
+ *           no source pixel.
+ *   colour  c = palette[min(label, P - 1)]: labels at or above P (the ignore value 255 too) and
+ *           negative int64 labels take the last entry -- entry 19 of the 20-entry Cityscapes
+ *           palette is black, the reference's `color_image[output == 255] = CITYSCAPE_PALETTE[-1]`.
+ *           swap_rb != 0 writes the entry as B, G, R (BGR frames going back to a cv2 writer).
+ *   overlay per channel out = (f * (256 - a) + c * a + 128) >> 8 with a = alpha_q8 in 0..256:
+ *           a = 0 returns the frame, a = 256 the colour, both exactly.  alpha_q8 is ignored when
+ *           frames == NULL.  (matplotlib's float compositing is not reproduced; this is the contract.)
+ * DRNMI_EINVAL before any HIP call: NULL labels / palette / out, another dtype, P outside 1..256,
+ * a non-positive size, oh > lh, ow > lw, alpha_q8 outside 0..256 (with frames), or n * lh * lw above
+ * 2^40 elements (the kernel indexes in 64 bits; the bound keeps every byte offset inside them). */
+int drnmi_render_labels(const void* labels, int32_t label_dtype, int32_t n, int32_t lh, int32_t lw,
+                        const uint8_t* frames, const uint8_t* palette, int32_t P, int32_t alpha_q8, int32_t swap_rb,
+                        uint8_t* out, int32_t oh, int32_t ow, void* stream);
+
 /* Multi-tensor in-place mask apply: w[t][i] *= m[t][i] for every tensor t.
  * Replaces Pruner.apply_masks (pruners/Pruner.py:17-20, same body BlockPruner.py:27-30,
  * SRMBRepMasker.py:20-23): one launch for all masked layers instead of one ATen mul_ per

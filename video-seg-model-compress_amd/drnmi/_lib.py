@@ -93,6 +93,8 @@ SIGNATURES = {
     "drnmi_resize_bilinear_u8": (ctypes.c_int, [_VP, _I32, _I32, _I32, _VP, _I32, _I32, _VP, _I64, _VP]),
     "drnmi_resize_bilinear_f32": (ctypes.c_int, [_VP, _I32, _I32, _I32, _VP, _I32, _I32, _I32, _VP, _I64, _VP]),
     "drnmi_argmax_nchw_f32": (ctypes.c_int, [_VP, _I32, _I32, _I64, _VP, _I32, _VP]),
+    "drnmi_render_labels": (ctypes.c_int, [_VP, _I32, _I32, _I32, _I32, _VP, _VP, _I32, _I32, _I32, _VP, _I32, _I32,
+                                           _VP]),
     "drnmi_mask_apply_f32": (ctypes.c_int, [_I32, _VP, _VP, _VP, _VP]),
     "drnmi_mask_apply_bits_f32": (ctypes.c_int, [_I32, _VP, _VP, _VP, _VP]),
     "drnmi_confusion_matrix": (ctypes.c_int, [_VP, _I32, _VP, _I32, _I64, _I32, _VP, _VP]),

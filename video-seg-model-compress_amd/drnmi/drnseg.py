@@ -24,7 +24,9 @@ Differences by design:
     quantisation, so this mode is ours) via set_precision().
   * segment(frames_u8) is the fused seg_video path (seg_video_old_no_plot.py:157-169:
     normalise -> model(img)[0] -> torch.max(final, 1)) producing uint8 labels without
-    materialising the 19-plane log-prob tensor.
+    materialising the 19-plane log-prob tensor.  segment(render="color" | "overlay") also returns
+    the picture that loop ends in (CITYSCAPE_PALETTE[pred], :170, alone or drawn over the frame),
+    made on the GPU by drnmi_render_labels with an integer blend (not matplotlib's compositing).
   * model_name is honoured (lmodels/drnseg.py:272 always builds D-22; semantic_seg.py
     :130-131 builds model_name — we follow the driver copy).
 """
@@ -145,7 +147,8 @@ class DRNSeg(nn.Module):
         return torch.ops.drnmi.predict(x, self._handle)
 
     def segment(self, frames_u8: torch.Tensor, mean=INFO_MEAN, std=INFO_STD, bgr: bool = False,
-                labels: torch.Tensor | None = None, size=None) -> torch.Tensor:
+                labels: torch.Tensor | None = None, size=None, render: str | None = None, alpha: float = 0.6,
+                palette=None):
         """Video path: uint8 HWC frames [B,H,W,3] on the GPU -> uint8 label maps [B,8h,8w].
 
         Fuses ToTensorVideoImage + Normalize (data_transforms.py:256-281, :109-125) into the
@@ -153,13 +156,34 @@ class DRNSeg(nn.Module):
         torch.ops.drnmi.segment (graph-capturable); `labels=` writes into a caller buffer.
         size=(oh, ow): first resize the frames on the GPU exactly as seg_video's
         T.Resize((300, 300)) does on each PIL frame (seg_video_old_no_plot.py:126-127;
-        Pillow BILINEAR arithmetic, drnmi_resize_bilinear_u8)."""
+        Pillow BILINEAR arithmetic, drnmi_resize_bilinear_u8).
+        render="color" / "overlay": returns (labels, image), image uint8 [B,H,W,3] at the size of
+        the frames the network saw (with size= the resized frames, what the reference overlays
+        onto: raw_images[i] is the resized PIL image): palette[label] (None = CITYSCAPE_PALETTE,
+        seg_video_old_no_plot.py:170), for "overlay" drawn over the frame with `alpha` by the
+        integer blend of drnmi_render_labels, in the frames' channel order (bgr).  As
+        torch.ops.drnmi.segment_render it is graph-capturable too."""
         if frames_u8.dtype != torch.uint8 or frames_u8.dim() != 4 or frames_u8.shape[3] != 3:
             raise ValueError("segment expects uint8 [B,H,W,3] frames")
+        if render not in (None, "color", "overlay"):
+            raise ValueError("render must be None, 'color' or 'overlay'")
         self._check_device(frames_u8)
         if size is not None and tuple(size) != tuple(frames_u8.shape[1:3]):
             from .ops import resize_bilinear_u8
             frames_u8 = resize_bilinear_u8(frames_u8, size)
+        if render is not None:
+            from .ops import render_labels
+            from .palette import CITYSCAPE_PALETTE, as_device_palette
+            if not 0.0 <= float(alpha) <= 1.0:
+                raise ValueError("alpha must be in [0, 1]")
+            pal = as_device_palette(CITYSCAPE_PALETTE if palette is None else palette, frames_u8.device)
+            if labels is None:
+                return torch.ops.drnmi.segment_render(frames_u8, self._handle, [float(v) for v in mean],
+                                                      [float(v) for v in std], bool(bgr), pal,
+                                                      int(round(float(alpha) * 256)), render == "overlay")
+            labels = self._segment_impl(frames_u8, mean, std, bgr, labels)
+            return labels, render_labels(labels, pal, frames_u8 if render == "overlay" else None, alpha, bgr,
+                                         frames_u8.shape[1:3])
         if labels is not None:
             return self._segment_impl(frames_u8, mean, std, bgr, labels)
         return torch.ops.drnmi.segment(frames_u8, self._handle, [float(v) for v in mean],

@@ -1,23 +1,36 @@
 """Evaluation drivers on the GPU: the callers of the hot path in semantic_seg.py (SURVEY.md §8a
 rows a18/a19, §8f row 4), same names and arguments.
 
-  test(eval_data_loader, model, num_classes, has_gt=True)        semantic_seg.py:429-468
+  test(eval_data_loader, model, num_classes, has_gt=True,
+       output_dir='pred', save_vis=False)                          semantic_seg.py:429-468
   val_miou(val_loader, model, num_classes, args=None, has_gt=True) semantic_seg.py:638-671
-  test_ms(eval_data_loader, model, num_classes, scales, has_gt=True) semantic_seg.py:507-557
+  test_ms(eval_data_loader, model, num_classes, scales, has_gt=True,
+          output_dir='pred', save_vis=False)                       semantic_seg.py:507-557
   resize_4d_tensor(tensor, width, height)                         semantic_seg.py:471-504
 
 Everything per image stays on the device: the forward (DRNSeg, HIP engine), the Pillow-exact
 bilinear resize of every log-prob plane and the fp32 scale sum (drnmi_resize_bilinear_f32,
 accumulate), the argmax (drnmi_argmax_nchw_f32) and the confusion matrix (drnmi_confusion_matrix).
-Only the 19 x 19 histogram ever comes back to the host.  Deviations: no save_vis / output_dir
-(image writing is out of scope), and the loader's tensors are moved to the model's device.
+Without save_vis only the 19 x 19 histogram ever comes back to the host.  With save_vis=True every
+image's label map goes to output_dir/<name[:-4]>.png (mode L) and its palette image to
+output_dir + '_color'/<name[:-4]>.png (save_output_images / save_colorful_images,
+semantic_seg.py:400-426): the colouring runs on the GPU (drnmi_render_labels) and only the finished
+uint8 images come to the host, where Pillow writes them.
+Deviations: output_dir and save_vis are keyword arguments (the reference has output_dir before
+has_gt positionally); the palette image is RGB for every palette -- the reference's TRIPLET_PALETTE
+(num_classes == 3) is RGBA with alpha 255 everywhere, and its 4th column is dropped
+(drnmi.palette); test_ms picks the palette by num_classes as test does (the reference's test_ms
+always takes CITYSCAPE_PALETTE); and the loader's tensors are moved to the model's device.
 """
 from __future__ import annotations
+
+import os
 
 import numpy as np
 import torch
 
 from . import metrics, ops
+from .palette import palette_for
 
 
 def resize_4d_tensor(tensor: torch.Tensor, width: int, height: int) -> torch.Tensor:
@@ -46,7 +59,28 @@ def _unwrap(model):
     return model
 
 
-def test(eval_data_loader, model, num_classes, has_gt=True, **_unused):
+def _save_png(array: np.ndarray, output_dir: str, filename: str) -> None:
+    from PIL import Image
+    fn = os.path.join(output_dir, filename[:-4] + '.png')
+    out_dir = os.path.split(fn)[0]
+    if not os.path.exists(out_dir):
+        os.makedirs(out_dir)
+    Image.fromarray(array).save(fn)
+
+
+def _save_vis(pred: torch.Tensor, names, output_dir: str, num_classes: int) -> None:
+    """pred [B, H, W] labels on the GPU -> the label PNG and the palette PNG of every image."""
+    if isinstance(names, str):
+        names = [names]
+    lab8 = pred.to(torch.uint8)                  # what the label PNG holds (the reference's astype(np.uint8))
+    color = ops.render_labels(lab8 if num_classes <= 256 else pred, palette_for(num_classes)).cpu().numpy()
+    lab = lab8.cpu().numpy()
+    for ind in range(len(names)):
+        _save_png(lab[ind], output_dir, names[ind])
+        _save_png(color[ind], output_dir + '_color', names[ind])
+
+
+def test(eval_data_loader, model, num_classes, has_gt=True, *, output_dir='pred', save_vis=False):
     """Single-scale eval loop: model(image)[0] -> torch.max(final, 1) -> fast_hist (on the GPU)."""
     model.eval()
     model = _unwrap(model)
@@ -55,6 +89,8 @@ def test(eval_data_loader, model, num_classes, has_gt=True, **_unused):
     for it, batch in enumerate(eval_data_loader):
         image = batch[0].to(dev)
         pred = model.predict(image)                  # fused forward + argmax (int64 labels)
+        if save_vis:
+            _save_vis(pred, batch[2], output_dir, num_classes)
         if has_gt:
             metrics.fast_hist(pred, batch[1].to(dev).long().reshape(pred.shape), num_classes, hist)
     if has_gt:
@@ -67,7 +103,7 @@ def val_miou(val_loader, model, num_classes, args=None, has_gt=True):
     return test(val_loader, model, num_classes, has_gt=has_gt)
 
 
-def test_ms(eval_data_loader, model, num_classes, scales, has_gt=True, **_unused):
+def test_ms(eval_data_loader, model, num_classes, scales, has_gt=True, *, output_dir='pred', save_vis=False):
     """Multi-scale eval: the log-probs of the image and of its len(scales) rescaled copies (the
     loader's SegListMS items: image, label, name, *scaled images) are each resized to the input
     size and summed in fp32 in the reference's order, then argmax(axis=1) and fast_hist."""
@@ -93,6 +129,8 @@ def test_ms(eval_data_loader, model, num_classes, scales, has_gt=True, **_unused
                 ops.resize_bilinear_f32(out, (h, w), out=final, accumulate=True)
         pred = ops.argmax_nchw(final)
         preds.append(pred)
+        if save_vis:
+            _save_vis(pred, input_data[2] if has_gt else input_data[1], output_dir, num_classes)
         if has_gt:
             metrics.fast_hist(pred, label.to(dev).long().reshape(pred.shape), num_classes, hist)
     if has_gt:

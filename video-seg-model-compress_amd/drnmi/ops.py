@@ -265,3 +265,44 @@ def abs_histogram(x: torch.Tensor, hist: torch.Tensor | None = None) -> torch.Te
     _lib.check(_lib.load().drnmi_abs_histogram(x.data_ptr(), code, x.numel(), hist.data_ptr(),
                                                ctypes.c_void_p(_lib.stream_ptr(dev))), "abs_histogram")
     return hist
+
+
+def render_labels(labels: torch.Tensor, palette=None, frames: torch.Tensor | None = None, alpha: float = 0.6,
+                  bgr: bool = False, out_hw=None, out: torch.Tensor | None = None) -> torch.Tensor:
+    """Label maps [n, lh, lw] (uint8 or int64) -> uint8 pictures [n, oh, ow, 3] (drnmi_render_labels):
+    palette[min(label, P - 1)], drawn over `frames` (uint8 [n, oh, ow, 3]) when given with
+    out = (f * (256 - a) + c * a + 128) >> 8, a = round(alpha * 256).  palette: [P, 3] / [P, 4]
+    (drnmi.palette.as_device_palette; None = CITYSCAPE_PALETTE).  bgr: the frames are B, G, R and the
+    picture is written in that order.  out_hw = (oh, ow) <= (lh, lw) crops the label map top-left; it
+    defaults to the frame size, else to the label size.  out=: write into a caller buffer."""
+    from .palette import CITYSCAPE_PALETTE, as_device_palette
+    if labels.dim() != 3 or labels.dtype not in (torch.uint8, torch.int64):
+        raise ValueError("render_labels expects uint8 or int64 [n, lh, lw] labels")
+    n, lh, lw = labels.shape
+    dev = labels.device
+    if dev.type != "cuda":
+        raise ValueError("render_labels runs on the HIP kernel only: labels must be on a ROCm device")
+    if frames is not None:
+        if frames.dtype != torch.uint8 or frames.dim() != 4 or frames.shape[0] != n or frames.shape[3] != 3 \
+                or frames.device != dev:
+            raise ValueError(f"frames must be uint8 [{n}, oh, ow, 3] on {dev}")
+        if out_hw is not None and tuple(int(v) for v in out_hw) != tuple(frames.shape[1:3]):
+            raise ValueError("out_hw must equal the frame size when frames are given")
+        out_hw = frames.shape[1:3]
+    oh, ow = (lh, lw) if out_hw is None else (int(out_hw[0]), int(out_hw[1]))
+    if not (0 < oh <= lh and 0 < ow <= lw) or n <= 0:
+        raise ValueError(f"render_labels: output {oh} x {ow} must be non-empty and inside the {lh} x {lw} label map")
+    if not 0.0 <= float(alpha) <= 1.0:
+        raise ValueError("alpha must be in [0, 1]")
+    pal = as_device_palette(CITYSCAPE_PALETTE if palette is None else palette, dev)
+    if out is None:
+        out = torch.empty(n, oh, ow, 3, dtype=torch.uint8, device=dev)
+    elif tuple(out.shape) != (n, oh, ow, 3) or out.dtype != torch.uint8 or not out.is_contiguous() or out.device != dev:
+        raise ValueError(f"out must be a contiguous uint8 [{n}, {oh}, {ow}, 3] tensor on {dev}")
+    labels = labels.contiguous()
+    fr = frames.contiguous() if frames is not None else None
+    _lib.check(_lib.load().drnmi_render_labels(
+        labels.data_ptr(), _lib.DRNMI_U8 if labels.dtype == torch.uint8 else _lib.DRNMI_I64, n, lh, lw,
+        fr.data_ptr() if fr is not None else None, pal.data_ptr(), pal.shape[0], int(round(float(alpha) * 256)),
+        1 if bgr else 0, out.data_ptr(), oh, ow, ctypes.c_void_p(_lib.stream_ptr(dev))), "render_labels")
+    return out

@@ -29,6 +29,13 @@ Ops (schema -> reference):
       DRNSeg.forward in eval mode (lmodels/drnseg.py:295-299)
   drnmi::predict(Tensor x, int model) -> Tensor
       torch.max(model(x)[0], 1)[1] (semantic_seg.py:444-445), int64 labels
+  drnmi::render_labels(Tensor labels, Tensor palette, Tensor? frames, int alpha_q8, bool bgr,
+                       int oh, int ow) -> Tensor
+      CITYSCAPE_PALETTE[pred] and its overlay on the frame (seg_video_old_no_plot.py:166-170,
+      semantic_seg.py:415-426): uint8 [n, oh, ow, 3]; palette uint8 [P, 3] on the device
+  drnmi::segment_render(Tensor frames_u8, int model, float[] mean, float[] std, bool bgr,
+                        Tensor palette, int alpha_q8, bool overlay) -> (Tensor labels, Tensor image)
+      drnmi::segment, then the colour image (overlay=False) or the overlay at the frames' size
 `model` is the handle of a live drnmi.drnseg.DRNSeg (its packed weights and launch plans are
 the op's state; DRNSeg.segment / forward / predict pass their own handle).
 """
@@ -228,5 +235,43 @@ def _(x, model):
     return x.new_empty((n, oh, ow), dtype=torch.int64)
 
 
+# ------------------------------------------------------------------ rendering
+def _render(labels, palette, frames, alpha_q8, bgr, oh, ow):
+    from .ops import render_labels as impl
+    if palette.dtype != torch.uint8 or palette.dim() != 2 or palette.shape[1] != 3 or palette.device != labels.device:
+        raise ValueError("drnmi::render_labels: palette must be uint8 [P, 3] on the labels' device "
+                         "(drnmi.palette.as_device_palette)")
+    if not 0 <= alpha_q8 <= 256:
+        raise ValueError("drnmi::render_labels: alpha_q8 must be in 0..256")
+    return impl(labels, palette, frames, alpha_q8 / 256.0, bgr, (oh, ow))    # round(a / 256 * 256) == a
+
+
+@torch.library.custom_op("drnmi::render_labels", mutates_args=(), device_types="cuda")
+def render_labels(labels: torch.Tensor, palette: torch.Tensor, frames: torch.Tensor | None, alpha_q8: int,
+                  bgr: bool, oh: int, ow: int) -> torch.Tensor:
+    return _render(labels, palette, frames, alpha_q8, bgr, oh, ow)
+
+
+@render_labels.register_fake
+def _(labels, palette, frames, alpha_q8, bgr, oh, ow):
+    return labels.new_empty((labels.shape[0], oh, ow, 3), dtype=torch.uint8)
+
+
+@torch.library.custom_op("drnmi::segment_render", mutates_args=(), device_types="cuda")
+def segment_render(frames_u8: torch.Tensor, model: int, mean: list[float], std: list[float], bgr: bool,
+                   palette: torch.Tensor, alpha_q8: int, overlay: bool) -> tuple[torch.Tensor, torch.Tensor]:
+    labels = _model(model)._segment_impl(frames_u8, mean, std, bgr, None)
+    h, w = frames_u8.shape[1:3]
+    return labels, _render(labels, palette, frames_u8 if overlay else None, alpha_q8, bgr, h, w)
+
+
+@segment_render.register_fake
+def _(frames_u8, model, mean, std, bgr, palette, alpha_q8, overlay):
+    n, h, w, _ = frames_u8.shape
+    oh, ow, _, _ = _out_hw(_model(model), h, w)
+    return (frames_u8.new_empty((n, oh, ow), dtype=torch.uint8),
+            frames_u8.new_empty((n, h, w, 3), dtype=torch.uint8))
+
+
 __all__ = ["conv2d_bn_act", "up8_logsoftmax_argmax", "mask_apply_", "segment", "forward", "predict",
-           "register_model"]
+           "render_labels", "segment_render", "register_model"]
