@@ -290,10 +290,21 @@ int drnmi_nhwc_to_nchw(const void* x, float* out, int32_t n, int32_t c, int32_t 
  *   lmodels/drnseg.py:257-266, :285-299 ; semantic_seg.py:445 ; seg_video_old_no_plot.py:166
  * logits: fp32 NCHW [n][c][h][w]; up_w: fp32 [16][16] (one depthwise plane, all planes equal);
  * logprobs: fp32 NCHW [n][c][8h][8w] or NULL; labels: [n][8h][8w] uint8 or int64 (label_dtype)
- * or NULL.  Ties in argmax resolve to the lowest class index. */
+ * or NULL.  Ties in argmax resolve to the lowest class index.
+ * 1 <= c <= 256 (what a uint8 label map holds), else DRNMI_ENOTSUP.  c <= 32 keeps the class vector
+ * in registers; 33 <= c <= 256 runs the three-sweep LDS-patch kernel (csrc/head_wide.hip: same
+ * per-pixel arithmetic in the same order), which needs logprobs 16-byte and labels 4-byte (uint8)
+ * or 8-byte (int64) aligned, else DRNMI_EINVAL. */
 int drnmi_up8_logsoftmax_argmax(const float* logits, const float* up_w, float* logprobs,
                                 void* labels, int32_t label_dtype, int32_t n, int32_t c,
                                 int32_t h, int32_t w, void* stream);
+
+/* The 33 .. 256-class kernel of drnmi_up8_logsoftmax_argmax for any 1 <= c <= 256 (same arguments,
+ * same alignment rule): what the tests use to pin it bit for bit against the c <= 32 kernels.
+ * Not a faster path: callers use drnmi_up8_logsoftmax_argmax. */
+int drnmi_up8_logsoftmax_argmax_wide(const float* logits, const float* up_w, float* logprobs,
+                                     void* labels, int32_t label_dtype, int32_t n, int32_t c,
+                                     int32_t h, int32_t w, void* stream);
 
 /* Labels-only form of the same head (the video path: no log-prob planes) on NHWC logits: fp32
  * [n][h][w][cs] rows, classes 0..c-1 first (cs % 4 == 0, cs >= c, 16-B aligned), as the seg conv
@@ -336,7 +347,8 @@ int drnmi_up8_labels_seg2_i8(const int32_t* partials, int32_t cs, const float* s
 /* Same head for DRNSeg(use_torch_up=True): nn.UpsamplingBilinear2d(scale_factor=8) (bilinear,
  * align_corners=True; lmodels/drnseg.py:285-287) + LogSoftmax + argmax.  Source index and
  * weights follow ATen's CPU kernel: scale = (in-1)/(out-1) in fp32, i0 = floor(scale*dst),
- * i1 = i0 + (i0 < in-1), l1 = scale*dst - i0.  Output [n][c][8h][8w]. */
+ * i1 = i0 + (i0 < in-1), l1 = scale*dst - i0.  Output [n][c][8h][8w].  1 <= c <= 256, else
+ * DRNMI_ENOTSUP; 33 <= c <= 256 recomputes the interpolation in three sweeps over the classes. */
 int drnmi_up8_bilinear_logsoftmax_argmax(const float* logits, float* logprobs, void* labels,
                                          int32_t label_dtype, int32_t n, int32_t c, int32_t h, int32_t w,
                                          void* stream);
@@ -403,7 +415,9 @@ int drnmi_mask_apply_bits_f32(int32_t ntensors, float* const* weights,
 /* Eval: accumulate the nclass x nclass confusion matrix hist[label*nclass + pred] += 1 over the
  * pixels with 0 <= label < nclass and pred < nclass (int64 hist, NOT cleared: accumulates across
  * calls like the reference's running hist).  Replaces fast_hist (semantic_seg.py:293-296) used by
- * test()/val_miou() (:455, :655).  pred/label dtypes: DRNMI_U8 or DRNMI_I64; nclass <= 32. */
+ * test()/val_miou() (:455, :655).  pred/label dtypes: DRNMI_U8 or DRNMI_I64; nclass <= 256
+ * (nclass <= 32: a 4 KiB LDS table; above: up to 128 KiB of LDS per workgroup, the label rows in
+ * two slabs from nclass = 182; npix <= 2^40 there). */
 int drnmi_confusion_matrix(const void* pred, int32_t pred_dtype, const void* label, int32_t label_dtype,
                            int64_t npix, int32_t nclass, int64_t* hist, void* stream);
 

@@ -56,4 +56,13 @@ bool s1x2row_conv_supported(const drnmi_conv_args& p);
 bool s1x2row_auto(const drnmi_conv_args& p);
 int s1x2row_conv_dispatch(const drnmi_conv_args& p, hipStream_t s);
 const char* s1x2row_conv_name(const drnmi_conv_args& p);
+// The heads and the confusion matrix for up to 256 classes (head_wide.hip); the entry points in
+// ops.hip route c > 32 / nclass > 32 here after their own argument checks (up8_wide_dispatch, also
+// behind drnmi_up8_logsoftmax_argmax_wide, repeats them); they return drnmi_status / hipError_t.
+int up8_wide_dispatch(const float* logits, const float* up_w, float* logprobs, void* labels, int label_dtype, int n,
+                      int c, int h, int w, hipStream_t s);
+int up8_bilinear_wide_dispatch(const float* logits, float* logprobs, void* labels, int label_dtype, int n, int c, int h,
+                               int w, hipStream_t s);
+int confusion_wide_dispatch(const void* pred, int pred_dtype, const void* label, int label_dtype, int64_t npix,
+                            int nclass, int64_t* hist, hipStream_t s);
 }  // namespace drnmi

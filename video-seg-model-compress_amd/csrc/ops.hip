@@ -3,7 +3,7 @@
 //   * NCHW fp32 -> NHWC boundary conversion          lmodels/drnseg.py:295-299 input
 //   * fused up x8 + LogSoftmax + argmax             lmodels/drnseg.py:257-299, semantic_seg.py:445
 //   * multi-tensor mask apply (float / bit masks)    pruners/Pruner.py:17-20
-#include "common.h"
+#include "kernels.h"
 
 namespace drnmi {
 namespace {
@@ -73,7 +73,8 @@ nhwc_to_nchw_kernel(const T* __restrict__ x, float* __restrict__ out, int c, int
 // i1 = (oy+4)>>3 (tap ky = oy+4-8*i1 in [0,8)) and i0 = i1-1 (tap ky+8), likewise for
 // columns: 4 taps per class.  The 16x16 kernel is shared by every class plane
 // (fill_up_weights copies plane 0 into all planes, lmodels/drnseg.py:265-266).
-constexpr int kMaxClasses = 32;
+constexpr int kMaxClasses = 32;        // up8_lsm_kernel / up8_bilinear_lsm_kernel: the class vector in registers
+constexpr int kMaxWideClasses = 256;   // above kMaxClasses: the three-sweep kernels of head_wide.hip
 
 template <int LABEL_DTYPE>
 __global__ void __launch_bounds__(256)
@@ -842,7 +843,8 @@ __global__ void __launch_bounds__(256) mask_apply_bits_kernel(const MaskBatchBit
 // ---------------------------------------------------------------- confusion matrix (eval)
 // hist[label * n + pred] += 1 over pixels with 0 <= label < n and pred < n
 // (semantic_seg.py:293-296 fast_hist; per-block LDS histogram, one global atomic per bin).
-constexpr int kMaxHistClasses = 32;
+constexpr int kMaxHistClasses = 32;        // this kernel's static table; up to 256: head_wide.hip
+constexpr int kMaxWideHistClasses = 256;
 
 template <typename TP, typename TL>
 __global__ void __launch_bounds__(256)
@@ -994,12 +996,13 @@ extern "C" int drnmi_up8_logsoftmax_argmax(const float* logits, const float* up_
                                            void* labels, int32_t label_dtype, int32_t n, int32_t c,
                                            int32_t h, int32_t w, void* stream) {
   if (logits == nullptr || up_w == nullptr || n <= 0 || h <= 0 || w <= 0) return DRNMI_EINVAL;
-  if (c <= 0 || c > kMaxClasses) return DRNMI_ENOTSUP;
+  if (c <= 0 || c > kMaxWideClasses) return DRNMI_ENOTSUP;
   if (labels != nullptr && label_dtype != DRNMI_U8 && label_dtype != DRNMI_I64) return DRNMI_EINVAL;
   if (static_cast<int64_t>(h) * 8 > 65535 || n > 65535) return DRNMI_EINVAL;
   const int W = w * 8;
   dim3 grid(static_cast<unsigned>((W + 255) / 256), static_cast<unsigned>(h * 8), static_cast<unsigned>(n));
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  if (c > kMaxClasses) return up8_wide_dispatch(logits, up_w, logprobs, labels, label_dtype, n, c, h, w, s);
   if (c == 19 && logprobs == nullptr && labels != nullptr) {   // labels only: 8-row kernel
     dim3 go(static_cast<unsigned>((W / 4 + 255) / 256), static_cast<unsigned>(h + 1), static_cast<unsigned>(n));
     if (label_dtype == DRNMI_I64) {
@@ -1030,12 +1033,13 @@ extern "C" int drnmi_up8_bilinear_logsoftmax_argmax(const float* logits, float* 
                                                     int32_t label_dtype, int32_t n, int32_t c, int32_t h, int32_t w,
                                                     void* stream) {
   if (logits == nullptr || n <= 0 || h <= 0 || w <= 0) return DRNMI_EINVAL;
-  if (c <= 0 || c > kMaxClasses) return DRNMI_ENOTSUP;
+  if (c <= 0 || c > kMaxWideClasses) return DRNMI_ENOTSUP;
   if (labels != nullptr && label_dtype != DRNMI_U8 && label_dtype != DRNMI_I64) return DRNMI_EINVAL;
   if (static_cast<int64_t>(h) * 8 > 65535 || n > 65535) return DRNMI_EINVAL;
   const int W = w * 8;
   dim3 grid(static_cast<unsigned>((W + 255) / 256), static_cast<unsigned>(h * 8), static_cast<unsigned>(n));
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  if (c > kMaxClasses) return up8_bilinear_wide_dispatch(logits, logprobs, labels, label_dtype, n, c, h, w, s);
   if (label_dtype == DRNMI_I64)
     hipLaunchKernelGGL(up8_bilinear_lsm_kernel<DRNMI_I64>, grid, dim3(256), 0, s, logits, logprobs, labels, c, h, w);
   else
@@ -1108,11 +1112,13 @@ extern "C" int drnmi_confusion_matrix(const void* pred, int32_t pred_dtype, cons
                                       int32_t label_dtype, int64_t npix, int32_t nclass, int64_t* hist,
                                       void* stream) {
   if (pred == nullptr || label == nullptr || hist == nullptr || npix < 0) return DRNMI_EINVAL;
-  if (nclass <= 0 || nclass > kMaxHistClasses) return DRNMI_ENOTSUP;
+  if (nclass <= 0 || nclass > kMaxWideHistClasses) return DRNMI_ENOTSUP;
   if ((pred_dtype != DRNMI_U8 && pred_dtype != DRNMI_I64) || (label_dtype != DRNMI_U8 && label_dtype != DRNMI_I64))
     return DRNMI_EINVAL;
   if (npix == 0) return DRNMI_OK;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  if (nclass > kMaxHistClasses)
+    return confusion_wide_dispatch(pred, pred_dtype, label, label_dtype, npix, nclass, hist, s);
   unsigned g = grid1d(npix);
   g = g > 2048 ? 2048 : g;
   auto* h = reinterpret_cast<unsigned long long*>(hist);

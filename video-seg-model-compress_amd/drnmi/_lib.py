@@ -83,6 +83,7 @@ SIGNATURES = {
     "drnmi_nchw_to_nhwc": (ctypes.c_int, [_VP, _VP, _I32, _I32, _I32, _I32, _I32, _I32, _VP]),
     "drnmi_nhwc_to_nchw": (ctypes.c_int, [_VP, _VP, _I32, _I32, _I32, _I32, _I32, _I32, _VP]),
     "drnmi_up8_logsoftmax_argmax": (ctypes.c_int, [_VP, _VP, _VP, _VP, _I32, _I32, _I32, _I32, _I32, _VP]),
+    "drnmi_up8_logsoftmax_argmax_wide": (ctypes.c_int, [_VP, _VP, _VP, _VP, _I32, _I32, _I32, _I32, _I32, _VP]),
     "drnmi_up8_labels_nhwc": (ctypes.c_int, [_VP, _I32, _VP, _VP, _I32, _I32, _I32, _I32, _I32, _VP]),
     "drnmi_up8_labels_seg2": (ctypes.c_int, [_VP, _I32, _VP, _VP, _VP, _I32, _I32, _I32, _I32, _I32, _VP]),
     "drnmi_conv_stag_seg": (ctypes.c_int, [ctypes.POINTER(ConvArgs), _VP, _I32, _I32, _VP, _VP]),

@@ -160,7 +160,7 @@ class DRNSeg(nn.Module):
         render="color" / "overlay": returns (labels, image), image uint8 [B,H,W,3] at the size of
         the frames the network saw (with size= the resized frames, what the reference overlays
         onto: raw_images[i] is the resized PIL image): palette[label] (None = CITYSCAPE_PALETTE,
-        seg_video_old_no_plot.py:170), for "overlay" drawn over the frame with `alpha` by the
+        seg_video_old_no_plot.py:170; a model with more than 20 classes: generic_palette), for "overlay" drawn over the frame with `alpha` by the
         integer blend of drnmi_render_labels, in the frames' channel order (bgr).  As
         torch.ops.drnmi.segment_render it is graph-capturable too."""
         if frames_u8.dtype != torch.uint8 or frames_u8.dim() != 4 or frames_u8.shape[3] != 3:
@@ -173,10 +173,12 @@ class DRNSeg(nn.Module):
             frames_u8 = resize_bilinear_u8(frames_u8, size)
         if render is not None:
             from .ops import render_labels
-            from .palette import CITYSCAPE_PALETTE, as_device_palette
+            from .palette import CITYSCAPE_PALETTE, as_device_palette, generic_palette
             if not 0.0 <= float(alpha) <= 1.0:
                 raise ValueError("alpha must be in [0, 1]")
-            pal = as_device_palette(CITYSCAPE_PALETTE if palette is None else palette, frames_u8.device)
+            if palette is None:
+                palette = CITYSCAPE_PALETTE if self.classes <= 20 else generic_palette(self.classes)
+            pal = as_device_palette(palette, frames_u8.device)
             if labels is None:
                 return torch.ops.drnmi.segment_render(frames_u8, self._handle, [float(v) for v in mean],
                                                       [float(v) for v in std], bool(bgr), pal,

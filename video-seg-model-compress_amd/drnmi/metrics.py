@@ -1,7 +1,7 @@
 """Segmentation metrics on the GPU (the eval caller of the hot path).
 
   fast_hist      semantic_seg.py:293-296  -> drnmi_confusion_matrix (HIP, int64 hist)
-  per_class_iu   semantic_seg.py:299-300  (19x19 host math)
+  per_class_iu   semantic_seg.py:299-300  (n x n host math)
   miou           semantic_seg.py:468      round(nanmean(iou) * 100, 2)
 """
 from __future__ import annotations
@@ -26,8 +26,8 @@ def fast_hist(pred: torch.Tensor, label: torch.Tensor, n: int, hist: torch.Tenso
         raise RuntimeError("fast_hist runs on the HIP kernel: tensors must be on a ROCm device")
     if pred.device != label.device:
         raise RuntimeError("pred and label are on different devices")
-    if not 0 < n <= 32:
-        raise ValueError("n must be in 1..32 (drnmi_confusion_matrix)")
+    if not 0 < n <= 256:
+        raise ValueError("n must be in 1..256 (drnmi_confusion_matrix)")
     if hist is None:
         hist = torch.zeros(n, n, dtype=torch.int64, device=pred.device)
     elif (hist.dtype != torch.int64 or tuple(hist.shape) != (n, n) or not hist.is_contiguous()

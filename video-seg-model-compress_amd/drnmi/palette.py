@@ -4,6 +4,7 @@ data, and their device form for the renderer (drnmi.ops.render_labels, csrc/rend
   CITYSCAPE_PALETTE  uint8 [20, 3] RGB: the 19 Cityscapes train classes, then black (entry 19 is
                      what labels >= 20, the ignore value 255 among them, are drawn with)
   TRIPLET_PALETTE    uint8 [3, 4] RGBA, used when num_classes == 3
+  generic_palette(n) uint8 [n, 3] RGB for more than 20 classes (ADE20K's 150): not a reference table
 
 Deviation: the renderer is RGB only.  as_device_palette drops a 4th column, so TRIPLET_PALETTE
 images come out as RGB where the reference's Image.fromarray(palettes[pred]) makes RGBA; its alpha
@@ -42,8 +43,28 @@ TRIPLET_PALETTE = np.asarray([
     [91, 192, 222, 255]], dtype=np.uint8)
 
 
+def generic_palette(num_classes: int) -> np.ndarray:
+    """uint8 [num_classes, 3] RGB for any 1 <= num_classes <= 256: the usual bit-interleaved colour
+    map.  Eight rounds; round r takes bits 0, 1, 2 of what is left of the class id to bit 7 - r of
+    R, G, B and drops them.  Class 0 is black, class 1 (128, 0, 0), class 2 (0, 128, 0), ...; the id
+    can be read back from the colour, so all 256 entries are distinct."""
+    if not 1 <= num_classes <= 256:
+        raise ValueError(f"num_classes must be in 1..256, got {num_classes}")
+    ids = np.arange(num_classes, dtype=np.int64)
+    pal = np.zeros((num_classes, 3), dtype=np.int64)
+    for r in range(8):
+        for ch in range(3):
+            pal[:, ch] |= ((ids >> ch) & 1) << (7 - r)
+        ids = ids >> 3
+    return pal.astype(np.uint8)
+
+
 def palette_for(num_classes: int) -> np.ndarray:
-    """The table the reference's eval drivers colour with (semantic_seg.py:450-452)."""
+    """The table the reference's eval drivers colour with (semantic_seg.py:450-452) for the class
+    counts it covers: TRIPLET_PALETTE for 3, else CITYSCAPE_PALETTE (19 colours, then black).  Above
+    20 classes that table would paint every class from 19 up black, so they get generic_palette."""
+    if num_classes > 20:
+        return generic_palette(num_classes)
     return TRIPLET_PALETTE if num_classes == 3 else CITYSCAPE_PALETTE
 
 
@@ -84,4 +105,4 @@ def _checked_u8(t: torch.Tensor) -> torch.Tensor:
     return t
 
 
-__all__ = ["CITYSCAPE_PALETTE", "TRIPLET_PALETTE", "palette_for", "as_device_palette"]
+__all__ = ["CITYSCAPE_PALETTE", "TRIPLET_PALETTE", "palette_for", "generic_palette", "as_device_palette"]
