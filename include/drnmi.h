@@ -309,9 +309,34 @@ int drnmi_up8_logsoftmax_argmax_wide(const float* logits, const float* up_w, flo
 /* Labels-only form of the same head (the video path: no log-prob planes) on NHWC logits: fp32
  * [n][h][w][cs] rows, classes 0..c-1 first (cs % 4 == 0, cs >= c, 16-B aligned), as the seg conv
  * writes them with y_sp = cs, y_sc = 1.  Same per-pixel arithmetic, near-tie fallback and argmax
- * order as drnmi_up8_logsoftmax_argmax: identical labels.  c == 19 (else DRNMI_ENOTSUP). */
+ * order as drnmi_up8_logsoftmax_argmax: identical labels.  c == 19 (else DRNMI_ENOTSUP); any other
+ * class count: drnmi_up8_labels_nhwc_wide. */
 int drnmi_up8_labels_nhwc(const float* logits, int32_t cs, const float* up_w, void* labels, int32_t label_dtype,
                           int32_t n, int32_t c, int32_t h, int32_t w, void* stream);
+
+/* The same labels-only head for any 1 <= c <= 256 (else DRNMI_ENOTSUP), c == 19 included: the
+ * runtime-class-count form of the 19-class tiled kernel (csrc/head_wide.hip
+ * up8_labels_wide_tile_kernel).  A workgroup stages its tile's 1/8-res logit vectors in LDS once;
+ * an 8 x 8 output window whose four taps agree on the best class by more than a guard is written
+ * without per-pixel work, the others are decided over the classes that can still win, and a pixel
+ * whose top two are closer than 2^-16 takes the three-sweep log-softmax argmax of
+ * drnmi_up8_logsoftmax_argmax (the same device function).  Labels are bit-identical to the
+ * labels-only drnmi_up8_logsoftmax_argmax on the NCHW form of the same values; the columns
+ * c .. cs - 1 of a row are never read into a decision.
+ * DRNMI_EINVAL before any HIP call: NULL pointers, a label_dtype other than DRNMI_U8 / DRNMI_I64,
+ * cs % 4 != 0, cs < c, non-positive sizes, logits not 16-byte aligned, labels not 4-byte (uint8) or
+ * 8-byte (int64) aligned, n or h above 65535, w above 2^27.  No allocation, no host synchronisation. */
+int drnmi_up8_labels_nhwc_wide(const float* logits, int32_t cs, const float* up_w, void* labels,
+                               int32_t label_dtype, int32_t n, int32_t c, int32_t h, int32_t w, void* stream);
+
+/* drnmi_up8_labels_nhwc_wide with counters, for the tests to prove that each path ran (not a
+ * faster path; the shipped kernel is compiled without the counting): the same labels, and
+ * stats (device, int64[3], 8-byte aligned, accumulated): [0] += windows written by the fast path
+ * (64 pixels each), [1] += pixels decided over the candidate classes, [2] += pixels through the
+ * three-sweep fallback. */
+int drnmi_up8_labels_nhwc_wide_stats(const float* logits, int32_t cs, const float* up_w, void* labels,
+                                     int32_t label_dtype, int32_t n, int32_t c, int32_t h, int32_t w, void* stream,
+                                     int64_t* stats);
 
 /* The labels-only video path with the seg classifier (1x1 c_in -> 19 + bias, lmodels/drnseg.py:278-284)
  * folded into the epilogue of the last 3x3 conv (D-22 layer8): `a` is that conv's argument block

@@ -2,8 +2,10 @@
 //   * up x8 + LogSoftmax + argmax      (ops.hip up8_lsm_kernel, c <= 32: the class vector in registers)
 //   * bilinear x8 + LogSoftmax + argmax (ops.hip up8_bilinear_lsm_kernel, likewise)
 //   * the confusion matrix              (ops.hip confusion_kernel, n <= 32: a 4 KiB LDS table)
-// that do not need the class count to fit a register array or a static LDS table.  256 is what a
-// uint8 label map can hold.
+// that do not need the class count to fit a register array or a static LDS table, and the
+// labels-only video head on NHWC logit rows for any class count (up8_labels_wide_tile_kernel, the
+// runtime-class-count form of ops.hip's up8_labels_tile_kernel).  256 is what a uint8 label map can
+// hold.
 #include "kernels.h"
 
 namespace drnmi {
@@ -32,6 +34,60 @@ namespace {
 // the lanes of one cell broadcast.
 constexpr int kWideMaxClasses = 256;
 constexpr int kWideRows = 3, kWideCols = 10, kWidePatch = kWideRows * kWideCols;
+
+// The three sweeps for the 4 pixels of one thread, shared by up8_lsm_wide_kernel and the full path of
+// up8_labels_wide_tile_kernel so that the two cannot round differently: class k's four taps are
+// t00[k * KS] (i0, j0), t01[k * KS] (i0, j1), t10[k * KS] (i1, j0), t11[k * KS] (i1, j1); the
+// up-sampled value is one mul + 3 fma in that order with the pixel's weights (0 for a tap outside
+// the image).  out: the 4 pixels' log-prob address in plane 0 (planes HW apart), or nullptr.
+template <int KS>
+__device__ __forceinline__ void lsm_sweeps4(const float* t00, const float* t01, const float* t10, const float* t11,
+                                            const float (&w00)[4], const float (&w01)[4], const float (&w10)[4],
+                                            const float (&w11)[4], int c, float* out, int64_t HW, int (&arg)[4]) {
+  auto upsampled = [&](int k, float (&a)[4]) {
+    const float s00 = t00[k * KS], s01 = t01[k * KS], s10 = t10[k * KS], s11 = t11[k * KS];
+#pragma unroll
+    for (int p = 0; p < 4; ++p) {
+      float v = s00 * w00[p];
+      v = fmaf(s01, w01[p], v);
+      v = fmaf(s10, w10[p], v);
+      v = fmaf(s11, w11[p], v);
+      a[p] = v;
+    }
+  };
+
+  float vmax[4] = {-INFINITY, -INFINITY, -INFINITY, -INFINITY};
+  for (int k = 0; k < c; ++k) {
+    float a[4];
+    upsampled(k, a);
+#pragma unroll
+    for (int p = 0; p < 4; ++p) vmax[p] = fmaxf(vmax[p], a[p]);
+  }
+  float sum[4] = {0.f, 0.f, 0.f, 0.f};
+  for (int k = 0; k < c; ++k) {
+    float a[4];
+    upsampled(k, a);
+#pragma unroll
+    for (int p = 0; p < 4; ++p) sum[p] += expf(a[p] - vmax[p]);
+  }
+  float lse[4];
+#pragma unroll
+  for (int p = 0; p < 4; ++p) lse[p] = logf(sum[p]);
+
+  float best[4] = {-INFINITY, -INFINITY, -INFINITY, -INFINITY};
+#pragma unroll
+  for (int p = 0; p < 4; ++p) arg[p] = 0;
+  for (int k = 0; k < c; ++k) {
+    float a[4], lp[4];
+    upsampled(k, a);
+#pragma unroll
+    for (int p = 0; p < 4; ++p) {
+      lp[p] = (a[p] - vmax[p]) - lse[p];
+      if (lp[p] > best[p]) { best[p] = lp[p]; arg[p] = k; }
+    }
+    if (out != nullptr) *reinterpret_cast<float4*>(out + k * HW) = make_float4(lp[0], lp[1], lp[2], lp[3]);
+  }
+}
 
 template <int LABEL_DTYPE>
 __global__ void __launch_bounds__(256)
@@ -79,52 +135,11 @@ up8_lsm_wide_kernel(const float* __restrict__ logits, const float* __restrict__ 
   }
   // tap (i0, j0) of class k: tp[k * kWidePatch]; (i0, j1): + 1; (i1, j0): + kWideCols; (i1, j1): + kWideCols + 1
   const float* tp = patch + ti * kWideCols + (j0 - JB);
-  auto upsampled = [&](int k, float (&a)[4]) {
-    const float* t = tp + k * kWidePatch;
-    const float s00 = t[0], s01 = t[1], s10 = t[kWideCols], s11 = t[kWideCols + 1];
-#pragma unroll
-    for (int p = 0; p < 4; ++p) {
-      float v = s00 * w00[p];
-      v = fmaf(s01, w01[p], v);
-      v = fmaf(s10, w10[p], v);
-      v = fmaf(s11, w11[p], v);
-      a[p] = v;
-    }
-  };
-
-  float vmax[4] = {-INFINITY, -INFINITY, -INFINITY, -INFINITY};
-  for (int k = 0; k < c; ++k) {
-    float a[4];
-    upsampled(k, a);
-#pragma unroll
-    for (int p = 0; p < 4; ++p) vmax[p] = fmaxf(vmax[p], a[p]);
-  }
-  float sum[4] = {0.f, 0.f, 0.f, 0.f};
-  for (int k = 0; k < c; ++k) {
-    float a[4];
-    upsampled(k, a);
-#pragma unroll
-    for (int p = 0; p < 4; ++p) sum[p] += expf(a[p] - vmax[p]);
-  }
-  float lse[4];
-#pragma unroll
-  for (int p = 0; p < 4; ++p) lse[p] = logf(sum[p]);
-
   const int64_t HW = static_cast<int64_t>(H) * W;
   const int64_t pix = static_cast<int64_t>(oy) * W + 4 * q;
-  float best[4] = {-INFINITY, -INFINITY, -INFINITY, -INFINITY};
-  int arg[4] = {0, 0, 0, 0};
+  int arg[4];
   float* out = logprobs != nullptr ? logprobs + static_cast<int64_t>(n) * c * HW + pix : nullptr;
-  for (int k = 0; k < c; ++k) {
-    float a[4], lp[4];
-    upsampled(k, a);
-#pragma unroll
-    for (int p = 0; p < 4; ++p) {
-      lp[p] = (a[p] - vmax[p]) - lse[p];
-      if (lp[p] > best[p]) { best[p] = lp[p]; arg[p] = k; }
-    }
-    if (out != nullptr) *reinterpret_cast<float4*>(out + k * HW) = make_float4(lp[0], lp[1], lp[2], lp[3]);
-  }
+  lsm_sweeps4<kWidePatch>(tp, tp + 1, tp + kWideCols, tp + kWideCols + 1, w00, w01, w10, w11, c, out, HW, arg);
   if (labels != nullptr) {
     if (LABEL_DTYPE == DRNMI_U8) {
       const uint32_t packed = static_cast<uint32_t>(arg[0]) | (static_cast<uint32_t>(arg[1]) << 8) |
@@ -136,6 +151,322 @@ up8_lsm_wide_kernel(const float* __restrict__ logits, const float* __restrict__ 
       for (int p = 0; p < 4; ++p) o[p] = arg[p];
     }
   }
+}
+
+// ---------------------------------------------------------------- labels only, NHWC logits, 1 .. 256 classes
+// The runtime-class-count form of ops.hip's up8_labels_tile_kernel (read that comment first): the
+// labels-only video head on the seg conv's fp32 NHWC rows [n][h][w][cs] (classes 0 .. c - 1 first;
+// the columns c .. cs - 1 are never read into a decision).  The labels are those of the labels-only
+// drnmi_up8_logsoftmax_argmax on the same values: the first k with lp > best over
+// lp = (v - vmax) - logf(sum), v = one mul + 3 fma over the taps (lsm_sweeps4).
+//
+// A workgroup owns TI x TJ tap windows (window (i1, j1) = the 8 x 8 output pixels whose taps are the
+// 1/8-res pixels (i1 - 1 .. i1, j1 - 1 .. j1)); TI x TJ <= 128 is chosen from c so that the tile's
+// (TI + 1) x (TJ + 1) logit vectors fit LDS (wide_tile_shape).
+//   1. the tile's vectors to LDS, pixel-major, VS floats apart (VS / 4 odd, so the vectors of
+//      neighbouring pixels start in different banks), by float4 row reads; a pixel outside the image
+//      is staged as up8_lsm_wide_kernel's clamped read (index 0, and its weight is 0);
+//   2. the per-pixel summary, four lanes per pixel over contiguous class ranges and merged in class
+//      order: argmax, top-2 margin, |best|, all classes finite;
+//   3. one window per thread: the fast path's test exactly as up8_labels_tile_kernel's -- interior
+//      window, the four taps share their argmax, every class finite and the smallest top-2 margin is
+//      at least
+//          guard = 2^-16 / min_phase(sum w) * (1 + 2^-10) + 2^-20 * max_t |L_t[best]|
+//      -- then the 64 labels are written with no per-pixel work; the others go to a slow list;
+//   4. a slow window per 16 lanes (8 rows x 2 four-pixel halves).  Interior all-finite windows first
+//      build their candidate list: class k is kept when max_t L_t[k] >= max_j min_t L_t[j] - guard
+//      (guard with max |L| over all taps and classes); a class below that can neither win nor come
+//      within 2^-16 of the winner anywhere in the window.  The 4 pixels are decided over the
+//      candidates (the same mul + 3 fma), and when the top two candidates of any of them are closer
+//      than 2^-16 -- and in border windows (a tap outside the image: clamped tap, zero weight) and
+//      windows with a non-finite tap -- lsm_sweeps4 runs over all c classes: the arithmetic of
+//      up8_lsm_wide_kernel, from the same function.
+// Why 2^-16 still separates argmax v from argmax lp at c <= 256: a pixel decided without the sweeps
+// has v_best - v_k >= 2^-16 for every other k (fast path and pruning: the bounds above, whose terms
+// -- the weights' sum, the rounding of one mul + 3 fma against max |L| -- do not depend on the class
+// count; candidates: tested).  Then v_best = vmax, v_best - vmax = 0 and lp_best = -lse exactly, and
+// for the others d = vmax - v_k >= 2^-16 is computed with a relative error of 2^-24 and
+// lp_k = fl(-d' - lse) with 0 <= lse <= ln 256 < 8: below 16 in magnitude the ulp of lp_k is at most
+// 2^-20 < d', above it is at most 2^-23 (d' + lse) < d', and rounding is monotone, so lp_k < lp_best
+// strictly and the first k with lp > best is argmax v.  An exact tie has d = 0 and takes the sweeps.
+// Labels are identical to the NCHW head's (tests/test_gpu_wide_labels.py).  Measured on a 150-class
+// network's logits, 2 x 1024 x 2048 (scripts/wide_labels_micro.py, profiles/many_classes_video): 208
+// us against 426 us for the labels-only up8_lsm_wide_kernel; on random logits 306 against 423 us.
+// The tile: 8 x 16 windows up to 32 classes, 4 x 16 up to 80, 4 x 8 above -- at most 29 KiB of
+// vectors up to 150 classes and 46 KiB at 256 (plus 7 KiB of static tables), so that four to five
+// workgroups share a CU's 160 KiB (two at 256): the slow windows' rounds are chains of dependent LDS
+// reads, and other workgroups' waves are what hides them.  Never above 64 KiB: no opt-in is needed.
+constexpr int kTileMaxPx = 9 * 17;                   // staged pixels of the largest tile (8 x 16 windows)
+
+__host__ __device__ inline void wide_tile_shape(int c, int& ti, int& tj, int& vs) {
+  ti = c <= 32 ? 8 : 4;
+  tj = c <= 80 ? 16 : 8;
+  vs = 4 * (((c + 3) >> 2) | 1);
+}
+
+template <int LABEL_DTYPE>
+__device__ __forceinline__ void store_wide_labels4(void* labels, int64_t pix, const int (&arg)[4]) {
+  if (LABEL_DTYPE == DRNMI_U8) {
+    const uint32_t packed = static_cast<uint32_t>(arg[0]) | (static_cast<uint32_t>(arg[1]) << 8) |
+                            (static_cast<uint32_t>(arg[2]) << 16) | (static_cast<uint32_t>(arg[3]) << 24);
+    *reinterpret_cast<uint32_t*>(reinterpret_cast<uint8_t*>(labels) + pix) = packed;
+  } else {
+    int64_t* o = reinterpret_cast<int64_t*>(labels) + pix;
+#pragma unroll
+    for (int p = 0; p < 4; ++p) o[p] = arg[p];
+  }
+}
+
+// STATS (the test entry): stats[0] += fast windows, [1] += pixels decided over candidates,
+// [2] += pixels through the sweeps
+template <int LABEL_DTYPE, bool STATS>
+__global__ void __launch_bounds__(256)
+up8_labels_wide_tile_kernel(const float* __restrict__ logits, const float* __restrict__ up_w, void* __restrict__ labels,
+                            int c, int cs, int h, int w, unsigned long long* __restrict__ stats) {
+  extern __shared__ __attribute__((aligned(16))) float vec[];     // [(TI + 1) * (TJ + 1)][VS]
+  __shared__ float wk[256];
+  __shared__ float wstat[1];
+  __shared__ float smarg[kTileMaxPx], sabsb[kTileMaxPx];
+  __shared__ int sam[kTileMaxPx];                    // argmax | 0x100 when every class is finite
+  __shared__ int nslow;
+  __shared__ unsigned short slist[128];              // window | 0x8000 when it builds candidates
+  __shared__ unsigned char clist[16][kWideMaxClasses];
+  __shared__ unsigned int scount[3];
+  int TI, TJ, VS;
+  wide_tile_shape(c, TI, TJ, VS);
+  const int PJ = TJ + 1, NPX = (TI + 1) * PJ, C4 = (c + 3) >> 2;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  wk[tid] = up_w[tid];
+  if (tid == 0) nslow = 0;
+  if (tid < 3) scount[tid] = 0;
+  __syncthreads();
+  if (wave == 0) {                                   // min over the 64 phases of sum w (0 if any w < 0)
+    const int ky1 = lane >> 3, kx1 = lane & 7;
+    const float a = wk[(ky1 + 8) * 16 + kx1 + 8], b = wk[(ky1 + 8) * 16 + kx1], cc = wk[ky1 * 16 + kx1 + 8],
+                d = wk[ky1 * 16 + kx1];
+    float lo = fminf(fminf(a, b), fminf(cc, d)) < 0.f ? 0.f : (a + b) + (cc + d);
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) lo = fminf(lo, __shfl_xor(lo, o));
+    if (lane == 0) wstat[0] = lo;
+  }
+  const int H = h * 8, W = w * 8;
+  const int I0 = blockIdx.y * TI, J0 = blockIdx.x * TJ;
+  const int n = blockIdx.z;
+  const int64_t HW = static_cast<int64_t>(H) * W;
+  const float* src = logits + static_cast<int64_t>(n) * h * w * cs;
+
+  // ---- 1. the tile's 1/8-res pixels (tap rows I0 - 1 .. I0 + TI - 1, columns J0 - 1 .. J0 + TJ - 1)
+#pragma unroll 4
+  for (int e = tid; e < NPX * C4; e += 256) {
+    const int px = e / C4, f = e - px * C4;
+    int iy = I0 - 1 + px / PJ, ix = J0 - 1 + px % PJ;
+    iy = (iy < 0 || iy >= h) ? 0 : iy;               // up8_lsm_wide_kernel's clamped read
+    ix = (ix < 0 || ix >= w) ? 0 : ix;
+    float4 v = *reinterpret_cast<const float4*>(src + (static_cast<int64_t>(iy) * w + ix) * cs + 4 * f);
+    v.y = 4 * f + 1 < c ? v.y : 0.f;                 // the row's padding columns
+    v.z = 4 * f + 2 < c ? v.z : 0.f;
+    v.w = 4 * f + 3 < c ? v.w : 0.f;
+    *reinterpret_cast<float4*>(vec + px * VS + 4 * f) = v;
+  }
+  __syncthreads();
+
+  // ---- 2. the per-pixel summary: lane s of a quad takes the float4 groups s F .. (s + 1) F - 1
+  const int F = (C4 + 3) >> 2;
+  for (int e0 = 0; e0 < NPX * 4; e0 += 256) {
+    const int px = (e0 + tid) >> 2, s = tid & 3;
+    float best = -INFINITY, second = -INFINITY;
+    int am = 0;
+    bool fin = true;
+    if (px < NPX) {
+      const int f1 = min((s + 1) * F, C4);
+      for (int f = s * F; f < f1; ++f) {
+        const float4 v = *reinterpret_cast<const float4*>(vec + px * VS + 4 * f);
+        const float x[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          const int k = 4 * f + j;
+          if (k < c) {
+            am = x[j] > best ? k : am;
+            second = __builtin_amdgcn_fmed3f(best, second, x[j]);
+            best = fmaxf(best, x[j]);
+            fin = fin && fabsf(x[j]) < INFINITY;     // false for NaN too
+          }
+        }
+      }
+    }
+#pragma unroll
+    for (int o = 1; o <= 2; o <<= 1) {               // the quad's ranges in class order: first maximum wins
+      const float ob = __shfl_xor(best, o), os = __shfl_xor(second, o);
+      const int oa = __shfl_xor(am, o), of = __shfl_xor(static_cast<int>(fin), o);
+      const bool upper = (tid & o) != 0;             // this lane holds the higher classes
+      const float lo_b = upper ? ob : best, hi_b = upper ? best : ob;
+      const int lo_a = upper ? oa : am, hi_a = upper ? am : oa;
+      am = hi_b > lo_b ? hi_a : lo_a;
+      second = fmaxf(fminf(best, ob), fmaxf(second, os));
+      best = fmaxf(best, ob);
+      fin = fin && of != 0;
+    }
+    if (px < NPX && s == 0) {
+      smarg[px] = best - second;
+      sabsb[px] = fabsf(best);
+      sam[px] = am | (fin ? 0x100 : 0);
+    }
+  }
+  __syncthreads();
+
+  // ---- 3. one window per thread
+  const float wmin = wstat[0];
+  if (tid < TI * TJ) {
+    const int ti = tid / TJ, tj = tid - ti * TJ;
+    const int i1 = I0 + ti, j1 = J0 + tj;
+    if (i1 <= h && j1 <= w) {
+      bool fast = false, cand = false;
+      int cls = 0;
+      if (i1 >= 1 && i1 < h && j1 >= 1 && j1 < w) {
+        const int p[4] = {ti * PJ + tj, ti * PJ + tj + 1, (ti + 1) * PJ + tj, (ti + 1) * PJ + tj + 1};
+        cls = sam[p[0]] & 0xff;
+        bool same = true, finite = true;
+        float mmin = INFINITY, amax = 0.f;
+#pragma unroll
+        for (int t = 0; t < 4; ++t) {
+          const int a = sam[p[t]];
+          same = same && (a & 0xff) == cls;
+          finite = finite && (a & 0x100) != 0;
+          mmin = fminf(mmin, smarg[p[t]]);
+          amax = fmaxf(amax, sabsb[p[t]]);
+        }
+        fast = same && wmin > 0.f && finite && mmin >= 0x1p-16f / wmin * (1.f + 0x1p-10f) + 0x1p-20f * amax;
+        cand = !fast && finite && wmin > 0.f;
+      }
+      if (fast) {
+        const int la[4] = {cls, cls, cls, cls};
+#pragma unroll
+        for (int r = 0; r < 8; ++r) {
+          const int64_t row = static_cast<int64_t>(n) * HW + static_cast<int64_t>(8 * i1 - 4 + r) * W;
+          store_wide_labels4<LABEL_DTYPE>(labels, row + 8 * j1 - 4, la);
+          store_wide_labels4<LABEL_DTYPE>(labels, row + 8 * j1, la);
+        }
+        if (STATS) atomicAdd(&scount[0], 1u);
+      } else {
+        const int at = atomicAdd(&nslow, 1);
+        slist[at] = static_cast<unsigned short>(tid | (cand ? 0x8000 : 0));
+      }
+    }
+  }
+  __syncthreads();
+
+  // ---- 4. the slow windows, one per 16 lanes per round (every thread runs every round: barriers)
+  const int ns = nslow;
+  const int g = tid >> 4, l = tid & 15, gsh = 16 * (g & 3);
+  for (int e0 = 0; e0 < ns; e0 += 16) {
+    const bool act = e0 + g < ns;
+    const int wt = act ? slist[e0 + g] : 0;
+    const bool cand = (wt & 0x8000) != 0;
+    const int ti = (wt & 0x7fff) / TJ, tj = (wt & 0x7fff) - ti * TJ;
+    const int i1 = I0 + ti, j1 = J0 + tj;
+    const float* t00 = vec + (ti * PJ + tj) * VS;    // taps (i0, j0), (i0, j1), (i1, j0), (i1, j1)
+    const float* t01 = t00 + VS;
+    const float* t10 = t00 + PJ * VS;
+    const float* t11 = t10 + VS;
+    // the candidate list: lane l takes the classes l, l + 16, ..
+    float lmax = -INFINITY, vabs = 0.f;
+    if (cand)
+      for (int k = l; k < c; k += 16) {
+        const float a0 = t00[k], a1 = t01[k], a2 = t10[k], a3 = t11[k];
+        vabs = fmaxf(vabs, fmaxf(fmaxf(fabsf(a0), fabsf(a1)), fmaxf(fabsf(a2), fabsf(a3))));
+        lmax = fmaxf(lmax, fminf(fminf(a0, a1), fminf(a2, a3)));
+      }
+#pragma unroll
+    for (int o = 8; o >= 1; o >>= 1) {
+      lmax = fmaxf(lmax, __shfl_xor(lmax, o));
+      vabs = fmaxf(vabs, __shfl_xor(vabs, o));
+    }
+    const float thr = lmax - (0x1p-16f / wmin * (1.f + 0x1p-10f) + 0x1p-20f * vabs);
+    int cnt = 0;
+    for (int k0 = 0; k0 < c; k0 += 16) {
+      const int k = k0 + l;
+      bool keep = false;
+      if (cand && k < c) keep = fmaxf(fmaxf(t00[k], t01[k]), fmaxf(t10[k], t11[k])) >= thr;
+      const unsigned int bits = static_cast<unsigned int>(__ballot(keep) >> gsh) & 0xffffu;
+      if (keep) clist[g][cnt + __popc(bits & ((1u << l) - 1u))] = static_cast<unsigned char>(k);
+      cnt += __popc(bits);
+    }
+    __syncthreads();
+    const int r = l & 7, hh = l >> 3;
+    const int q = 2 * j1 - 1 + hh;                   // output columns 4 q .. 4 q + 3
+    const int oy = 8 * i1 - 4 + r;
+    if (act && q >= 0 && 4 * q < W && oy >= 0 && oy < H) {
+      const bool vi0 = i1 - 1 >= 0, vi1 = i1 < h, vj0 = j1 - 1 >= 0, vj1 = j1 < w;
+      const int ky1 = r, ky0 = r + 8;
+      float w00[4], w01[4], w10[4], w11[4];
+#pragma unroll
+      for (int p = 0; p < 4; ++p) {
+        const int kx1 = 4 * hh + p, kx0 = kx1 + 8;   // 4 q + p + 4 - 8 j1
+        w00[p] = (vi0 && vj0) ? wk[ky0 * 16 + kx0] : 0.f;
+        w01[p] = (vi0 && vj1) ? wk[ky0 * 16 + kx1] : 0.f;
+        w10[p] = (vi1 && vj0) ? wk[ky1 * 16 + kx0] : 0.f;
+        w11[p] = (vi1 && vj1) ? wk[ky1 * 16 + kx1] : 0.f;
+      }
+      int arg[4] = {0, 0, 0, 0};
+      bool decided = false;
+      if (cand) {
+        float best[4] = {-INFINITY, -INFINITY, -INFINITY, -INFINITY};
+        float second[4] = {-INFINITY, -INFINITY, -INFINITY, -INFINITY};
+        for (int i = 0; i < cnt; ++i) {
+          const int k = clist[g][i];
+          const float s00 = t00[k], s01 = t01[k], s10 = t10[k], s11 = t11[k];
+#pragma unroll
+          for (int p = 0; p < 4; ++p) {
+            float v = s00 * w00[p];
+            v = fmaf(s01, w01[p], v);
+            v = fmaf(s10, w10[p], v);
+            v = fmaf(s11, w11[p], v);
+            arg[p] = v > best[p] ? k : arg[p];
+            second[p] = __builtin_amdgcn_fmed3f(best[p], second[p], v);
+            best[p] = fmaxf(best[p], v);
+          }
+        }
+        decided = true;
+#pragma unroll
+        for (int p = 0; p < 4; ++p) decided = decided && !(best[p] - second[p] < 0x1p-16f);
+      }
+      if (!decided) lsm_sweeps4<1>(t00, t01, t10, t11, w00, w01, w10, w11, c, nullptr, 0, arg);
+      store_wide_labels4<LABEL_DTYPE>(labels, static_cast<int64_t>(n) * HW + static_cast<int64_t>(oy) * W + 4 * q, arg);
+      if (STATS) atomicAdd(&scount[decided ? 1 : 2], 4u);
+    }
+    __syncthreads();
+  }
+  if (STATS) {
+    if (tid < 3 && scount[tid] != 0) atomicAdd(&stats[tid], static_cast<unsigned long long>(scount[tid]));
+  }
+}
+
+template <int LABEL_DTYPE, bool STATS>
+int launch_labels_wide_tile(const float* logits, int cs, const float* up_w, void* labels, int n, int c, int h, int w,
+                            int64_t* stats, hipStream_t s) {
+  int ti, tj, vs;
+  wide_tile_shape(c, ti, tj, vs);
+  const size_t lds = static_cast<size_t>((ti + 1) * (tj + 1)) * vs * sizeof(float);
+  const dim3 grid(static_cast<unsigned>((w + tj) / tj), static_cast<unsigned>((h + ti) / ti), static_cast<unsigned>(n));
+  hipLaunchKernelGGL((up8_labels_wide_tile_kernel<LABEL_DTYPE, STATS>), grid, dim3(256), lds, s, logits, up_w, labels, c,
+                     cs, h, w, reinterpret_cast<unsigned long long*>(stats));
+  return static_cast<int>(hipGetLastError());
+}
+
+template <bool STATS>
+int labels_wide_tile_dispatch(const float* logits, int cs, const float* up_w, void* labels, int label_dtype, int n,
+                              int c, int h, int w, int64_t* stats, hipStream_t s) {
+  if (logits == nullptr || up_w == nullptr || labels == nullptr || (STATS && stats == nullptr)) return DRNMI_EINVAL;
+  if (n <= 0 || h <= 0 || w <= 0) return DRNMI_EINVAL;
+  if (c <= 0 || c > kWideMaxClasses) return DRNMI_ENOTSUP;
+  if (label_dtype != DRNMI_U8 && label_dtype != DRNMI_I64) return DRNMI_EINVAL;
+  if (cs < c || cs % 4 != 0 || (reinterpret_cast<uintptr_t>(logits) & 15) != 0) return DRNMI_EINVAL;
+  if ((reinterpret_cast<uintptr_t>(labels) & (label_dtype == DRNMI_I64 ? 7 : 3)) != 0) return DRNMI_EINVAL;
+  if (STATS && (reinterpret_cast<uintptr_t>(stats) & 7) != 0) return DRNMI_EINVAL;
+  if (h > 65535 || w > (1 << 27) || n > 65535) return DRNMI_EINVAL;   // grid.y, grid.z; 8 w in an int
+  if (label_dtype == DRNMI_I64)
+    return launch_labels_wide_tile<DRNMI_I64, STATS>(logits, cs, up_w, labels, n, c, h, w, stats, s);
+  return launch_labels_wide_tile<DRNMI_U8, STATS>(logits, cs, up_w, labels, n, c, h, w, stats, s);
 }
 
 // ---------------------------------------------------------------- bilinear x8 (use_torch_up), wide
@@ -318,4 +649,18 @@ extern "C" int drnmi_up8_logsoftmax_argmax_wide(const float* logits, const float
                                                 int32_t label_dtype, int32_t n, int32_t c, int32_t h, int32_t w,
                                                 void* stream) {
   return up8_wide_dispatch(logits, up_w, logprobs, labels, label_dtype, n, c, h, w, reinterpret_cast<hipStream_t>(stream));
+}
+
+extern "C" int drnmi_up8_labels_nhwc_wide(const float* logits, int32_t cs, const float* up_w, void* labels,
+                                          int32_t label_dtype, int32_t n, int32_t c, int32_t h, int32_t w,
+                                          void* stream) {
+  return labels_wide_tile_dispatch<false>(logits, cs, up_w, labels, label_dtype, n, c, h, w, nullptr,
+                                          reinterpret_cast<hipStream_t>(stream));
+}
+
+extern "C" int drnmi_up8_labels_nhwc_wide_stats(const float* logits, int32_t cs, const float* up_w, void* labels,
+                                                int32_t label_dtype, int32_t n, int32_t c, int32_t h, int32_t w,
+                                                void* stream, int64_t* stats) {
+  return labels_wide_tile_dispatch<true>(logits, cs, up_w, labels, label_dtype, n, c, h, w, stats,
+                                         reinterpret_cast<hipStream_t>(stream));
 }

@@ -85,6 +85,8 @@ SIGNATURES = {
     "drnmi_up8_logsoftmax_argmax": (ctypes.c_int, [_VP, _VP, _VP, _VP, _I32, _I32, _I32, _I32, _I32, _VP]),
     "drnmi_up8_logsoftmax_argmax_wide": (ctypes.c_int, [_VP, _VP, _VP, _VP, _I32, _I32, _I32, _I32, _I32, _VP]),
     "drnmi_up8_labels_nhwc": (ctypes.c_int, [_VP, _I32, _VP, _VP, _I32, _I32, _I32, _I32, _I32, _VP]),
+    "drnmi_up8_labels_nhwc_wide": (ctypes.c_int, [_VP, _I32, _VP, _VP, _I32, _I32, _I32, _I32, _I32, _VP]),
+    "drnmi_up8_labels_nhwc_wide_stats": (ctypes.c_int, [_VP, _I32, _VP, _VP, _I32, _I32, _I32, _I32, _I32, _VP, _VP]),
     "drnmi_up8_labels_seg2": (ctypes.c_int, [_VP, _I32, _VP, _VP, _VP, _I32, _I32, _I32, _I32, _I32, _VP]),
     "drnmi_conv_stag_seg": (ctypes.c_int, [ctypes.POINTER(ConvArgs), _VP, _I32, _I32, _VP, _VP]),
     "drnmi_conv_stag_seg_kernel_name": (ctypes.c_char_p, [ctypes.POINTER(ConvArgs)]),

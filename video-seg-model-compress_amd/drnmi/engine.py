@@ -668,19 +668,26 @@ class Plan:
     # stores instead of 19 strided planes) and drnmi_up8_labels_nhwc reads them; same values,
     # same labels.  Only where the seg conv runs on conv_big (bf16 input), on the int8 tile
     # (int8 nets: store_tile_i8's 16-B fp32 rows) or on conv_x6 (fp32x) and the 19-class head.
+    # Any other class count 1 .. 256 (bf16 and int8 plans): rows of round_up(classes, 4) floats
+    # and drnmi_up8_labels_nhwc_wide; the seg classifier is not folded into the last conv there.
     SEG_NHWC_CS = 20
 
     def _setup_seg_nhwc(self):
         self.seg_idx, self.seg_nhwc_args, self.seg_fused = -1, None, None
+        self.seg_classes, self.seg_cs = 19, self.SEG_NHWC_CS
         nodes = self.packed.graph.nodes
         idx = [i for i, nd in enumerate(nodes) if nd.out_fp32_nchw]
         if len(idx) != 1 or self.args[idx[0]] is None:
             return
         i = idx[0]
         nd, a0 = nodes[i], self.args[i]
-        if nd.conv.out_channels != 19 or nd.conv.kernel_size[0] != 1:
+        classes = nd.conv.out_channels
+        if nd.conv.kernel_size[0] != 1 or not 1 <= classes <= 256:
             return
-        cs = self.SEG_NHWC_CS
+        wide = classes != 19
+        if wide and self.packed.precision not in ("bf16", "int8"):
+            return                               # fp32 / fp32x plans keep the logits planes
+        cs = (classes + 3) // 4 * 4 if wide else self.SEG_NHWC_CS
         lh, lw = self.shapes[nd.dst]
         a = _lib.ConvArgs()
         ctypes.pointer(a)[0] = a0
@@ -694,7 +701,9 @@ class Plan:
                                                    device=self.packed.device)
         a.y = self.bufs["logits_nhwc"].data_ptr()
         self.seg_idx, self.seg_nhwc_args = i, a
-        self._setup_seg_fused(i)
+        self.seg_classes, self.seg_cs = classes, cs
+        if not wide:
+            self._setup_seg_fused(i)
 
     def _setup_seg_fused(self, i: int):
         """The seg classifier folded into its producer's epilogue (drnmi_conv_stag_seg) when that
@@ -963,9 +972,15 @@ class Plan:
             lab_dtype, n, c, lh, lw, ctypes.c_void_p(stream)), "up8_logsoftmax_argmax")
 
     def head_labels_nhwc(self, up_w: torch.Tensor, stream: int, labels: torch.Tensor):
-        """Labels from the NHWC logits run_backbone(labels_only=True) wrote (drnmi_up8_labels_nhwc)."""
+        """Labels from the NHWC logits run_backbone(labels_only=True) wrote (drnmi_up8_labels_nhwc; any class
+        count but 19: drnmi_up8_labels_nhwc_wide)."""
         lh, lw = self.shapes["logits"]
         lab_dtype = _lib.DRNMI_I64 if labels.dtype == torch.int64 else _lib.DRNMI_U8
+        if self.seg_classes != 19:
+            _lib.check(_lib.load().drnmi_up8_labels_nhwc_wide(
+                self.bufs["logits_nhwc"].data_ptr(), self.seg_cs, up_w.data_ptr(), labels.data_ptr(), lab_dtype,
+                self.n, self.seg_classes, lh, lw, ctypes.c_void_p(stream)), "up8_labels_nhwc_wide")
+            return
         _lib.check(_lib.load().drnmi_up8_labels_nhwc(
             self.bufs["logits_nhwc"].data_ptr(), self.SEG_NHWC_CS, up_w.data_ptr(), labels.data_ptr(), lab_dtype,
             self.n, 19, lh, lw, ctypes.c_void_p(stream)), "up8_labels_nhwc")
