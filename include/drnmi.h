@@ -605,6 +605,42 @@ int drnmi_sgd_step_f32(int32_t ntensors, float* const* params, const float* cons
                        float momentum, float dampening, float weight_decay, int32_t nesterov,
                        void* stream);
 
+/* Fine-tune data path (csrc/ingest.hip): the batch of the train() / validate() loop made on the
+ * GPU from uint8 images and labels.  Replaces the per-sample PIL / numpy pipeline of
+ * semantic_seg.py:885-889 and :918-921: RandomCrop with reflection padding
+ * (data_transforms.py:9-45, :128-155), RandomHorizontalFlip (:96-106), ToTensor (:228-253) and
+ * Normalize (:109-125).  The random draws and the padding geometry stay on the host
+ * (drnmi/data.py); they reach the kernel as two index tables per sample.
+ *   images  device uint8 [n][h][w][3];  labels  device uint8 [n][h][w], or NULL with target == NULL;
+ *   rowmap  device int32 [n][th], colmap device int32 [n][tw].  An entry e >= 0 is a source row /
+ *           column inside the image.  An entry e < 0 marks a padded position: its image source
+ *           index is ~e (the reflection) and its label is 255 (the 'constant' pad, :31-32).
+ *   mean3 / std3  HOST pointers to 3 floats, as in drnmi_frame_ingest_u8;
+ *   out     fp32 NCHW [n][3][th][tw], 16-byte aligned:
+ *             out[i][c][y][x] = (float(images[i][r][q][c]) / 255.0f - mean[c]) / std[c]
+ *           with r / q the decoded entries of rowmap[i][y] / colmap[i][x]: division, subtraction,
+ *           division in fp32, nothing contracted -- the sequence of drnmi_frame_ingest_u8, bit-identical
+ *           to img.float().div(255) followed by sub_(m).div_(s);
+ *   target  int64 [n][th][tw], 8-byte aligned: 255 where rowmap or colmap is negative, else
+ *           labels[i][r][q] (ToTensor's LongTensor, :253).
+ * The kernel clamps every decoded index into [0, h-1] / [0, w-1] before it reads: no table content
+ * makes it read outside the images.  64-bit indexing, no allocation, no host synchronisation
+ * (graph-capturable).  DRNMI_EINVAL before any HIP call: NULL images / rowmap / colmap / out / mean3 /
+ * std3, labels and target not both NULL or both set, a non-positive size, out not 16-byte or target
+ * not 8-byte aligned, n * h * w or n * th * tw above 2^40. */
+int drnmi_train_ingest_u8(const uint8_t* images, const uint8_t* labels, int32_t n, int32_t h, int32_t w,
+                          const int32_t* rowmap, const int32_t* colmap, int32_t th, int32_t tw,
+                          const float* mean3, const float* std3, float* out, int64_t* target, void* stream);
+
+/* Pixel accuracy, eval_score=accuracy (utils.py:267-277; semantic_seg.py:1072, :1004), in one pass
+ * over log-probs [n][c][hw] and int64 targets [n][hw].  counts is device int64[2], accumulated and
+ * NOT cleared (like drnmi_confusion_matrix): counts[0] += pixels with target != ignore_index,
+ * counts[1] += those whose argmax over c equals the target (a tie takes the lowest index, as in
+ * drnmi_argmax_nchw_f32).  A target outside 0..c-1 other than ignore_index counts and is never
+ * correct.  DRNMI_EINVAL: NULL pointers, non-positive sizes, n * hw above 2^40 or c above 2^20. */
+int drnmi_pixel_accuracy_f32(const float* logprobs, const int64_t* target, int32_t n, int32_t c, int64_t hw,
+                             int64_t ignore_index, int64_t* counts, void* stream);
+
 /* Library version string, e.g. "drnmi 0.1.0 gfx950". */
 const char* drnmi_version(void);
 

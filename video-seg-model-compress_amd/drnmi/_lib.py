@@ -130,6 +130,8 @@ SIGNATURES = {
     "drnmi_quantize_i8": (ctypes.c_int, [_VP, _I32, _VP, _I64, _F32, _VP]),
     "drnmi_absmax": (ctypes.c_int, [_VP, _I32, _I64, _VP, _VP]),
     "drnmi_abs_histogram": (ctypes.c_int, [_VP, _I32, _I64, _VP, _VP]),
+    "drnmi_train_ingest_u8": (ctypes.c_int, [_VP, _VP, _I32, _I32, _I32, _VP, _VP, _I32, _I32, _VP, _VP, _VP, _VP, _VP]),
+    "drnmi_pixel_accuracy_f32": (ctypes.c_int, [_VP, _VP, _I32, _I32, _I64, _I64, _VP, _VP]),
     "drnmi_version": (ctypes.c_char_p, []),
     "drnmi_abi_version": (ctypes.c_int32, []),
     "drnmi_conv_args_size": (ctypes.c_int64, []),

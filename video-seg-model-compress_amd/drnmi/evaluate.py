@@ -7,6 +7,8 @@ rows a18/a19, §8f row 4), same names and arguments.
   test_ms(eval_data_loader, model, num_classes, scales, has_gt=True,
           output_dir='pred', save_vis=False)                       semantic_seg.py:507-557
   resize_4d_tensor(tensor, width, height)                         semantic_seg.py:471-504
+  validate(val_loader, model, criterion, epoch, writer, args,
+           eval_score=None, print_freq=10)                         semantic_seg.py:234-283
 
 Everything per image stays on the device: the forward (DRNSeg, HIP engine), the Pillow-exact
 bilinear resize of every log-prob plane and the fp32 scale sum (drnmi_resize_bilinear_f32,
@@ -138,4 +140,60 @@ def test_ms(eval_data_loader, model, num_classes, scales, has_gt=True, *, output
     return preds
 
 
-__all__ = ["resize_4d_tensor", "test", "val_miou", "test_ms"]
+def validate(val_loader, model, criterion, epoch=0, writer=None, args=None, eval_score=None, print_freq=10):
+    """semantic_seg.py:234-283 -- the per-epoch validation of the fine-tune loop: eval-mode
+    model(input)[0], criterion(output, target.long().squeeze(1)), eval_score(output, target), each
+    averaged with the weight input.size(0) as the reference's AverageMeter does (sum += val * n,
+    avg = sum / count).  Returns score.avg (0 when eval_score is None) and sends the loss mean to
+    writer.add_scalar('Loss/Eval', ., epoch) when a writer is given.
+
+    The sums stay on the device: the loss in fp64 (the reference's meter adds the Python floats
+    of loss.item()), the score in fp32 (its meter adds the fp32 score tensors).  The host reads
+    them only to print, every print_freq batches, and at the end; the reference's loss.item()
+    synchronises every batch.  Deviations: epoch / writer / args are optional; the bare
+    print(loss_val) after every batch is dropped; the returned score is a Python float (the
+    reference returns the 0-dim tensor)."""
+    import time
+    model.eval()
+    dev = _device_of(_unwrap(model))
+    loss_sum = torch.zeros((), dtype=torch.float64, device=dev)
+    score_sum = torch.zeros((), dtype=torch.float32, device=dev)
+    count = 0
+    loss_val = 0.0
+    n_batches = len(val_loader) if hasattr(val_loader, "__len__") else -1
+    end = time.time()
+    with torch.no_grad():
+        for i, (input, target) in enumerate(val_loader):
+            if type(criterion) in (torch.nn.L1Loss, torch.nn.MSELoss):
+                target = target.float()
+            input = input.to(dev)
+            target = target.to(dev, non_blocking=True)
+            target_var = target.long()
+            if target_var.dim() == 4:                       # the reference's squeeze(1) of [n, 1, h, w]
+                target_var = target_var.squeeze(1)
+            output = model(input)[0]
+            loss = criterion(output, target_var)
+            bs = input.size(0)
+            loss_sum += loss.detach().double() * bs
+            count += bs
+            s = None
+            if eval_score is not None:
+                s = eval_score(output, target_var)
+                score_sum += torch.as_tensor(s, dtype=torch.float32, device=dev) * bs
+            if i % print_freq == 0:
+                now = time.time()
+                print('Test: [{0}/{1}]\tTime {2:.3f}\tLoss {3:.4f} ({4:.4f})\tScore {5:.3f} ({6:.3f})'.format(
+                    i, n_batches, now - end, float(loss), float(loss_sum) / count,
+                    float(s) if s is not None else 0.0, float(score_sum) / count))
+                end = now
+    if count:
+        loss_val = float(loss_sum) / count
+    score_avg = float(score_sum / count) if (eval_score is not None and count) else 0
+    print(' * Loss {} : {}'.format(loss_val, epoch))
+    if writer is not None:
+        writer.add_scalar('Loss/Eval', loss_val, epoch)
+    print(' * Score {:.3f}'.format(score_avg))
+    return score_avg
+
+
+__all__ = ["resize_4d_tensor", "test", "val_miou", "test_ms", "validate"]

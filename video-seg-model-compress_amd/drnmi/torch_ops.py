@@ -36,6 +36,11 @@ Ops (schema -> reference):
   drnmi::segment_render(Tensor frames_u8, int model, float[] mean, float[] std, bool bgr,
                         Tensor palette, int alpha_q8, bool overlay) -> (Tensor labels, Tensor image)
       drnmi::segment, then the colour image (overlay=False) or the overlay at the frames' size
+  drnmi::train_ingest(Tensor images_u8, Tensor? labels_u8, Tensor rowmap, Tensor colmap, float[] mean,
+                      float[] std) -> (Tensor input, Tensor target)
+      the training transform list (semantic_seg.py:885-889: RandomCrop with reflection padding,
+      RandomHorizontalFlip, ToTensor, Normalize) on a uint8 batch, crop / pad / flip given as the
+      index tables of drnmi.data.index_maps; target is empty when labels is None
 `model` is the handle of a live drnmi.drnseg.DRNSeg (its packed weights and launch plans are
 the op's state; DRNSeg.segment / forward / predict pass their own handle).
 """
@@ -273,5 +278,69 @@ def _(frames_u8, model, mean, std, bgr, palette, alpha_q8, overlay):
             frames_u8.new_empty((n, h, w, 3), dtype=torch.uint8))
 
 
+# ------------------------------------------------------------------ fine-tune data path
+def _ingest_check(images, labels, rowmap, colmap, mean, std):
+    if images.dtype != torch.uint8 or images.dim() != 4 or images.shape[3] != 3:
+        raise TypeError("drnmi::train_ingest: images must be uint8 [n, h, w, 3]")
+    n, h, w, _ = images.shape
+    if labels is not None and (labels.dtype != torch.uint8 or tuple(labels.shape) != (n, h, w)
+                               or labels.device != images.device):
+        raise TypeError("drnmi::train_ingest: labels must be uint8 [n, h, w] on the images' device")
+    for name, t in (("rowmap", rowmap), ("colmap", colmap)):
+        if t.dtype != torch.int32 or t.dim() != 2 or t.shape[0] != n or t.shape[1] < 1 or t.device != images.device:
+            raise TypeError(f"drnmi::train_ingest: {name} must be int32 [n, size] on the images' device")
+    if len(mean) != 3 or len(std) != 3:
+        raise ValueError("drnmi::train_ingest: mean and std must have 3 entries")
+
+
+def train_ingest_into(images, labels, rowmap, colmap, mean, std, out, target) -> None:
+    """drnmi_train_ingest_u8 into caller-owned `out` fp32 [n, 3, th, tw] / `target` int64
+    [n, th, tw] (contiguous; slices of a batch).  A slice the C-ABI refuses for its alignment
+    (an odd th * tw puts sample i's planes off the 16-byte grid) is made in a fresh tensor and
+    copied."""
+    _ingest_check(images, labels, rowmap, colmap, mean, std)
+    n, h, w, _ = images.shape
+    th, tw = rowmap.shape[1], colmap.shape[1]
+    if (labels is None) != (target is None):
+        raise ValueError("drnmi::train_ingest: labels and target go together")
+    if tuple(out.shape) != (n, 3, th, tw) or out.dtype != torch.float32 or not out.is_contiguous():
+        raise ValueError("drnmi::train_ingest: out must be contiguous fp32 [n, 3, th, tw]")
+    if target is not None and (tuple(target.shape) != (n, th, tw) or target.dtype != torch.int64
+                               or not target.is_contiguous()):
+        raise ValueError("drnmi::train_ingest: target must be contiguous int64 [n, th, tw]")
+    dst = out if out.data_ptr() % 16 == 0 else torch.empty_like(out)
+    images, rowmap, colmap = images.contiguous(), rowmap.contiguous(), colmap.contiguous()
+    labels = labels.contiguous() if labels is not None else None
+    f3 = ctypes.c_float * 3
+    _lib.check(_lib.load().drnmi_train_ingest_u8(
+        images.data_ptr(), labels.data_ptr() if labels is not None else None, n, h, w, rowmap.data_ptr(),
+        colmap.data_ptr(), th, tw, f3(*mean), f3(*std), dst.data_ptr(),
+        target.data_ptr() if target is not None else None, ctypes.c_void_p(_lib.stream_ptr(images.device))),
+        "drnmi::train_ingest")
+    if dst is not out:
+        out.copy_(dst)
+
+
+@torch.library.custom_op("drnmi::train_ingest", mutates_args=(), device_types="cuda")
+def train_ingest(images: torch.Tensor, labels: torch.Tensor | None, rowmap: torch.Tensor, colmap: torch.Tensor,
+                 mean: list[float], std: list[float]) -> tuple[torch.Tensor, torch.Tensor]:
+    """RandomCrop (reflection pad) + RandomHorizontalFlip + ToTensor + Normalize of a uint8 batch
+    (semantic_seg.py:885-889) through the index tables of drnmi.data.index_maps: fp32 input
+    [n, 3, th, tw] and int64 target [n, th, tw] (empty when labels is None)."""
+    _ingest_check(images, labels, rowmap, colmap, mean, std)
+    n, th, tw = images.shape[0], rowmap.shape[1], colmap.shape[1]
+    out = torch.empty(n, 3, th, tw, device=images.device, dtype=torch.float32)
+    target = torch.empty((n, th, tw) if labels is not None else (0,), device=images.device, dtype=torch.int64)
+    train_ingest_into(images, labels, rowmap, colmap, mean, std, out, target if labels is not None else None)
+    return out, target
+
+
+@train_ingest.register_fake
+def _(images, labels, rowmap, colmap, mean, std):
+    n, th, tw = images.shape[0], rowmap.shape[1], colmap.shape[1]
+    return (images.new_empty((n, 3, th, tw), dtype=torch.float32),
+            images.new_empty((n, th, tw) if labels is not None else (0,), dtype=torch.int64))
+
+
 __all__ = ["conv2d_bn_act", "up8_logsoftmax_argmax", "mask_apply_", "segment", "forward", "predict",
-           "render_labels", "segment_render", "register_model"]
+           "render_labels", "segment_render", "train_ingest", "train_ingest_into", "register_model"]

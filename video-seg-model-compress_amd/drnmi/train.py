@@ -662,6 +662,31 @@ class CrossEntropyLoss(torch.nn.Module):
         return _CEFn.apply(logprobs.contiguous(), target.contiguous(), self.ignore_index)
 
 
+# ====================================================================== eval score
+def accuracy(output: torch.Tensor, target: torch.Tensor, ignore_index: int = 255) -> torch.Tensor:
+    """utils.accuracy drop-in for `eval_score=accuracy` (utils.py:267-277; semantic_seg.py:1072,
+    :1004): the percentage of pixels with target != ignore_index whose argmax over the class planes
+    equals the target, as a 0-dim fp32 device tensor float32(correct) * float32(100.0 / count).
+    One pass (drnmi_pixel_accuracy_f32) instead of the reference's argmax plus boolean-index
+    gather, and no host synchronisation.  count == 0 gives NaN (the reference raises
+    ZeroDivisionError there)."""
+    if not output.is_cuda:
+        raise RuntimeError("drnmi accuracy runs on the HIP kernel (no CPU fallback)")
+    if output.dtype != torch.float32 or output.dim() < 2:
+        raise ValueError("expected fp32 [n, c, ...] scores")
+    if target.dtype != torch.int64:
+        raise ValueError("expected int64 targets (semantic_seg.py:195 target.long())")
+    n, c = output.shape[0], output.shape[1]
+    hw = output[0, 0].numel()
+    if target.numel() != n * hw or target.device != output.device:
+        raise ValueError(f"target shape {tuple(target.shape)} does not match {tuple(output.shape)}")
+    output, target = output.detach().contiguous(), target.contiguous()
+    counts = torch.zeros(2, dtype=torch.int64, device=output.device)
+    _lib.check(_lib.load().drnmi_pixel_accuracy_f32(_vp(output), _vp(target), n, c, hw, int(ignore_index), _vp(counts),
+                                                    ctypes.c_void_p(_lib.stream_ptr(output.device))), "pixel_accuracy")
+    return counts[1].float() * (100.0 / counts[0].double()).float()
+
+
 # ====================================================================== optimizer
 class SGD(torch.optim.Optimizer):
     """torch.optim.SGD drop-in (semantic_seg.py:963-966) whose step is one multi-tensor HIP
