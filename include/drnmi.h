@@ -74,7 +74,7 @@ typedef struct drnmi_conv_args {
   int32_t relu;             /* 1: ReLU after the (optional) residual add            */
   int32_t dtype;            /* DRNMI_BF16 or DRNMI_F32: x, w, res                   */
   int32_t out_dtype;        /* DRNMI_BF16 or DRNMI_F32: y                           */
-  int32_t tile;             /* tile id (drnmi_conv_tile_name), -1 = auto            */
+  int32_t tile;             /* enum drnmi_tile (below), DRNMI_TILE_AUTO = -1        */
   int32_t algo;             /* DRNMI_ALGO_IGEMM or DRNMI_ALGO_PATCH (see below)     */
   int32_t src_u8;           /* PATCH only: x is uint8 HWC3 frames, normalised on load */
   int32_t bgr;              /* src_u8: swap channel 0 and 2 on read                  */
@@ -133,16 +133,7 @@ typedef struct drnmi_conv_args {
 
 /* Algorithms behind drnmi_conv2d_bn_act:
  *  DRNMI_ALGO_IGEMM  NHWC implicit GEMM (any power-of-two cin >= 8, any ks/stride/dil; bf16 or
- *                    fp32).  tile -1 picks the bf16 LDS-DMA kernel (tiles 4..7: 128/256/64/64
- *                    output channels x 256 pixels, tile 6 with 32-channel K steps, tile 7 with
- *                    64; cin >= 64, ks 1 or 3) when it applies, else a
- *                    register-staged tile 0..3 by cout.  Whole 256-pixel output rows (3x3, stride
- *                    1, cin % 128 == 0) route to the strip tiles: 19 conv_stag (256 / 128
- *                    channels, 8 waves with staggered SIMD partners), 22 conv_w1 (the same tile
- *                    as 4 waves of 128 x 128, one per SIMD; auto at cin >= 512 without residual),
- *                    23 conv_w1h (128 x 128 tiles, two workgroups per CU; auto at cout 128) --
- *                    all with the same K order, so bit-identical.  int8 (dtype DRNMI_I8) takes
- *                    19 / 22 / 23 as its int8 forms (auto: 23 at cin, cout <= 256, else 19).
+ *                    fp32), on the tile drnmi_conv_args.tile names (enum drnmi_tile below).
  *  DRNMI_ALGO_PATCH  bf16-only small-channel direct conv for the full-resolution layers
  *                    (lmodels/drn.py:132-137 layer0, :201-211 layer1/layer2): the input tile
  *                    plus halo is staged once in LDS and reused by all ks*ks taps; weights stay
@@ -155,7 +146,42 @@ typedef struct drnmi_conv_args {
  *                    c = 3 are zero), which also replaces the frame-ingest kernel. */
 enum drnmi_algo { DRNMI_ALGO_IGEMM = 0, DRNMI_ALGO_PATCH = 1 };
 
+/* drnmi_conv_args.tile of a DRNMI_ALGO_IGEMM launch, in the order of drnmi_conv_tile_name.
+ * DRNMI_TILE_AUTO picks the bf16 LDS-DMA kernel (DMA128 / DMA256 / DMA64K32 / DMA64: 128 / 256 /
+ * 64 / 64 output channels x 256 pixels, 64-channel K steps but DMA64K32's 32; cin >= 32, ks 1 or
+ * 3) when it applies, else a register-staged tile IGEMM_* by cout.  Whole 256-pixel output rows
+ * (3x3, stride 1, cin % 128 == 0) route to the strip tiles: STAG (256 / 128 channels, 8 waves
+ * with staggered SIMD partners), W1 (the same tile as 4 waves of 128 x 128, one per SIMD; auto at
+ * cin >= 512 without residual), W1H (128 x 128 tiles, two workgroups per CU; auto at cout 128) --
+ * all with the same K order, so bit-identical.  int8 (dtype DRNMI_I8) takes STAG / W1 / W1H as its
+ * int8 forms (auto: W1H at cin, cout <= 256, else STAG) and ignores the other ids.  The forced ids
+ * exist for the bit-identity tests and A/B runs.  DRNMI_F32X3 (conv_x6) reads tile >= 0 in its own
+ * encoding instead: tile % 6 is the conv_x6 variant and, when tile >= 6, tile / 6 the split-K
+ * count (only with a workspace). */
+enum drnmi_tile {
+  DRNMI_TILE_AUTO = -1,
+  DRNMI_TILE_IGEMM_128X128 = 0, DRNMI_TILE_IGEMM_128X64 = 1, DRNMI_TILE_IGEMM_256X32 = 2, DRNMI_TILE_IGEMM_256X16 = 3,
+  DRNMI_TILE_DMA128 = 4, DRNMI_TILE_DMA256 = 5, DRNMI_TILE_DMA64K32 = 6, DRNMI_TILE_DMA64 = 7,
+  DRNMI_TILE_DMA256K32 = 8, DRNMI_TILE_DMA128K32 = 9,
+  DRNMI_TILE_DMA128P = 10, DRNMI_TILE_DMA256P = 11, DRNMI_TILE_DMA64K32P = 12, DRNMI_TILE_DMA64P = 13,
+  DRNMI_TILE_DMA256K32P = 14, DRNMI_TILE_DMA128K32P = 15,      /* the same six, persistent */
+  DRNMI_TILE_PP256 = 16,           /* ping-pong 4-phase schedule */
+  DRNMI_TILE_HALO = 17,            /* conv_halo: 4 x 64 pixel blocks, cin / cout 64 or 128 */
+  DRNMI_TILE_STRIP = 18,           /* strip-staged B (3x3, wo % 256 == 0) */
+  DRNMI_TILE_STAG = 19,
+  DRNMI_TILE_S2ROW = 20,           /* stride-2 3x3 32 -> 64 / 64 -> 128 row walk */
+  DRNMI_TILE_S1X2ROW = 21,         /* stride-1 3x3 64 -> 64 + 1x1 stride-2 downsample from 32 channels */
+  DRNMI_TILE_W1 = 22,
+  DRNMI_TILE_W1H = 23,
+  DRNMI_TILE_COUNT = 24            /* drnmi_conv_num_tiles() */
+};
+
 int drnmi_conv2d_bn_act(const drnmi_conv_args* args, void* stream);
+
+/* The status drnmi_conv2d_bn_act would refuse these arguments with (DRNMI_EINVAL / DRNMI_ENOTSUP),
+ * or 0 when it would launch; no launch is made and x, wgt, shift, y are not looked at.
+ * drnmi_conv_kernel_name(args) is NULL exactly when this is not 0. */
+int drnmi_conv_status(const drnmi_conv_args* args);
 
 /* Rows of the args->stats partials this launch writes (4 per 256-pixel tile), or 0 when it
  * cannot produce them (not conv_x6, or a split-K plan: compute the statistics from y). */
@@ -257,7 +283,8 @@ int drnmi_absmax(const void* x, int32_t dtype, int64_t n, float* out, void* stre
 int drnmi_abs_histogram(const void* x, int32_t dtype, int64_t n, int64_t* hist, void* stream);
 
 /* Name of the kernel (template instance) drnmi_conv2d_bn_act would launch for these
- * arguments, e.g. "conv_big_kernel<3, 128, 2, 2>"; NULL if none.  No launch, no GPU needed.
+ * arguments, e.g. "conv_big_kernel<3, 128, 2, 2>"; NULL if it would refuse them (the same
+ * decision: drnmi_conv_status; x, wgt, shift, y may be NULL).  No launch, no GPU needed.
  * (Used by bench.py to attribute timed launches to kernels as rocprofv3 names them.) */
 const char* drnmi_conv_kernel_name(const drnmi_conv_args* args);
 
@@ -354,7 +381,8 @@ int drnmi_up8_labels_nhwc_wide_stats(const float* logits, int32_t cs, const floa
  * seg_scale[k] + seg_shift[k] (drnmi_up8_labels_seg2_i8). */
 int drnmi_conv_stag_seg(const drnmi_conv_args* a, const void* seg_w, int32_t seg_k_pad, int32_t seg_rows,
                         void* partials, void* stream);
-/* The kernel drnmi_conv_stag_seg launches for these arguments (as rocprofv3 names it), or NULL. */
+/* The kernel drnmi_conv_stag_seg launches for these arguments (as rocprofv3 names it), or NULL
+ * where its checks of the conv arguments refuse them. */
 const char* drnmi_conv_stag_seg_kernel_name(const drnmi_conv_args* a);
 
 /* Labels from those partials: logit[k] = (bias[k] + partial_0[k]) + partial_1[k] (bias: >= cs

@@ -1,0 +1,67 @@
+"""The conv routing table is pinned against the commit before the routing refactor: for every row
+of tests/route_grid.py, tests/golden/conv_routes.npz (tests/golden/make_route_golden.py) holds the
+kernel name and the launch entry point's status that commit gave.  The name and status queries
+must reproduce them: the status exactly, the name wherever the launch was accepted, and no name
+wherever it was refused.  No launch entry point is called."""
+import ctypes
+import os
+
+import numpy as np
+import pytest
+
+import route_grid
+from drnmi import _lib
+
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "conv_routes.npz")
+
+
+@pytest.fixture(scope="module")
+def table():
+    args, entry = route_grid.grid()
+    z = np.load(GOLDEN, allow_pickle=False)
+    return args, entry, [str(n) for n in z["names"]], z["name_index"], z["status"], str(z["sha256"])
+
+
+def _query(lib, args, entry):
+    """(name or None, status or None) per row; the seg-fused entry has no status query."""
+    base, size = args.ctypes.data, args.dtype.itemsize
+    names, status = [], []
+    for i in range(len(args)):
+        a = ctypes.cast(base + i * size, ctypes.POINTER(_lib.ConvArgs))
+        if entry[i]:
+            name, st = lib.drnmi_conv_stag_seg_kernel_name(a), None
+        else:
+            name, st = lib.drnmi_conv_kernel_name(a), lib.drnmi_conv_status(a)
+        names.append(None if name is None else name.decode())
+        status.append(st)
+    return names, status
+
+
+def test_grid_is_the_recorded_one(table):
+    args, entry, names, index, status, sha = table
+    assert len(args) <= 150000
+    assert route_grid.digest(args, entry) == sha
+    assert len(index) == len(status) == len(args)
+    # every kernel name of the table is reached by a row that launches
+    assert {names[i] for i in np.unique(index[status == 0])} == set(names[1:])
+
+
+def test_routes_match_the_parent_commit(table):
+    args, entry, names, index, status, _ = table
+    lib = _lib.load()
+    got_names, got_status = _query(lib, args, entry)
+    probes = args.copy()                     # the engine's probes leave the data pointers NULL
+    for f in route_grid.DATA_POINTERS:
+        probes[f] = 0
+    probe_names, probe_status = _query(lib, probes, entry)
+    bad = []
+    for i in range(len(args)):
+        want_name = names[index[i]] if status[i] == 0 else None
+        ok = got_names[i] == want_name and probe_names[i] == want_name
+        if not entry[i]:
+            ok = ok and got_status[i] == status[i] and probe_status[i] == status[i] and \
+                (got_names[i] is None) == (got_status[i] < 0)
+        if not ok:
+            bad.append((i, int(entry[i]), want_name, int(status[i]), got_names[i], got_status[i], probe_names[i],
+                        probe_status[i]))
+    assert not bad, f"{len(bad)} of {len(args)} rows differ; first: {bad[:5]}"

@@ -732,11 +732,16 @@ def _x6_case(case, split, tile=-1, check=True, stats=False):
     a.ks, a.stride, a.pad, a.dil = ks, s, pad, dil
     a.k, a.k_pad = k, wpk.shape[1]
     a.relu, a.dtype, a.out_dtype, a.tile, a.algo = 1, _lib.DRNMI_F32X3, _lib.DRNMI_F32, tile, _lib.ALGO_IGEMM
-    name = _lib.load().drnmi_conv_kernel_name(ctypes.byref(a)).decode()
+    name = _lib.load().drnmi_conv_kernel_name(ctypes.byref(a))
+    if name is None:                                  # a forced tile wider than the packed rows: refused, so unnamed
+        bco = {0: 256, 1: 128, 2: 64, 3: 128, 4: 128, 5: 64}[tile % 6]
+        assert tile >= 0 and (cout + bco - 1) // bco * bco > wpk.shape[0]
+        assert _lib.load().drnmi_conv_status(ctypes.byref(a)) == -1
+        return None
+    name = name.decode()
     assert name.startswith("conv_x6_kernel")
     bco = int(name.split("<")[1].split(",")[1]) * int(name.split(",")[2])
-    if (cout + bco - 1) // bco * bco > wpk.shape[0]:
-        return None                                   # a forced tile wider than the packed rows
+    assert (cout + bco - 1) // bco * bco <= wpk.shape[0]
     keep = {"y": y}
     if split:
         nb = _lib.load().drnmi_conv_workspace_bytes(ctypes.byref(a))

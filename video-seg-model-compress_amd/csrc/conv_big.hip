@@ -646,105 +646,20 @@ hipError_t launch_big(const drnmi_conv_args& p, hipStream_t s) {
 
 constexpr int kStripLds = 2 * 256 * 128 + 2 * kStripBytes;   // 2 A stages + 2 strips (130 KB)
 
+// conv_strip_kernel / conv_i8_strip_kernel
+template <auto KERNEL>
 hipError_t launch_strip(const drnmi_conv_args& p, hipStream_t s) {
   static bool attr_set = false;
   if (!attr_set) {
-    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_strip_kernel),
+    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(KERNEL),
                                              hipFuncAttributeMaxDynamicSharedMemorySize, kStripLds);
     if (e != hipSuccess) return e;
     attr_set = true;
   }
   const int64_t M = static_cast<int64_t>(p.n) * p.ho * p.wo;
   const int64_t blocks = (M / kBPX) * ((p.cout + 255) / 256);
-  hipLaunchKernelGGL(conv_strip_kernel, dim3(static_cast<unsigned>(blocks)), dim3(512), kStripLds, s, p);
+  hipLaunchKernelGGL(KERNEL, dim3(static_cast<unsigned>(blocks)), dim3(512), kStripLds, s, p);
   return hipGetLastError();
-}
-
-// Routing is fixed (no environment switches): auto-picked strip launches run conv_w1_kernel (one
-// wave per SIMD, 128 x 128 per wave, bit-identical) on the long-K residual-free launches (w1_auto),
-// else conv_stag_kernel when cin % 128 == 0 (5-6 % faster than the strip tile, bit-identical),
-// else conv_strip_kernel; the other tiles stay reachable through an explicit drnmi_conv_args.tile
-// for the bit-identity tests.
-
-// a 256-pixel tile is a run of one output row, the strip of 256 + 2 dil rows fits its buffer
-bool strip_ok(const drnmi_conv_args& p) {
-  return p.ks == 3 && p.stride == 1 && p.pad == p.dil && p.dil >= 1 && p.dil <= 4 && p.wo % kBPX == 0 &&
-         p.x2 == nullptr && p.unit_mask == nullptr && p.cin % 64 == 0 && p.k == 9 * p.cin;
-}
-
-// the staggered strip tile (conv_stag.hip): strip geometry, cin % 128 == 0 (an even number of
-// 3-step tap groups), optionally with the fused downsample (x2 validated by x2_ok)
-bool stag_ok(const drnmi_conv_args& p) {
-  const int tco = p.cout <= 128 ? 128 : 256;          // conv_stag128_* / conv_stag_* tile
-  return p.ks == 3 && p.stride == 1 && p.pad == p.dil && p.dil >= 1 && p.dil <= 4 && p.wo % kBPX == 0 &&
-         p.unit_mask == nullptr && p.cin % 128 == 0 && (p.cout + tco - 1) / tco * tco <= p.cout_pad &&
-         (p.x2 == nullptr ? p.k == 9 * p.cin : (p.cin2 % 64 == 0 && p.k == 9 * p.cin + p.cin2));
-}
-
-// 128-channel convs (D-22 layer4) go to the staggered 128-channel tile instead of the halo
-// kernel when both apply (88-96 vs 102-107 us, profiles/r4c_stag128_vs_halo)
-bool halo_preferred(const drnmi_conv_args& p) { return !(big_conv_supported(p) && stag_ok(p)); }
-
-struct Variant {
-  int bco, bk;
-  const char* name3;
-  const char* name1;
-};
-
-// tile ids 4 + v in drnmi_conv_args.tile
-constexpr Variant kVariants[] = {
-    {128, 64, "conv_big_kernel<3, 128, 1, 3, 64, false, 4, false, false>", "conv_big_kernel<1, 128, 1, 3, 64, false, 4, false, false>"},
-    {256, 64, "conv_big_kernel<3, 128, 2, 2, 64, false, 4, false, false>", "conv_big_kernel<1, 128, 2, 2, 64, false, 4, false, false>"},
-    {64, 32, "conv_big_kernel<3, 64, 1, 4, 32, false, 4, false, false>", "conv_big_kernel<1, 64, 1, 4, 32, false, 4, false, false>"},
-    {64, 64, "conv_big_kernel<3, 64, 1, 2, 64, false, 4, false, false>", "conv_big_kernel<1, 64, 1, 2, 64, false, 4, false, false>"},
-    {256, 32, "conv_big_kernel<3, 128, 2, 4, 32, false, 4, false, false>", "conv_big_kernel<1, 128, 2, 4, 32, false, 4, false, false>"},
-    {128, 32, "conv_big_kernel<3, 128, 1, 4, 32, false, 4, false, false>", "conv_big_kernel<1, 128, 1, 4, 32, false, 4, false, false>"},
-    {128, 64, "conv_big_kernel<3, 128, 1, 3, 64, true, 4, false, false>", "conv_big_kernel<1, 128, 1, 3, 64, true, 4, false, false>"},
-    {256, 64, "conv_big_kernel<3, 128, 2, 2, 64, true, 4, false, false>", "conv_big_kernel<1, 128, 2, 2, 64, true, 4, false, false>"},
-    {64, 32, "conv_big_kernel<3, 64, 1, 4, 32, true, 4, false, false>", "conv_big_kernel<1, 64, 1, 4, 32, true, 4, false, false>"},
-    {64, 64, "conv_big_kernel<3, 64, 1, 2, 64, true, 4, false, false>", "conv_big_kernel<1, 64, 1, 2, 64, true, 4, false, false>"},
-    {256, 32, "conv_big_kernel<3, 128, 2, 4, 32, true, 4, false, false>", "conv_big_kernel<1, 128, 2, 4, 32, true, 4, false, false>"},
-    {128, 32, "conv_big_kernel<3, 128, 1, 4, 32, true, 4, false, false>", "conv_big_kernel<1, 128, 1, 4, 32, true, 4, false, false>"},
-    {256, 64, "conv_pp_kernel<3>", "conv_pp_kernel<1>"},
-};
-constexpr int kPingPong = 12;
-constexpr int kHalo = 13;   // conv_halo.hip (tile id 17)
-constexpr int kStrip = 14;  // conv_strip_kernel (tile id 18); auto routes variant 1 there when strip_ok
-constexpr int kStag = 15;   // conv_stag_kernel (tile id 19): the strip tile with staggered SIMD partners
-constexpr int kS2Row = 16;  // conv_s2row_kernel (tile id 20): stride-2 3x3 32 -> 64 / 64 -> 128, row walk
-constexpr int kS1X2Row = 17;  // conv_s1x2row_kernel (tile id 21): stride-1 3x3 64 -> 64 + 1x1 s2 downsample 32 -> 64
-constexpr int kW1 = 18;      // conv_w1_kernel (tile id 22): the stag256 tile as 4 waves of 128 x 128, one per SIMD
-constexpr int kW1H = 19;     // conv_w1h_kernel (tile id 23): 128 x 128 tiles of 4 waves of 64 x 64, two per CU
-constexpr int kNumVariants = sizeof(kVariants) / sizeof(kVariants[0]);
-
-// conv_w1 (conv_w1.hip): the staggered tile's shapes (+ the fused downsample: conv_w1_x2), 256-channel blocks
-bool w1_ok(const drnmi_conv_args& p) {
-  return stag_ok(p) && p.cout % 256 == 0 && p.scale == nullptr && p.out_dtype == DRNMI_BF16 &&
-         p.y_sc == 1 && p.y_sp == p.cout && p.y_sn == static_cast<int64_t>(p.ho) * p.wo * p.cout;
-}
-// auto-routed where it measured no slower inside the network (same-box interleaved bench A/B,
-// profiles/r10m_w1_ab): the long-K residual-free launches (D-22 layer6.1 conv1, layer7).  At
-// cin 128 / 256 (18 / 36 K steps) and with a residual its per-tile prologue and epilogue, issued
-// by 4 waves instead of 8, cost more than the loop saves (layer5.0 conv1 145 vs 130 us)
-bool w1_auto(const drnmi_conv_args& p) { return w1_ok(p) && p.x2 == nullptr && p.cin >= 512 && p.res == nullptr; }
-// conv_w1h: the same shapes at 128-channel blocks (a 128-pixel run: wo % 128 == 0 follows from stag_ok)
-bool w1h_ok(const drnmi_conv_args& p) {
-  return stag_ok(p) && p.cout % 128 == 0 && p.scale == nullptr && p.out_dtype == DRNMI_BF16 &&
-         p.y_sc == 1 && p.y_sp == p.cout && p.y_sn == static_cast<int64_t>(p.ho) * p.wo * p.cout;
-}
-bool w1h_auto(const drnmi_conv_args& p) { return w1h_ok(p) && p.cout <= 128; }
-
-template <int KS, bool PERSIST>
-hipError_t launch_base(const drnmi_conv_args& p, int base, hipStream_t s) {
-  switch (base) {
-    case 0: return launch_big<KS, 128, 1, 3, 64, PERSIST>(p, s);   // 128 x 256 tile, 4 waves, 3 x 48 KB
-    case 1: return launch_big<KS, 128, 2, 2, 64, PERSIST>(p, s);   // 256 x 256 tile, 8 waves, 2 x 64 KB
-    case 2: return launch_big<KS, 64, 1, 4, 32, PERSIST>(p, s);    //  64 x 256 tile, 4 waves, 4 x 20 KB
-    case 3: return launch_big<KS, 64, 1, 2, 64, PERSIST>(p, s);    //  64 x 256 tile, 4 waves, 2 x 40 KB
-    case 4: return launch_big<KS, 128, 2, 4, 32, PERSIST>(p, s);   // 256 x 256 tile, 8 waves, 4 x 32 KB
-    case 5: return launch_big<KS, 128, 1, 4, 32, PERSIST>(p, s);   // 128 x 256 tile, 4 waves, 4 x 24 KB
-    default: return hipErrorInvalidValue;
-  }
 }
 
 template <int KS, int WCO, int WC, int NST, int BK, bool OCC2 = false>
@@ -770,80 +685,9 @@ hipError_t launch_i8(const drnmi_conv_args& p, hipStream_t s) {
   return hipGetLastError();
 }
 
-// int8 variants: 0 = 256 x 256 tile / 128-B rows, 1 = 128 x 256 / 128-B, 2 = 256 x 256 / 64-B,
-// 3 = 128 x 256 / 64-B (K steps of 128 or 64 int8 channels)
-struct I8Variant {
-  int bco;
-  const char* name3;
-  const char* name1;
-};
-constexpr I8Variant kI8Variants[] = {
-    {256, "conv_i8_kernel<3, 128, 2, 2, 128>", "conv_i8_kernel<1, 128, 2, 2, 128>"},
-    {128, "conv_i8_kernel<3, 128, 1, 3, 128>", "conv_i8_kernel<1, 128, 1, 3, 128>"},
-    {256, "conv_i8_kernel<3, 128, 2, 4, 64>", "conv_i8_kernel<1, 128, 2, 4, 64>"},
-    {128, "conv_i8_kernel<3, 128, 1, 4, 64>", "conv_i8_kernel<1, 128, 1, 4, 64>"},
-    {128, "conv_i8_occ2_kernel<3, 128, 1, 2, 64>", "conv_i8_occ2_kernel<1, 128, 1, 2, 64>"},
-};
-constexpr int kI8Occ2 = 4;   // 128 x 256 / 64-B rows, 2 stages, two workgroups per CU
-
-int i8_variant(const drnmi_conv_args& p) {
-  const int wide = p.cout % 256 == 0 ? 0 : 1;
-  // 1x1: the two-workgroups-per-CU tile (71.6-73.5 vs 86.7-86.9 us for layer5.0 / layer6.0's
-  // downsample, 65.6-67.0 for the seg conv: profiles/r6_int8_fusions/occ2_ab.txt)
-  return p.ks == 1 && p.cout_pad % kI8Variants[kI8Occ2].bco == 0 ? kI8Occ2 : (p.cin >= 128 ? 0 : 2) + wide;
-}
-
-template <int KS>
-hipError_t launch_i8_variant(const drnmi_conv_args& p, int v, hipStream_t s) {
-  switch (v) {
-    case 0: return launch_i8<KS, 128, 2, 2, 128>(p, s);   // 2 x 64 KB
-    case 1: return launch_i8<KS, 128, 1, 3, 128>(p, s);   // 3 x 48 KB
-    case 2: return launch_i8<KS, 128, 2, 4, 64>(p, s);    // 4 x 32 KB
-    case 3: return launch_i8<KS, 128, 1, 4, 64>(p, s);    // 4 x 24 KB
-    case kI8Occ2: return launch_i8<KS, 128, 1, 2, 64, true>(p, s);   // 2 x 24 KB, 2 WGs / CU
-    default: return hipErrorInvalidValue;
-  }
-}
-
-
-template <int KS>
-hipError_t launch_sparse(const drnmi_conv_args& p, int base, hipStream_t s) {
-  switch (base) {
-    case 0: return launch_big<KS, 128, 1, 3, 64, false, 4, true>(p, s);
-    case 1: return launch_big<KS, 128, 2, 2, 64, false, 4, true>(p, s);
-    case 4: return launch_big<KS, 128, 2, 4, 32, false, 4, true>(p, s);
-    case 5: return launch_big<KS, 128, 1, 4, 32, false, 4, true>(p, s);
-    default: return hipErrorInvalidValue;
-  }
-}
-
-const char* sparse_name(int ks, int base) {
-  static const char* n3[6] = {"conv_big_kernel<3, 128, 1, 3, 64, false, 4, true, false>",
-                              "conv_big_kernel<3, 128, 2, 2, 64, false, 4, true, false>", nullptr, nullptr,
-                              "conv_big_kernel<3, 128, 2, 4, 32, false, 4, true, false>",
-                              "conv_big_kernel<3, 128, 1, 4, 32, false, 4, true, false>"};
-  static const char* n1[6] = {"conv_big_kernel<1, 128, 1, 3, 64, false, 4, true, false>",
-                              "conv_big_kernel<1, 128, 2, 2, 64, false, 4, true, false>", nullptr, nullptr,
-                              "conv_big_kernel<1, 128, 2, 4, 32, false, 4, true, false>",
-                              "conv_big_kernel<1, 128, 1, 4, 32, false, 4, true, false>"};
-  return ks == 3 ? n3[base] : n1[base];
-}
-
-int auto_variant(const drnmi_conv_args& p) {
-  if (p.cin < 64) return p.cout % 256 == 0 ? 4 : p.cout % 128 == 0 ? 5 : 2;   // K steps of 32
-  // cout <= 32 (the seg 1x1) also takes the 64-wide BK-32 tile: 57 vs 66 us on the D-22 seg conv
-  // at batch 8 (scripts/conv_micro.py) — two workgroups fit per CU where the 32-wide 3 x 36 KB ring fits one
-  // 64 -> 128 (D-22 layer4.0 conv1 / downsample, stride 2): the 64-wide BK-32 tile too, two
-  // workgroups per CU against one for the 128 x 256 x 3-stage ring: 98 vs 116 us (3x3), 50 vs
-  // 75 us (1x1) at batch 8 (scripts/conv_micro.py); the fused-x2 instantiations are bases 0/1
-  if (p.cin <= 64 && p.cout % 256 != 0 && p.x2 == nullptr) {
-    // cin == 64 3x3 (D-22 layer4.0 conv1, stride 2): the 64-wide tile with 64-channel K steps on a
-    // 2 x 40 KB ring halves the K steps of the BK-32 tile at the same DMA bytes: 93.6 vs 102 us
-    // at batch 8 (profiles/r3k_tile_64w_bk64_ab.txt)
-    if (p.cin == 64 && p.ks == 3) return 3;
-    return 2;
-  }
-  return p.cout % 256 == 0 ? 1 : p.cout % 128 == 0 ? 0 : 2;
+template <int KS, int WCO, int WC, int NST, int BK>
+hipError_t launch_i8_occ2(const drnmi_conv_args& p, hipStream_t s) {
+  return launch_i8<KS, WCO, WC, NST, BK, true>(p, s);
 }
 
 // one lane per 16 x 32 unit; lanes 0-31 / 32-63 of a wave cover the 32 units of two mask words
@@ -878,6 +722,78 @@ unit_mask_kernel(const T* __restrict__ w, int rows_pad, int k_pad, int wpr, uint
 
 }  // namespace
 
+// conv_big_kernel<KS, WCO, WC, NST, BK, PERSIST, 4, SPARSE, X2>, rows [ks == 3]
+#define BIG_ROW(KS, WCO, WC, NST, BK, PERSIST, SPARSE, X2) \
+  DRNMI_KERNEL_ROW(conv_big_kernel, launch_big, KS, WCO, WC, NST, BK, PERSIST, 4, SPARSE, X2)
+#define BIG_ROWS(...) {BIG_ROW(1, __VA_ARGS__), BIG_ROW(3, __VA_ARGS__)}
+#define BIG_NONE {kNoKernel, kNoKernel}
+#define BIG_DENSE(WCO, WC, NST, BK, PERSIST) WCO * WC, BK, BIG_ROWS(WCO, WC, NST, BK, PERSIST, false, false)
+#define BIG_SPARSE(WCO, WC, NST, BK) BIG_ROWS(WCO, WC, NST, BK, false, true, false)
+#define BIG_X2(WCO, WC, NST, BK) BIG_ROWS(WCO, WC, NST, BK, false, false, true)
+const BigVariant& big_variant(int v) {
+  static const BigVariant k[kNumBigVariants] = {
+    {BIG_DENSE(128, 1, 3, 64, false), BIG_SPARSE(128, 1, 3, 64), BIG_X2(128, 1, 3, 64)},   // 128 x 256 tile, 4 waves, 3 x 48 KB
+    {BIG_DENSE(128, 2, 2, 64, false), BIG_SPARSE(128, 2, 2, 64), BIG_X2(128, 2, 2, 64)},   // 256 x 256 tile, 8 waves, 2 x 64 KB
+    {BIG_DENSE(64, 1, 4, 32, false), BIG_NONE, BIG_NONE},                                  //  64 x 256 tile, 4 waves, 4 x 20 KB
+    {BIG_DENSE(64, 1, 2, 64, false), BIG_NONE, BIG_NONE},                                  //  64 x 256 tile, 4 waves, 2 x 40 KB
+    {BIG_DENSE(128, 2, 4, 32, false), BIG_SPARSE(128, 2, 4, 32), BIG_NONE},                // 256 x 256 tile, 8 waves, 4 x 32 KB
+    {BIG_DENSE(128, 1, 4, 32, false), BIG_SPARSE(128, 1, 4, 32), BIG_NONE},                // 128 x 256 tile, 4 waves, 4 x 24 KB
+    {BIG_DENSE(128, 1, 3, 64, true), BIG_NONE, BIG_NONE},                                  // the same six, persistent
+    {BIG_DENSE(128, 2, 2, 64, true), BIG_NONE, BIG_NONE},
+    {BIG_DENSE(64, 1, 4, 32, true), BIG_NONE, BIG_NONE},
+    {BIG_DENSE(64, 1, 2, 64, true), BIG_NONE, BIG_NONE},
+    {BIG_DENSE(128, 2, 4, 32, true), BIG_NONE, BIG_NONE},
+    {BIG_DENSE(128, 1, 4, 32, true), BIG_NONE, BIG_NONE},
+    {256, 64, {DRNMI_KERNEL_ROW(conv_pp_kernel, launch_pp, 1), DRNMI_KERNEL_ROW(conv_pp_kernel, launch_pp, 3)}, BIG_NONE,
+     BIG_NONE},
+  };
+  return k[v];
+}
+
+const ConvKernel* strip_kernel(bool i8) {
+  static const ConvKernel k[2] = {DRNMI_KERNEL_ROW0(conv_strip_kernel, launch_strip),
+                                  DRNMI_KERNEL_ROW0(conv_i8_strip_kernel, launch_strip)};
+  return &k[i8];
+}
+
+#define I8_ROWS(KERNEL, LAUNCH, ...) {DRNMI_KERNEL_ROW(KERNEL, LAUNCH, 1, __VA_ARGS__), DRNMI_KERNEL_ROW(KERNEL, LAUNCH, 3, __VA_ARGS__)}
+const I8Variant& i8_variant_row(int v) {
+  static const I8Variant k[5] = {
+    {256, I8_ROWS(conv_i8_kernel, launch_i8, 128, 2, 2, 128)},             // 2 x 64 KB
+    {128, I8_ROWS(conv_i8_kernel, launch_i8, 128, 1, 3, 128)},             // 3 x 48 KB
+    {256, I8_ROWS(conv_i8_kernel, launch_i8, 128, 2, 4, 64)},              // 4 x 32 KB
+    {128, I8_ROWS(conv_i8_kernel, launch_i8, 128, 1, 4, 64)},              // 4 x 24 KB
+    {128, I8_ROWS(conv_i8_occ2_kernel, launch_i8_occ2, 128, 1, 2, 64)},    // 2 x 24 KB, 2 WGs / CU
+  };
+  return k[v];
+}
+
+// a 256-pixel tile is a run of one output row, the strip of 256 + 2 dil rows fits its buffer
+bool strip_ok(const drnmi_conv_args& p) {
+  return p.ks == 3 && p.stride == 1 && p.pad == p.dil && p.dil >= 1 && p.dil <= 4 && p.wo % kBPX == 0 &&
+         p.x2 == nullptr && p.unit_mask == nullptr && p.cin % 64 == 0 && p.k == 9 * p.cin;
+}
+
+// the staggered strip tile (conv_stag.hip): strip geometry, cin % 128 == 0 (an even number of
+// 3-step tap groups), optionally with the fused downsample (x2 validated by x2_ok)
+bool stag_ok(const drnmi_conv_args& p) {
+  const int tco = p.cout <= 128 ? 128 : 256;          // conv_stag128_* / conv_stag_* tile
+  return p.ks == 3 && p.stride == 1 && p.pad == p.dil && p.dil >= 1 && p.dil <= 4 && p.wo % kBPX == 0 &&
+         p.unit_mask == nullptr && p.cin % 128 == 0 && (p.cout + tco - 1) / tco * tco <= p.cout_pad &&
+         (p.x2 == nullptr ? p.k == 9 * p.cin : (p.cin2 % 64 == 0 && p.k == 9 * p.cin + p.cin2));
+}
+
+// conv_w1 (conv_w1.hip): the staggered tile's shapes (+ the fused downsample: conv_w1_x2), 256-channel blocks
+bool w1_ok(const drnmi_conv_args& p) {
+  return stag_ok(p) && p.cout % 256 == 0 && p.scale == nullptr && p.out_dtype == DRNMI_BF16 &&
+         p.y_sc == 1 && p.y_sp == p.cout && p.y_sn == static_cast<int64_t>(p.ho) * p.wo * p.cout;
+}
+// conv_w1h: the same shapes at 128-channel blocks (a 128-pixel run: wo % 128 == 0 follows from stag_ok)
+bool w1h_ok(const drnmi_conv_args& p) {
+  return stag_ok(p) && p.cout % 128 == 0 && p.scale == nullptr && p.out_dtype == DRNMI_BF16 &&
+         p.y_sc == 1 && p.y_sp == p.cout && p.y_sn == static_cast<int64_t>(p.ho) * p.wo * p.cout;
+}
+
 bool i8_conv_supported(const drnmi_conv_args& p) {
   return p.dtype == DRNMI_I8 && p.scale != nullptr && p.cin >= 64 && (p.cin & (p.cin - 1)) == 0 &&
          p.cout_pad % 128 == 0 && (p.ks == 1 || p.ks == 3) && p.k == p.ks * p.ks * p.cin && p.k_pad == p.k &&
@@ -885,22 +801,9 @@ bool i8_conv_supported(const drnmi_conv_args& p) {
          (p.out_dtype == DRNMI_F32 || p.out_dtype == DRNMI_BF16 || p.out_dtype == DRNMI_I8);
 }
 
+// int8 strip-staged B: the 256 x 256 tile with 128-B rows (i8_variant_row(0): cin >= 128, cout % 256 == 0)
 bool i8_strip_ok(const drnmi_conv_args& p) {
-  return i8_variant(p) == 0 && p.cin % 128 == 0 && strip_ok(p);
-}
-
-hipError_t launch_i8_strip(const drnmi_conv_args& p, hipStream_t s) {
-  static bool attr_set = false;
-  if (!attr_set) {
-    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_i8_strip_kernel),
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, kStripLds);
-    if (e != hipSuccess) return e;
-    attr_set = true;
-  }
-  const int64_t M = static_cast<int64_t>(p.n) * p.ho * p.wo;
-  const int64_t blocks = (M / kBPX) * ((p.cout + 255) / 256);
-  hipLaunchKernelGGL(conv_i8_strip_kernel, dim3(static_cast<unsigned>(blocks)), dim3(512), kStripLds, s, p);
-  return hipGetLastError();
+  return p.cout % 256 == 0 && p.cin % 128 == 0 && strip_ok(p);
 }
 
 // int8 staggered strip tile (conv_stag.hip): 128-channel K steps, so cin % 256 == 0 gives the
@@ -910,56 +813,16 @@ bool i8_stag_ok(const drnmi_conv_args& p) {
 }
 
 // int8 conv_w1 (conv_w1_i8_kernel): the staggered int8 tile's shapes at 256-channel blocks with a
-// dense int8 NHWC output (its 16-B epilogue).  Not auto-routed: on the long-K residual-free int8
-// launches it measured no faster inside the network (profiles/r11_w1i8: layer6.1 conv1 460 vs 450
-// us); the seg-fused layer8 launch (drnmi_conv_stag_seg) takes its SEGF form (431 vs 456 us)
+// dense int8 NHWC output (its 16-B epilogue)
 bool i8_w1_ok(const drnmi_conv_args& p) {
   return i8_stag_ok(p) && p.cout % 256 == 0 && p.out_dtype == DRNMI_I8 && p.y_sc == 1 && p.y_sp == p.cout &&
          p.y_sn == static_cast<int64_t>(p.ho) * p.wo * p.cout;
 }
 // int8 conv_w1h (conv_w1h_i8_kernel: 128 x 128 tiles, two workgroups per CU, odd tap-group counts
-// too): whole-row strip geometry, cin % 128 == 0, 128-channel blocks, dense int8 NHWC output;
-// auto-routed at cin, cout <= 256 (D-22 layer4.1, layer5 in int8 nets: profiles/r11_int8_layer4)
+// too): whole-row strip geometry, cin % 128 == 0, 128-channel blocks, dense int8 NHWC output
 bool i8_w1h_ok(const drnmi_conv_args& p) {
   return strip_ok(p) && p.cin % 128 == 0 && p.cout % 128 == 0 && p.out_dtype == DRNMI_I8 && p.y_sc == 1 &&
          p.y_sp == p.cout && p.y_sn == static_cast<int64_t>(p.ho) * p.wo * p.cout;
-}
-bool i8_w1h_pick(const drnmi_conv_args& p) {
-  return p.tile == 4 + kW1H || (p.tile < 0 && i8_w1h_ok(p) && (p.cout <= 128 || p.cin == 128 || (p.cin <= 256 && p.cout <= 256)));
-}
-// tile id 22 forces the one-wave-per-SIMD int8 tile (the bit-identity tests); else the staggered one
-bool i8_w1_pick(const drnmi_conv_args& p) { return p.tile == 4 + kW1; }
-
-int i8_conv_dispatch(const drnmi_conv_args& p, hipStream_t s) {
-  if (!i8_conv_supported(p)) return DRNMI_ENOTSUP;
-  const int v = i8_variant(p);
-  if ((p.cout + kI8Variants[v].bco - 1) / kI8Variants[v].bco * kI8Variants[v].bco > p.cout_pad) return DRNMI_EINVAL;
-  if (p.ks == 3 && i8_w1h_pick(p)) {
-    if (!i8_w1h_ok(p)) return DRNMI_ENOTSUP;
-    const hipError_t e = launch_w1h(p, s);
-    return e == hipErrorInvalidValue ? DRNMI_ENOTSUP : static_cast<int>(e);
-  }
-  if (p.ks == 3 && i8_stag_ok(p)) {
-    const bool w1 = i8_w1_pick(p);
-    if (w1 && !i8_w1_ok(p)) return DRNMI_ENOTSUP;
-    const hipError_t e = w1 ? launch_w1(p, s) : launch_stag(p, s);
-    return e == hipErrorInvalidValue ? DRNMI_ENOTSUP : static_cast<int>(e);
-  }
-  if (p.ks == 3 && i8_strip_ok(p)) {
-    const hipError_t e = launch_i8_strip(p, s);
-    return e == hipErrorInvalidValue ? DRNMI_ENOTSUP : static_cast<int>(e);
-  }
-  const hipError_t e = p.ks == 3 ? launch_i8_variant<3>(p, v, s) : launch_i8_variant<1>(p, v, s);
-  return e == hipErrorInvalidValue ? DRNMI_ENOTSUP : static_cast<int>(e);
-}
-
-const char* i8_conv_name(const drnmi_conv_args& p) {
-  if (!i8_conv_supported(p)) return nullptr;
-  const int v = i8_variant(p);
-  if (p.ks == 3 && i8_w1h_pick(p)) return i8_w1h_ok(p) ? "conv_w1h_i8_kernel" : nullptr;
-  if (p.ks == 3 && i8_stag_ok(p)) return !i8_w1_pick(p) ? "conv_i8_stag_kernel" : i8_w1_ok(p) ? "conv_w1_i8_kernel" : nullptr;
-  if (p.ks == 3 && i8_strip_ok(p)) return "conv_i8_strip_kernel";
-  return p.ks == 3 ? kI8Variants[v].name3 : kI8Variants[v].name1;
 }
 
 // second input (fused 1x1 downsample): bf16 NHWC x2 [n][h2][w2][cin2], cin2 a multiple of 64 with
@@ -978,107 +841,6 @@ bool big_conv_supported(const drnmi_conv_args& p) {
          (p.ks == 1 || p.ks == 3) && x2_ok(p) && p.k_pad == p.k &&
          (p.out_dtype == DRNMI_F32 || (p.y_sc == 1 && p.y_sp == p.cout));
 }
-
-int big_conv_dispatch(const drnmi_conv_args& p, int variant, hipStream_t s) {
-  if (variant == kS2Row || (variant < 0 && s2row_auto(p))) return s2row_conv_dispatch(p, s);
-  if (variant == kS1X2Row || (variant < 0 && s1x2row_auto(p))) return s1x2row_conv_dispatch(p, s);
-  if (variant == kW1 || variant == kW1H) {
-    if (!big_conv_supported(p) || !(variant == kW1 ? w1_ok(p) : w1h_ok(p))) return DRNMI_ENOTSUP;
-    const hipError_t e = variant == kW1 ? launch_w1(p, s) : launch_w1h(p, s);
-    return e == hipErrorInvalidValue ? DRNMI_ENOTSUP : static_cast<int>(e);
-  }
-  // the halo kernel (cin/cout 64-128) stays dense: it beats unit skipping on those shapes
-  if (variant == kHalo || (variant < 0 && halo_conv_supported(p) && halo_preferred(p))) return halo_conv_dispatch(p, s);
-  if (!big_conv_supported(p)) return DRNMI_ENOTSUP;
-  const bool auto_pick = variant < 0;
-  if (variant < 0) variant = auto_variant(p);
-  if (auto_pick) {
-    if (w1_auto(p)) variant = kW1;
-    else if (w1h_auto(p)) variant = kW1H;
-    else if (stag_ok(p)) variant = kStag;
-    else if (variant == 1 && strip_ok(p)) variant = kStrip;
-  }
-  if (variant == kW1 || variant == kW1H) {
-    const hipError_t e = variant == kW1 ? launch_w1(p, s) : launch_w1h(p, s);
-    return e == hipErrorInvalidValue ? DRNMI_ENOTSUP : static_cast<int>(e);
-  }
-  if (variant == kStrip || variant == kStag) {
-    if (variant == kStag ? !stag_ok(p) : (!strip_ok(p) || p.cin < 64)) return DRNMI_ENOTSUP;
-    if (variant == kStrip && (p.cout + 255) / 256 * 256 > p.cout_pad) return DRNMI_EINVAL;
-    const hipError_t e = variant == kStag ? launch_stag(p, s) : launch_strip(p, s);
-    return e == hipErrorInvalidValue ? DRNMI_ENOTSUP : static_cast<int>(e);
-  }
-  if (variant >= kNumVariants) return DRNMI_ENOTSUP;
-  const Variant& v = kVariants[variant];
-  if (p.cin < v.bk) return DRNMI_ENOTSUP;                            // a K step must fit in one tap
-  // every weight row a tile's DMA reads must exist: ceil(cout / BCO) * BCO <= cout_pad
-  if ((p.cout + v.bco - 1) / v.bco * v.bco > p.cout_pad) return DRNMI_EINVAL;
-  hipError_t e;
-  if (variant == kPingPong) {
-    if (p.cout % 256 != 0 || p.x2 != nullptr) return DRNMI_ENOTSUP;
-    e = p.ks == 3 ? launch_pp<3>(p, s) : launch_pp<1>(p, s);
-    return e == hipErrorInvalidValue ? DRNMI_ENOTSUP : static_cast<int>(e);
-  }
-  const int base = variant % 6;
-  const bool persist = variant >= 6;
-  if (p.x2 != nullptr) {                  // fused second input: its own instantiation (bases 0 / 1)
-    if (persist || (base != 0 && base != 1)) return DRNMI_ENOTSUP;
-    if (p.ks == 3) e = base == 1 ? launch_big<3, 128, 2, 2, 64, false, 4, false, true>(p, s)
-                                 : launch_big<3, 128, 1, 3, 64, false, 4, false, true>(p, s);
-    else e = base == 1 ? launch_big<1, 128, 2, 2, 64, false, 4, false, true>(p, s)
-                       : launch_big<1, 128, 1, 3, 64, false, 4, false, true>(p, s);
-    return e == hipErrorInvalidValue ? DRNMI_ENOTSUP : static_cast<int>(e);
-  }
-  if (p.unit_mask != nullptr && !persist && sparse_name(p.ks, base) != nullptr && p.k_pad / v.bk <= 128) {
-    e = p.ks == 3 ? launch_sparse<3>(p, base, s) : launch_sparse<1>(p, base, s);
-    return e == hipErrorInvalidValue ? DRNMI_ENOTSUP : static_cast<int>(e);
-  }
-  if (p.ks == 3) e = persist ? launch_base<3, true>(p, base, s) : launch_base<3, false>(p, base, s);
-  else e = persist ? launch_base<1, true>(p, base, s) : launch_base<1, false>(p, base, s);
-  return e == hipErrorInvalidValue ? DRNMI_ENOTSUP : static_cast<int>(e);
-}
-
-const char* big_conv_name(const drnmi_conv_args& p, int variant) {
-  if (variant == kS2Row || (variant < 0 && s2row_auto(p))) return s2row_conv_name(p);
-  if (variant == kS1X2Row || (variant < 0 && s1x2row_auto(p))) return s1x2row_conv_name(p);
-  if (variant == kW1 || variant == kW1H) {
-    if (!big_conv_supported(p) || !(variant == kW1 ? w1_ok(p) : w1h_ok(p))) return nullptr;
-    if (variant == kW1) return p.x2 != nullptr ? "conv_w1_x2_kernel" : "conv_w1_kernel";
-    return p.x2 != nullptr ? "conv_w1h_x2_kernel" : "conv_w1h_kernel";
-  }
-  if (variant == kHalo || (variant < 0 && halo_conv_supported(p) && halo_preferred(p))) return halo_conv_name(p);
-  const bool auto_pick = variant < 0;
-  if (variant < 0) variant = auto_variant(p);
-  if (auto_pick) {
-    if (w1_auto(p)) variant = kW1;
-    else if (w1h_auto(p)) variant = kW1H;
-    else if (stag_ok(p)) variant = kStag;
-    else if (variant == 1 && strip_ok(p)) variant = kStrip;
-  }
-  if (variant == kW1) return p.x2 != nullptr ? "conv_w1_x2_kernel" : "conv_w1_kernel";
-  if (variant == kW1H) return p.x2 != nullptr ? "conv_w1h_x2_kernel" : "conv_w1h_kernel";
-  if (variant == kStag) {
-    if (!stag_ok(p)) return nullptr;
-    if (p.cout <= 128) return p.x2 != nullptr ? "conv_stag128_x2_kernel" : "conv_stag128_kernel";
-    return p.x2 != nullptr ? "conv_stag_x2_kernel" : "conv_stag_kernel";
-  }
-  if (variant == kStrip) return strip_ok(p) && p.cin >= 64 ? "conv_strip_kernel" : nullptr;
-  if (variant >= kNumVariants) return nullptr;
-  if (p.x2 != nullptr) {
-    if (variant != 0 && variant != 1) return nullptr;
-    static const char* n[2][2] = {{"conv_big_kernel<1, 128, 1, 3, 64, false, 4, false, true>",
-                                   "conv_big_kernel<1, 128, 2, 2, 64, false, 4, false, true>"},
-                                  {"conv_big_kernel<3, 128, 1, 3, 64, false, 4, false, true>",
-                                   "conv_big_kernel<3, 128, 2, 2, 64, false, 4, false, true>"}};
-    return n[p.ks == 3 ? 1 : 0][variant];
-  }
-  if (p.unit_mask != nullptr && variant < 6 && sparse_name(p.ks, variant) != nullptr &&
-      p.k_pad / kVariants[variant].bk <= 128)
-    return sparse_name(p.ks, variant);
-  return p.ks == 3 ? kVariants[variant].name3 : kVariants[variant].name1;
-}
-
-int big_conv_num_variants() { return kNumVariants; }
 
 int weight_unit_mask(const void* wgt, int dtype, int rows_pad, int k_pad, uint32_t* mask, int* count,
                      hipStream_t s) {
@@ -1103,53 +865,7 @@ int weight_unit_mask(const void* wgt, int dtype, int rows_pad, int k_pad, uint32
 }
 
 }  // namespace drnmi
-
-using namespace drnmi;
-
-// The labels-only video path's last 3x3 conv (D-22 layer8) with the seg classifier folded into its
-// epilogue (conv_stag.hip SEGF): same launch geometry and MFMA work as conv_stag_kernel, the
-// activation is never stored.  Validated like the conv it replaces plus the seg operands.
-extern "C" int drnmi_conv_stag_seg(const drnmi_conv_args* a, const void* seg_w, int32_t seg_k_pad, int32_t seg_rows,
-                                   void* partials, void* stream) {
-  if (a == nullptr || seg_w == nullptr || partials == nullptr) return DRNMI_EINVAL;
-  const drnmi_conv_args& p = *a;
-  if (p.x == nullptr || p.wgt == nullptr || p.shift == nullptr) return DRNMI_EINVAL;
-  if (p.algo != DRNMI_ALGO_IGEMM || p.src_u8) return DRNMI_EINVAL;
-  if (p.dtype == DRNMI_I8) {
-    // int8 nets: the conv's int8 output (out_dtype I8, quantised with out_scale) feeds int8 seg
-    // weights; int32 partials
-    if (p.out_dtype != DRNMI_I8 || p.scale == nullptr) return DRNMI_EINVAL;
-    if (p.ho != (p.h + 2 * p.pad - p.dil * (p.ks - 1) - 1) / p.stride + 1 ||
-        p.wo != (p.w + 2 * p.pad - p.dil * (p.ks - 1) - 1) / p.stride + 1)
-      return DRNMI_EINVAL;
-    if (seg_k_pad < p.cout || seg_k_pad % 16 != 0 || seg_rows < 32 || (reinterpret_cast<uintptr_t>(partials) & 15) != 0)
-      return DRNMI_EINVAL;
-    if (!(i8_conv_supported(p) && p.ks == 3 && i8_stag_ok(p)) || p.res != nullptr || p.cout % 256 != 0 ||
-        p.cout_pad < p.cout)
-      return DRNMI_ENOTSUP;
-    // the one-wave-per-SIMD int8 tile (conv_w1_i8_seg_kernel); tile 19 forces the staggered one
-    const hipError_t e = p.tile == 4 + kStag ? launch_stag_seg(p, seg_w, seg_k_pad, partials, reinterpret_cast<hipStream_t>(stream))
-                                             : launch_w1_seg(p, seg_w, seg_k_pad, partials, reinterpret_cast<hipStream_t>(stream));
-    return e == hipErrorInvalidValue ? DRNMI_ENOTSUP : static_cast<int>(e);
-  }
-  if (p.dtype != DRNMI_BF16 || p.out_dtype != DRNMI_BF16) return DRNMI_EINVAL;
-  if (p.ho != (p.h + 2 * p.pad - p.dil * (p.ks - 1) - 1) / p.stride + 1 ||
-      p.wo != (p.w + 2 * p.pad - p.dil * (p.ks - 1) - 1) / p.stride + 1)
-    return DRNMI_EINVAL;
-  if (seg_k_pad < p.cout || seg_k_pad % 8 != 0 || seg_rows < 32 || (reinterpret_cast<uintptr_t>(partials) & 15) != 0)
-    return DRNMI_EINVAL;
-  if (!(big_conv_supported(p) && stag_ok(p)) || p.x2 != nullptr ||
-      p.scale != nullptr || p.res != nullptr || p.cout % 256 != 0 || p.cout_pad < p.cout)
-    return DRNMI_ENOTSUP;
-  // the one-wave-per-SIMD tile (conv_w1_seg_kernel); tile 19 forces the staggered one (the same
-  // partial logits, bit for bit: the bit-identity test)
-  const hipError_t e = p.tile == 4 + kStag ? launch_stag_seg(p, seg_w, seg_k_pad, partials, reinterpret_cast<hipStream_t>(stream))
-                                           : launch_w1_seg(p, seg_w, seg_k_pad, partials, reinterpret_cast<hipStream_t>(stream));
-  return e == hipErrorInvalidValue ? DRNMI_ENOTSUP : static_cast<int>(e);
-}
-
-extern "C" const char* drnmi_conv_stag_seg_kernel_name(const drnmi_conv_args* a) {
-  if (a == nullptr) return nullptr;
-  if (a->dtype == DRNMI_I8) return a->tile == 4 + kStag ? "conv_i8_stag_seg_kernel" : "conv_w1_i8_seg_kernel";
-  return a->tile == 4 + kStag ? "conv_stag_seg_kernel" : "conv_w1_seg_kernel";
+extern "C" int drnmi_weight_unit_mask(const void* wgt, int32_t dtype, int32_t rows_pad, int32_t k_pad,
+                                      uint32_t* mask, int32_t* nonzero_units, void* stream) {
+  return drnmi::weight_unit_mask(wgt, dtype, rows_pad, k_pad, mask, nonzero_units, reinterpret_cast<hipStream_t>(stream));
 }

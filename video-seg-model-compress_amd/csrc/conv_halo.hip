@@ -371,9 +371,9 @@ conv_halo_kernel(const drnmi_conv_args p) {
 // measured the same: 128.0 vs 128.3 us, D-22 layer3, 8 frames)
 constexpr int halo_tc(int /*cin*/, int /*cout*/) { return 64; }
 
-template <int CIN, int WC>
+template <int CIN, int WC, int TC>
 hipError_t launch_halo(const drnmi_conv_args& p, hipStream_t s) {
-  constexpr int TC = halo_tc(CIN, 64 * WC);
+  static_assert(TC == halo_tc(CIN, 64 * WC), "the block width halo_conv_supported sizes the patch for");
   const int lds = kNST * 64 * WC * 128 + patch_bytes(CIN, p.dil, TC);
   static int attr_lds = 0;
   if (attr_lds < lds) {
@@ -409,18 +409,11 @@ bool halo_conv_supported(const drnmi_conv_args& p) {
   return kNST * 64 * wc * 128 + patch_bytes(p.cin, p.dil, halo_tc(p.cin, p.cout)) <= 160 * 1024;
 }
 
-int halo_conv_dispatch(const drnmi_conv_args& p, hipStream_t s) {
-  if (!halo_conv_supported(p)) return DRNMI_ENOTSUP;
-  hipError_t e;
-  if (p.cin == 64) e = p.cout == 64 ? launch_halo<64, 1>(p, s) : launch_halo<64, 2>(p, s);
-  else e = p.cout == 64 ? launch_halo<128, 1>(p, s) : launch_halo<128, 2>(p, s);
-  return static_cast<int>(e);
-}
-
-const char* halo_conv_name(const drnmi_conv_args& p) {
-  if (p.cin == 64)
-    return p.cout == 64 ? "conv_halo_kernel<64, 1, 64>" : "conv_halo_kernel<64, 2, 64>";
-  return p.cout == 64 ? "conv_halo_kernel<128, 1, 64>" : "conv_halo_kernel<128, 2, 64>";
+const ConvKernel* halo_kernel(int cin, int cout) {
+  static const ConvKernel k[2][2] = {
+      {DRNMI_KERNEL_ROW(conv_halo_kernel, launch_halo, 64, 1, 64), DRNMI_KERNEL_ROW(conv_halo_kernel, launch_halo, 64, 2, 64)},
+      {DRNMI_KERNEL_ROW(conv_halo_kernel, launch_halo, 128, 1, 64), DRNMI_KERNEL_ROW(conv_halo_kernel, launch_halo, 128, 2, 64)}};
+  return &k[cin == 128][cout == 128];
 }
 
 }  // namespace drnmi

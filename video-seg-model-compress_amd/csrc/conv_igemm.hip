@@ -22,8 +22,6 @@
 #include "common.h"
 #include "kernels.h"
 
-#include <cstdio>
-
 namespace drnmi {
 
 namespace {
@@ -245,32 +243,6 @@ conv_igemm_kernel(const drnmi_conv_args p) {
   }
 }
 
-struct TileDesc {
-  int bm, bn;
-  const char* name;
-};
-
-constexpr TileDesc kTiles[] = {
-    {128, 128, "128x128"},
-    {128, 64, "128x64"},
-    {256, 32, "256x32"},
-    {256, 16, "256x16"},
-    // conv_big.hip (bf16, LDS-DMA implicit GEMM, cin >= 32, ks 1/3): cout tile x 256 pixels
-    {128, 128, "dma128"}, {256, 256, "dma256"}, {64, 64, "dma64k32"}, {32, 32, "dma32"},
-    {256, 256, "dma256k32"}, {128, 128, "dma128k32"},
-    {128, 128, "dma128p"}, {256, 256, "dma256p"}, {64, 64, "dma64k32p"}, {32, 32, "dma32p"},
-    {256, 256, "dma256k32p"}, {128, 128, "dma128k32p"},   // p = persistent
-    {256, 256, "pp256"},                                   // ping-pong 4-phase schedule
-    {128, 128, "halo"},                                    // conv_halo.hip, 4x64 pixel block
-    {256, 256, "strip256"},                                // conv_big.hip, strip-staged B (3x3, wo % 256 == 0)
-    {256, 256, "stag256"},                                 // the strip tile, SIMD partners half a K step apart
-    {64, 64, "s2row"},                                     // conv_s2row.hip: stride-2 3x3 32->64 / 64->128 row walk
-    {64, 64, "s1x2row"},                                   // conv_s2row.hip: stride-1 3x3 64->64 + 1x1 s2 downsample
-    {256, 256, "w1stag256"},                               // conv_w1.hip: the stag256 tile as 4 waves of 128 x 128
-    {128, 128, "w1h128"},                                  // conv_w1.hip: 128 x 128 tile, 4 waves of 64 x 64, 2 per CU
-};
-constexpr int kNumTiles = sizeof(kTiles) / sizeof(kTiles[0]);
-
 template <typename T, int BM, int BN, int WM, int WN, int KS>
 hipError_t launch_conv(const drnmi_conv_args& p, hipStream_t stream) {
   const int64_t M = static_cast<int64_t>(p.n) * p.ho * p.wo;
@@ -280,140 +252,22 @@ hipError_t launch_conv(const drnmi_conv_args& p, hipStream_t stream) {
   return hipGetLastError();
 }
 
-template <typename T, int KS>
-hipError_t dispatch_tile(const drnmi_conv_args& p, int tile, hipStream_t s) {
-  switch (tile) {
-    case 0: return launch_conv<T, 128, 128, 2, 2, KS>(p, s);
-    case 1: return launch_conv<T, 128, 64, 2, 2, KS>(p, s);
-    case 2: return launch_conv<T, 256, 32, 4, 1, KS>(p, s);
-    case 3: return launch_conv<T, 256, 16, 4, 1, KS>(p, s);
-    default: return hipErrorInvalidValue;
-  }
-}
-
-template <typename T>
-hipError_t dispatch_ks(const drnmi_conv_args& p, int tile, hipStream_t s) {
-  switch (p.ks) {
-    case 1: return dispatch_tile<T, 1>(p, tile, s);
-    case 3: return dispatch_tile<T, 3>(p, tile, s);
-    case 7: return dispatch_tile<T, 7>(p, tile, s);
-    default: return hipErrorInvalidValue;
-  }
-}
-
-int auto_tile(int cout) {
-  if (cout > 64) return 0;
-  if (cout > 32) return 1;
-  if (cout > 16) return 2;
-  return 3;
-}
-
+// the element types as the kernel names spell them
+using bf16 = bf16_t;
+using f32 = float;
+#define IGEMM_TILES(T, KS)                                                 \
+  {DRNMI_KERNEL_ROW(conv_igemm_kernel, launch_conv, T, 128, 128, 2, 2, KS), \
+   DRNMI_KERNEL_ROW(conv_igemm_kernel, launch_conv, T, 128, 64, 2, 2, KS),  \
+   DRNMI_KERNEL_ROW(conv_igemm_kernel, launch_conv, T, 256, 32, 4, 1, KS),  \
+   DRNMI_KERNEL_ROW(conv_igemm_kernel, launch_conv, T, 256, 16, 4, 1, KS)}
+// [bf16][ks 1 / 3 / 7][tile]
 }  // namespace
 
+const ConvKernel* igemm_kernel(int dtype, int tile, int ks) {
+  static const ConvKernel kIgemm[2][3][4] = {{IGEMM_TILES(f32, 1), IGEMM_TILES(f32, 3), IGEMM_TILES(f32, 7)},
+                                             {IGEMM_TILES(bf16, 1), IGEMM_TILES(bf16, 3), IGEMM_TILES(bf16, 7)}};
+  const int k = ks == 1 ? 0 : ks == 3 ? 1 : ks == 7 ? 2 : -1;
+  return k < 0 ? nullptr : &kIgemm[dtype == DRNMI_BF16][k][tile];
+}
+
 }  // namespace drnmi
-
-using namespace drnmi;
-
-extern "C" int drnmi_conv_num_tiles(void) { return kNumTiles; }
-
-extern "C" const char* drnmi_conv_tile_name(int tile) {
-  return (tile >= 0 && tile < kNumTiles) ? kTiles[tile].name : nullptr;
-}
-
-extern "C" int drnmi_conv2d_bn_act(const drnmi_conv_args* a, void* stream) {
-  if (a == nullptr) return DRNMI_EINVAL;
-  const drnmi_conv_args& p = *a;
-  // BN-statistics partials and output row strides: conv_x6 only
-  if (p.stats != nullptr && (p.algo != DRNMI_ALGO_IGEMM || x6_conv_stats_rows(p) <= 0)) return DRNMI_EINVAL;
-  if (p.y_sr != 0 && (p.algo != DRNMI_ALGO_IGEMM || p.dtype != DRNMI_F32X3 || p.y_sc != 1 || p.y_sr < 0 ||
-                      !x6_conv_supported(p)))
-    return DRNMI_EINVAL;
-  if (p.algo == DRNMI_ALGO_PATCH) {
-    if (p.x2 != nullptr) return DRNMI_ENOTSUP;     // fused second input: LDS-DMA kernels only
-    if (p.x == nullptr || p.wgt == nullptr || p.y == nullptr || p.shift == nullptr ||
-        p.n <= 0 || p.h <= 0 || p.w <= 0 || p.cout > p.cout_pad)
-      return DRNMI_EINVAL;
-    if (p.ho != (p.h + 2 * p.pad - p.dil * (p.ks - 1) - 1) / p.stride + 1 ||
-        p.wo != (p.w + 2 * p.pad - p.dil * (p.ks - 1) - 1) / p.stride + 1)
-      return DRNMI_EINVAL;
-    return patch_conv_dispatch(p, reinterpret_cast<hipStream_t>(stream));
-  }
-  if (p.algo != DRNMI_ALGO_IGEMM || p.src_u8) return DRNMI_EINVAL;
-  const bool pow2 = p.cin >= 8 && (p.cin & (p.cin - 1)) == 0;
-  if (!pow2 || p.n <= 0 || p.h <= 0 || p.w <= 0 || p.ho <= 0 || p.wo <= 0) return DRNMI_EINVAL;
-  if (p.cout <= 0 || p.cout > p.cout_pad || p.k != p.ks * p.ks * p.cin + (p.x2 != nullptr ? p.cin2 : 0))
-    return DRNMI_EINVAL;
-  if (p.k_pad < p.k || p.k_pad % kBK != 0 || p.stride <= 0 || p.dil <= 0 || p.pad < 0) return DRNMI_EINVAL;
-  if (p.x == nullptr || p.wgt == nullptr || p.y == nullptr || p.shift == nullptr)
-    return DRNMI_EINVAL;
-  if (p.dtype == DRNMI_I8) {
-    if (p.out_dtype != DRNMI_I8 && p.out_dtype != DRNMI_BF16 && p.out_dtype != DRNMI_F32) return DRNMI_EINVAL;
-  } else if (p.dtype == DRNMI_F32X3) {
-    if (p.out_dtype != DRNMI_F32) return DRNMI_EINVAL;
-  } else if ((p.dtype != DRNMI_BF16 && p.dtype != DRNMI_F32) ||
-             (p.out_dtype != DRNMI_BF16 && p.out_dtype != DRNMI_F32)) {
-    return DRNMI_EINVAL;
-  }
-  // Output geometry must be the conv's: ho = (h + 2 pad - dil (ks-1) - 1) / stride + 1 -- except for
-  // the row-strided (y_sr) class launches of a stride-2 data gradient, whose taps past the input's
-  // bottom / right edge read zeros (an asymmetric pad; conv_x6 bounds-checks every tap)
-  if (p.y_sr == 0 && (p.ho != (p.h + 2 * p.pad - p.dil * (p.ks - 1) - 1) / p.stride + 1 ||
-                      p.wo != (p.w + 2 * p.pad - p.dil * (p.ks - 1) - 1) / p.stride + 1))
-    return DRNMI_EINVAL;
-  if (p.dtype == DRNMI_I8) return i8_conv_dispatch(p, reinterpret_cast<hipStream_t>(stream));   // int8: one kernel family
-  if (p.dtype == DRNMI_F32X3) return x6_conv_dispatch(p, reinterpret_cast<hipStream_t>(stream));
-  if (p.tile >= 4 || (p.tile < 0 && (big_conv_supported(p) || halo_conv_supported(p))))
-    return big_conv_dispatch(p, p.tile < 0 ? -1 : p.tile - 4, reinterpret_cast<hipStream_t>(stream));
-  if (p.x2 != nullptr) return DRNMI_ENOTSUP;          // fused second input: LDS-DMA kernels only
-  const int tile = p.tile < 0 ? auto_tile(p.cout) : p.tile;
-  if (tile >= 4 || p.cout_pad % kTiles[tile].bn != 0) return DRNMI_EINVAL;
-  const int64_t M = static_cast<int64_t>(p.n) * p.ho * p.wo;
-  if (M >= (int64_t(1) << 31) / 2) return DRNMI_EINVAL;
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  hipError_t e = p.dtype == DRNMI_BF16 ? dispatch_ks<bf16_t>(p, tile, s) : dispatch_ks<float>(p, tile, s);
-  if (e == hipErrorInvalidValue) return DRNMI_ENOTSUP;
-  return static_cast<int>(e);
-}
-
-extern "C" int64_t drnmi_conv_workspace_bytes(const drnmi_conv_args* a) {
-  if (a == nullptr) return -1;
-  return a->dtype == DRNMI_F32X3 && a->algo == DRNMI_ALGO_IGEMM ? x6_conv_workspace_bytes(*a) : 0;
-}
-
-extern "C" int64_t drnmi_conv_stats_rows(const drnmi_conv_args* a) {
-  if (a == nullptr) return -1;
-  return a->dtype == DRNMI_F32X3 && a->algo == DRNMI_ALGO_IGEMM ? x6_conv_stats_rows(*a) : 0;
-}
-
-extern "C" int drnmi_stem_layer1(const drnmi_conv_args* stem, const drnmi_conv_args* next, void* stream) {
-  if (stem == nullptr || next == nullptr) return DRNMI_EINVAL;
-  return stem_l1_dispatch(*stem, *next, reinterpret_cast<hipStream_t>(stream));
-}
-
-extern "C" const char* drnmi_stem_layer1_kernel_name(const drnmi_conv_args* stem, const drnmi_conv_args* next) {
-  if (stem == nullptr || next == nullptr || !stem_l1_ok(*stem, *next)) return nullptr;
-  return "stem_l1_kernel";
-}
-
-extern "C" int drnmi_weight_unit_mask(const void* wgt, int32_t dtype, int32_t rows_pad, int32_t k_pad,
-                                      uint32_t* mask, int32_t* nonzero_units, void* stream) {
-  return weight_unit_mask(wgt, dtype, rows_pad, k_pad, mask, nonzero_units, reinterpret_cast<hipStream_t>(stream));
-}
-
-extern "C" const char* drnmi_conv_kernel_name(const drnmi_conv_args* a) {
-  if (a == nullptr) return nullptr;
-  const drnmi_conv_args& p = *a;
-  if (p.algo == DRNMI_ALGO_PATCH) return patch_conv_name(p);
-  if (p.dtype == DRNMI_I8) return i8_conv_name(p);
-  if (p.dtype == DRNMI_F32X3) return x6_conv_name(p);
-  if (p.tile >= 4 || (p.tile < 0 && (big_conv_supported(p) || halo_conv_supported(p))))
-    return big_conv_name(p, p.tile < 0 ? -1 : p.tile - 4);
-  const int tile = p.tile < 0 ? auto_tile(p.cout) : p.tile;
-  if (tile > 3 || (p.ks != 1 && p.ks != 3 && p.ks != 7)) return nullptr;
-  static const char* tn[4] = {"128, 128, 2, 2", "128, 64, 2, 2", "256, 32, 4, 1", "256, 16, 4, 1"};
-  static char buf[8][96];
-  static int slot = 0;
-  char* b = buf[slot++ & 7];
-  snprintf(b, 96, "conv_igemm_kernel<%s, %s, %d>", p.dtype == DRNMI_BF16 ? "bf16" : "f32", tn[tile], p.ks);
-  return b;
-}

@@ -487,48 +487,17 @@ int g_cus = 0;
 constexpr auto kern32 = &conv_s2row_kernel<32, kRing32, kWgs32>;
 constexpr auto kern64 = &conv_s2row_kernel<64, kRing64, kWgs64>;
 
-}  // namespace
-
-bool s2row_conv_supported(const drnmi_conv_args& p) {
-  const bool c32 = p.cin == 32 && p.cout == 64, c64 = p.cin == 64 && p.cout == 128;
-  return p.dtype == DRNMI_BF16 && p.out_dtype == DRNMI_BF16 && (c32 || c64) && p.ks == 3 && p.stride == 2 &&
-         p.pad == 1 && p.dil == 1 && p.scale == nullptr && p.res == nullptr && p.x2 == nullptr &&
-         p.unit_mask == nullptr && p.k == 9 * p.cin && p.k_pad >= p.k && p.k_pad % 8 == 0 && p.cout_pad >= p.cout &&
-         p.n > 0 && p.h >= 1 && p.w >= 1 && p.ho == (p.h - 1) / 2 + 1 && p.wo == (p.w - 1) / 2 + 1 && p.y_sc == 1 &&
-         p.y_sp == p.cout && p.y_sn == static_cast<int64_t>(p.ho) * p.wo * p.cout &&
-         static_cast<int64_t>(p.n) * p.h * p.w * p.cin * 2 < (int64_t(1) << 31) &&
-         static_cast<int64_t>(p.n) * p.ho * p.wo * p.cout * 2 < (int64_t(1) << 31);
-}
-
-bool s2row_auto(const drnmi_conv_args& p) { return s2row_conv_supported(p); }
-
-bool s1x2row_conv_supported(const drnmi_conv_args& p) {
-  return p.dtype == DRNMI_BF16 && p.out_dtype == DRNMI_BF16 && p.cin == 64 && p.cout == 64 && p.ks == 3 &&
-         p.stride == 1 && p.pad == 1 && p.dil == 1 && p.x2 != nullptr && p.cin2 == 32 && p.stride2 == 2 &&
-         p.scale == nullptr && p.res == nullptr && p.unit_mask == nullptr && p.k == 9 * 64 + 32 && p.k_pad >= p.k &&
-         p.k_pad % 8 == 0 && p.cout_pad >= 64 && p.n > 0 && p.h >= 1 && p.w >= 1 && p.ho == p.h && p.wo == p.w &&
-         2 * (p.ho - 1) < p.h2 && 2 * (p.wo - 1) < p.w2 && p.y_sc == 1 && p.y_sp == 64 &&
-         p.y_sn == static_cast<int64_t>(p.ho) * p.wo * 64 && static_cast<int64_t>(p.n) * p.h * p.w * 128 < (int64_t(1) << 31) &&
-         static_cast<int64_t>(p.n) * p.h2 * p.w2 * 64 < (int64_t(1) << 31);
-}
-
-bool s1x2row_auto(const drnmi_conv_args& p) { return s1x2row_conv_supported(p); }
-
-const char* s1x2row_conv_name(const drnmi_conv_args& p) {
-  return s1x2row_conv_supported(p) ? "conv_s1x2row_kernel" : nullptr;
-}
-
-int s1x2row_conv_dispatch(const drnmi_conv_args& p, hipStream_t st) {
-  if (!s1x2row_conv_supported(p)) return DRNMI_ENOTSUP;
+template <auto KERNEL>
+hipError_t launch_s1x2row(const drnmi_conv_args& p, hipStream_t st) {
   static int wgs = 0;
   if (wgs == 0) {
     int dev = 0, cus = 0;
     if (hipGetDevice(&dev) != hipSuccess ||
         hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0)
       cus = 256;
-    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_s1x2row_kernel),
+    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(KERNEL),
                                              hipFuncAttributeMaxDynamicSharedMemorySize, kS1Lds);
-    if (e != hipSuccess) return static_cast<int>(e);
+    if (e != hipSuccess) return e;
     wgs = 2 * cus;                                      // two workgroups per CU (58 KB LDS each)
   }
   S1Params a;
@@ -546,22 +515,18 @@ int s1x2row_conv_dispatch(const drnmi_conv_args& p, hipStream_t st) {
   a.relu = p.relu;
   a.strips = (p.w + 63) / 64;
   const int64_t total = static_cast<int64_t>(p.n) * a.strips * p.h;
-  if (total >= (int64_t(1) << 31)) return DRNMI_ENOTSUP;
+  if (total >= (int64_t(1) << 31)) return hipErrorInvalidValue;
   a.total = static_cast<int>(total);
   a.per_wg = (a.total + wgs - 1) / wgs;
   const int grid = (a.total + a.per_wg - 1) / a.per_wg;
-  hipLaunchKernelGGL(conv_s1x2row_kernel, dim3(grid), dim3(256), kS1Lds, st, a);
-  return static_cast<int>(hipGetLastError());
+  hipLaunchKernelGGL(KERNEL, dim3(grid), dim3(256), kS1Lds, st, a);
+  return hipGetLastError();
 }
 
-const char* s2row_conv_name(const drnmi_conv_args& p) {
-  if (!s2row_conv_supported(p)) return nullptr;
-  static_assert(kRing32 == 7 && kWgs32 == 2 && kRing64 == 7 && kWgs64 == 2, "kernel names below");
-  return p.cin == 32 ? "conv_s2row_kernel<32, 7, 2>" : "conv_s2row_kernel<64, 7, 2>";
-}
-
-int s2row_conv_dispatch(const drnmi_conv_args& p, hipStream_t st) {
-  if (!s2row_conv_supported(p)) return DRNMI_ENOTSUP;
+template <int CIN, int RING, int WGS>
+hipError_t launch_s2row(const drnmi_conv_args& p, hipStream_t st) {
+  static_assert(CIN == 32 ? (RING == kRing32 && WGS == kWgs32) : (CIN == 64 && RING == kRing64 && WGS == kWgs64),
+                "the instantiations whose attributes are set below");
   if (g_cus == 0) {
     int dev = 0, cus = 0;
     if (hipGetDevice(&dev) != hipSuccess ||
@@ -572,11 +537,10 @@ int s2row_conv_dispatch(const drnmi_conv_args& p, hipStream_t st) {
     if (e == hipSuccess)
       e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern64), hipFuncAttributeMaxDynamicSharedMemorySize,
                               s2_lds_bytes<kRing64>());
-    if (e != hipSuccess) return static_cast<int>(e);
+    if (e != hipSuccess) return e;
     g_cus = cus;
   }
-  const bool c32 = p.cin == 32;
-  const int wgs = g_cus * (c32 ? kWgs32 : kWgs64);   // persistent: WGS workgroups per CU
+  const int wgs = g_cus * WGS;   // persistent: WGS workgroups per CU
   S2Params a;
   a.x = static_cast<const uint16_t*>(p.x);
   a.wgt = static_cast<const uint16_t*>(p.wgt);
@@ -589,16 +553,49 @@ int s2row_conv_dispatch(const drnmi_conv_args& p, hipStream_t st) {
   a.wo = p.wo;
   a.k_pad = p.k_pad;
   a.relu = p.relu;
-  const int ows = p.cin == 32 ? S2Cfg<32>::OWS : S2Cfg<64>::OWS;
+  const int ows = S2Cfg<CIN>::OWS;
   a.strips = (p.wo + ows - 1) / ows;
   const int64_t total = static_cast<int64_t>(p.n) * a.strips * p.ho;
-  if (total >= (int64_t(1) << 31)) return DRNMI_ENOTSUP;
+  if (total >= (int64_t(1) << 31)) return hipErrorInvalidValue;
   a.total = static_cast<int>(total);
   a.per_wg = (a.total + wgs - 1) / wgs;
   const int grid = (a.total + a.per_wg - 1) / a.per_wg;
-  if (c32) hipLaunchKernelGGL(kern32, dim3(grid), dim3(256), s2_lds_bytes<kRing32>(), st, a);
-  else hipLaunchKernelGGL(kern64, dim3(grid), dim3(256), s2_lds_bytes<kRing64>(), st, a);
-  return static_cast<int>(hipGetLastError());
+  hipLaunchKernelGGL((conv_s2row_kernel<CIN, RING, WGS>), dim3(grid), dim3(256), s2_lds_bytes<RING>(), st, a);
+  return hipGetLastError();
+}
+
+}  // namespace
+
+bool s2row_conv_supported(const drnmi_conv_args& p) {
+  const bool c32 = p.cin == 32 && p.cout == 64, c64 = p.cin == 64 && p.cout == 128;
+  return p.dtype == DRNMI_BF16 && p.out_dtype == DRNMI_BF16 && (c32 || c64) && p.ks == 3 && p.stride == 2 &&
+         p.pad == 1 && p.dil == 1 && p.scale == nullptr && p.res == nullptr && p.x2 == nullptr &&
+         p.unit_mask == nullptr && p.k == 9 * p.cin && p.k_pad >= p.k && p.k_pad % 8 == 0 && p.cout_pad >= p.cout &&
+         p.n > 0 && p.h >= 1 && p.w >= 1 && p.ho == (p.h - 1) / 2 + 1 && p.wo == (p.w - 1) / 2 + 1 && p.y_sc == 1 &&
+         p.y_sp == p.cout && p.y_sn == static_cast<int64_t>(p.ho) * p.wo * p.cout &&
+         static_cast<int64_t>(p.n) * p.h * p.w * p.cin * 2 < (int64_t(1) << 31) &&
+         static_cast<int64_t>(p.n) * p.ho * p.wo * p.cout * 2 < (int64_t(1) << 31);
+}
+
+bool s1x2row_conv_supported(const drnmi_conv_args& p) {
+  return p.dtype == DRNMI_BF16 && p.out_dtype == DRNMI_BF16 && p.cin == 64 && p.cout == 64 && p.ks == 3 &&
+         p.stride == 1 && p.pad == 1 && p.dil == 1 && p.x2 != nullptr && p.cin2 == 32 && p.stride2 == 2 &&
+         p.scale == nullptr && p.res == nullptr && p.unit_mask == nullptr && p.k == 9 * 64 + 32 && p.k_pad >= p.k &&
+         p.k_pad % 8 == 0 && p.cout_pad >= 64 && p.n > 0 && p.h >= 1 && p.w >= 1 && p.ho == p.h && p.wo == p.w &&
+         2 * (p.ho - 1) < p.h2 && 2 * (p.wo - 1) < p.w2 && p.y_sc == 1 && p.y_sp == 64 &&
+         p.y_sn == static_cast<int64_t>(p.ho) * p.wo * 64 && static_cast<int64_t>(p.n) * p.h * p.w * 128 < (int64_t(1) << 31) &&
+         static_cast<int64_t>(p.n) * p.h2 * p.w2 * 64 < (int64_t(1) << 31);
+}
+
+const ConvKernel* s2row_kernel(int cin) {
+  static const ConvKernel k[2] = {DRNMI_KERNEL_ROW(conv_s2row_kernel, launch_s2row, 32, 7, 2),
+                                  DRNMI_KERNEL_ROW(conv_s2row_kernel, launch_s2row, 64, 7, 2)};
+  return &k[cin == 64];
+}
+
+const ConvKernel* s1x2row_kernel() {
+  static const ConvKernel k = DRNMI_KERNEL_ROW0(conv_s1x2row_kernel, launch_s1x2row);
+  return &k;
 }
 
 }  // namespace drnmi

@@ -582,6 +582,7 @@ conv_stag_x2_kernel(const drnmi_conv_args p) {
 constexpr int kStagLds = 2 * 256 * 128 + 2 * kStripBytes;     // 2 A stages + 2 strips (130 KB)
 constexpr int kStag128Lds = 2 * 128 * 128 + 2 * kStripBytes;  // 128-channel tile (98 KB)
 
+template <auto KERNEL>
 hipError_t launch_stag_seg(const drnmi_conv_args& p, const void* seg_w, int seg_k_pad, void* part, hipStream_t s) {
   static bool attr_set = false;
   if (!attr_set) {
@@ -596,12 +597,11 @@ hipError_t launch_stag_seg(const drnmi_conv_args& p, const void* seg_w, int seg_
   a.sf = SegFuse{seg_w, seg_k_pad, part};
   const int64_t M = static_cast<int64_t>(p.n) * p.ho * p.wo;
   const dim3 grid(static_cast<unsigned>((M / kBPX) * ((p.cout + 255) / 256)));
-  if (p.dtype == DRNMI_I8) hipLaunchKernelGGL(conv_i8_stag_seg_kernel, grid, dim3(512), kStagLds, s, a);
-  else hipLaunchKernelGGL(conv_stag_seg_kernel, grid, dim3(512), kStagLds, s, a);
+  hipLaunchKernelGGL(KERNEL, grid, dim3(512), kStagLds, s, a);
   return hipGetLastError();
 }
 
-hipError_t launch_stag(const drnmi_conv_args& p, hipStream_t s) {
+static hipError_t stag_attrs() {
   static bool attr_set = false;
   if (!attr_set) {
     for (const void* f : {reinterpret_cast<const void*>(&conv_stag_kernel), reinterpret_cast<const void*>(&conv_stag_x2_kernel),
@@ -615,20 +615,43 @@ hipError_t launch_stag(const drnmi_conv_args& p, hipStream_t s) {
     }
     attr_set = true;
   }
+  return hipSuccess;
+}
+
+// the 256-channel tile
+template <auto KERNEL>
+hipError_t launch_stag(const drnmi_conv_args& p, hipStream_t s) {
+  const hipError_t e = stag_attrs();
+  if (e != hipSuccess) return e;
   const int64_t M = static_cast<int64_t>(p.n) * p.ho * p.wo;
   const dim3 grid(static_cast<unsigned>((M / kBPX) * ((p.cout + 255) / 256)));
-  if (p.dtype != DRNMI_I8 && p.cout <= 128) {
-    const dim3 g128(static_cast<unsigned>((M / kBPX) * ((p.cout + 127) / 128)));
-    if (p.x2 != nullptr) hipLaunchKernelGGL(conv_stag128_x2_kernel, g128, dim3(512), kStag128Lds, s, p);
-    else hipLaunchKernelGGL(conv_stag128_kernel, g128, dim3(512), kStag128Lds, s, p);
-  } else if (p.dtype == DRNMI_I8) {
-    hipLaunchKernelGGL(conv_i8_stag_kernel, grid, dim3(512), kStagLds, s, p);
-  } else if (p.x2 != nullptr) {
-    hipLaunchKernelGGL(conv_stag_x2_kernel, grid, dim3(512), kStagLds, s, p);
-  } else {
-    hipLaunchKernelGGL(conv_stag_kernel, grid, dim3(512), kStagLds, s, p);
-  }
+  hipLaunchKernelGGL(KERNEL, grid, dim3(512), kStagLds, s, p);
   return hipGetLastError();
+}
+
+// the 128-channel tile (bf16, cout <= 128)
+template <auto KERNEL>
+hipError_t launch_stag128(const drnmi_conv_args& p, hipStream_t s) {
+  const hipError_t e = stag_attrs();
+  if (e != hipSuccess) return e;
+  const int64_t M = static_cast<int64_t>(p.n) * p.ho * p.wo;
+  const dim3 g128(static_cast<unsigned>((M / kBPX) * ((p.cout + 127) / 128)));
+  hipLaunchKernelGGL(KERNEL, g128, dim3(512), kStag128Lds, s, p);
+  return hipGetLastError();
+}
+
+const ConvKernel* stag_kernel(bool i8, bool tile128, bool x2) {
+  static const ConvKernel k[2][2] = {
+      {DRNMI_KERNEL_ROW0(conv_stag_kernel, launch_stag), DRNMI_KERNEL_ROW0(conv_stag_x2_kernel, launch_stag)},
+      {DRNMI_KERNEL_ROW0(conv_stag128_kernel, launch_stag128), DRNMI_KERNEL_ROW0(conv_stag128_x2_kernel, launch_stag128)}};
+  static const ConvKernel k8 = DRNMI_KERNEL_ROW0(conv_i8_stag_kernel, launch_stag);
+  return i8 ? &k8 : &k[tile128][x2];
+}
+
+const SegKernel* stag_seg_kernel(bool i8) {
+  static const SegKernel k[2] = {DRNMI_SEG_ROW(conv_stag_seg_kernel, launch_stag_seg),
+                                 DRNMI_SEG_ROW(conv_i8_stag_seg_kernel, launch_stag_seg)};
+  return &k[i8];
 }
 
 }  // namespace drnmi

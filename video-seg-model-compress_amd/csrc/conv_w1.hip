@@ -707,6 +707,7 @@ static hipError_t w1_attrs() {
   return hipSuccess;
 }
 
+template <auto KERNEL>
 hipError_t launch_w1_seg(const drnmi_conv_args& p, const void* seg_w, int seg_k_pad, void* part, hipStream_t s) {
   const hipError_t e = w1_attrs();
   if (e != hipSuccess) return e;
@@ -715,31 +716,46 @@ hipError_t launch_w1_seg(const drnmi_conv_args& p, const void* seg_w, int seg_k_
   a.sf = W1Seg{seg_w, seg_k_pad, part};
   const int64_t M = static_cast<int64_t>(p.n) * p.ho * p.wo;
   const dim3 grid(static_cast<unsigned>((M / W1::TPX) * ((p.cout + 255) / 256)));
-  if (p.dtype == DRNMI_I8) hipLaunchKernelGGL(conv_w1_i8_seg_kernel, grid, dim3(256), W1::LDS, s, a);
-  else hipLaunchKernelGGL(conv_w1_seg_kernel, grid, dim3(256), W1::LDS, s, a);
+  hipLaunchKernelGGL(KERNEL, grid, dim3(256), W1::LDS, s, a);
   return hipGetLastError();
 }
 
+template <auto KERNEL>
 hipError_t launch_w1(const drnmi_conv_args& p, hipStream_t s) {
   const hipError_t e0 = w1_attrs();
   if (e0 != hipSuccess) return e0;
   const int64_t M = static_cast<int64_t>(p.n) * p.ho * p.wo;
   const dim3 grid(static_cast<unsigned>((M / W1::TPX) * ((p.cout + 255) / 256)));
-  if (p.dtype == DRNMI_I8) hipLaunchKernelGGL(conv_w1_i8_kernel, grid, dim3(256), W1::LDS, s, p);
-  else if (p.x2 != nullptr) hipLaunchKernelGGL(conv_w1_x2_kernel, grid, dim3(256), W1::LDS, s, p);
-  else hipLaunchKernelGGL(conv_w1_kernel, grid, dim3(256), W1::LDS, s, p);
+  hipLaunchKernelGGL(KERNEL, grid, dim3(256), W1::LDS, s, p);
   return hipGetLastError();
 }
 
+template <auto KERNEL>
 hipError_t launch_w1h(const drnmi_conv_args& p, hipStream_t s) {
   const hipError_t e0 = w1_attrs();
   if (e0 != hipSuccess) return e0;
   const int64_t M = static_cast<int64_t>(p.n) * p.ho * p.wo;
   const dim3 grid(static_cast<unsigned>((M / W1H::TPX) * ((p.cout + 127) / 128)));
-  if (p.dtype == DRNMI_I8) hipLaunchKernelGGL(conv_w1h_i8_kernel, grid, dim3(256), W1H::LDS, s, p);
-  else if (p.x2 != nullptr) hipLaunchKernelGGL(conv_w1h_x2_kernel, grid, dim3(256), W1H::LDS, s, p);
-  else hipLaunchKernelGGL(conv_w1h_kernel, grid, dim3(256), W1H::LDS, s, p);
+  hipLaunchKernelGGL(KERNEL, grid, dim3(256), W1H::LDS, s, p);
   return hipGetLastError();
+}
+
+const ConvKernel* w1_kernel(bool i8, bool x2) {
+  static const ConvKernel k[3] = {DRNMI_KERNEL_ROW0(conv_w1_kernel, launch_w1), DRNMI_KERNEL_ROW0(conv_w1_x2_kernel, launch_w1),
+                                  DRNMI_KERNEL_ROW0(conv_w1_i8_kernel, launch_w1)};
+  return &k[i8 ? 2 : x2];
+}
+
+const ConvKernel* w1h_kernel(bool i8, bool x2) {
+  static const ConvKernel k[3] = {DRNMI_KERNEL_ROW0(conv_w1h_kernel, launch_w1h), DRNMI_KERNEL_ROW0(conv_w1h_x2_kernel, launch_w1h),
+                                  DRNMI_KERNEL_ROW0(conv_w1h_i8_kernel, launch_w1h)};
+  return &k[i8 ? 2 : x2];
+}
+
+const SegKernel* w1_seg_kernel(bool i8) {
+  static const SegKernel k[2] = {DRNMI_SEG_ROW(conv_w1_seg_kernel, launch_w1_seg),
+                                 DRNMI_SEG_ROW(conv_w1_i8_seg_kernel, launch_w1_seg)};
+  return &k[i8];
 }
 
 }  // namespace drnmi

@@ -595,108 +595,27 @@ hipError_t launch_x6(const drnmi_conv_args& p, int splits, hipStream_t s) {
   return hipGetLastError();
 }
 
+}  // namespace
+
 // variants: 0 <K, 128, 2, 4> (256 channels x 256 pixels, 8 waves), 1 <K, 128, 1, 4> (128 x 256, 4
 // waves), 2 <K, 64, 1, 4> (64 x 256, 4 waves), 3 <K, 64, 2, 4> (128 x 256, 8 waves), 4 <K, 64, 2, 2>
 // (128 x 128, 4 waves, two workgroups per CU), 5 <K, 32, 2, 2> (64 x 128, 4 waves of 32 channels,
-// two per CU).  A drnmi_conv_args.tile >= 0 forces variant tile % 6 and, when tile >= 6, tile / 6
-// split-K partitions (tests, micro-benchmarks; split-K only with a caller workspace).  Every variant
-// keeps each accumulator's MFMA order: bit-identical.
-constexpr int kNumX6 = 6;
-constexpr int kX6Bco[kNumX6] = {256, 128, 64, 128, 128, 64};
-constexpr int kX6Bpx[kNumX6] = {256, 256, 256, 256, 128, 128};
-constexpr int kX6Occ[kNumX6] = {1, 1, 1, 1, 2, 2};
-// seconds per 32-channel K step of one workgroup tile, fitted to scripts/x6_micro.py's sweep on
+// two per CU).  Every variant keeps each accumulator's MFMA order: bit-identical.
+// step: seconds per 32-channel K step of one workgroup tile, fitted to scripts/x6_micro.py's sweep on
 // the fine-tune shapes (profiles/r8_finetune/x6_micro_variants.txt): the 256 x 256 tile ~4.3 us,
 // the 8-wave 128 x 256 ~3.0 us, the two-per-CU 128 x 128 ~2.7 us (its 2.1-3.0 us spread tracks
 // how the two resident workgroups overlap; past two rounds the model under-charges it)
-constexpr double kX6Step[kNumX6] = {4.3e-6, 3.6e-6, 2.2e-6, 3.0e-6, 2.7e-6, 2.3e-6};
-// 128-channel layers take the two-per-CU 128 x 128 tile: D-22 layer4's five launches 1631-1649 ->
-// 1510-1568 us against the 8-wave 128 x 256 tile, same box, three interleaved runs each
-// (profiles/r9_x6_v5/v4_ab.txt; the 8-wave tile had beaten the 4-wave one, 492 vs 511 us,
-// profiles/r7_x6).  64-channel
-// layers (and the 19-class seg) take the two-per-CU 64 x 128 tile (eight waves per CU instead of
-// four): D-22 layer3 3x3 750 -> 660 us at batch 8, the fine-tune's 1x1 256 -> 64 49 -> 37 us, the
-// seg 1x1 512 -> 19 153 -> 142 us (profiles/r9_x6_v5)
-int x6_auto_variant(const drnmi_conv_args& p) {
-  return p.cout % 256 == 0 ? 0 : p.cout % 128 == 0 ? 4 : p.cout <= 64 ? 5 : 2;
+static_assert(kBK == kX6BK, "the K step conv_route.cpp plans with");
+#define X6_ROW(...) \
+  ConvKernel { "conv_x6_kernel<" #__VA_ARGS__ ">", &launch_x6<__VA_ARGS__> }
+#define X6_VARIANT(WCO, WC, PS, STEP)                                                            \
+  {X6Cfg<WCO, WC, PS>::BCO, X6Cfg<WCO, WC, PS>::BPX, X6Cfg<WCO, WC, PS>::OCC, STEP,             \
+   {X6_ROW(1, WCO, WC, PS), X6_ROW(2, WCO, WC, PS), X6_ROW(3, WCO, WC, PS)}}
+const X6Variant& x6_variant(int v) {
+  static const X6Variant k[kNumX6] = {X6_VARIANT(128, 2, 4, 4.3e-6), X6_VARIANT(128, 1, 4, 3.6e-6), X6_VARIANT(64, 1, 4, 2.2e-6),
+                                      X6_VARIANT(64, 2, 4, 3.0e-6),  X6_VARIANT(64, 2, 2, 2.7e-6),  X6_VARIANT(32, 2, 2, 2.3e-6)};
+  return k[v];
 }
-
-int x6_num_cus() {
-  static int cus = 0;
-  if (cus == 0) {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess ||
-        hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0)
-      cus = 256;
-  }
-  return cus;
-}
-
-// Launch plan (variant, split-K count); split_ok: the launch has (drnmi_conv_args.ws) or is sizing
-// (drnmi_conv_workspace_bytes) a caller workspace.  Inference launches (none) take the auto variant
-// unsplit.  The fp32x training path (a workspace) picks among the 256- / 128-channel tiles
-// and S = 1..4 by a cost model: rounds of resident workgroups x K steps per workgroup x the
-// variant's step time, plus the split partials' HBM round trip (S x M x cout fp32 written and
-// read) and the output (+ residual) stream.  The default (auto variant, S = 1) is kept unless the
-// best plan is >= 5 % faster.  The model is within a few % of the SPLITS sweep (512 -> 512 d4 at
-// 2 x 128 x 96: 631 / 580 us modelled for S = 1 / 4, 627 / 580 measured).
-struct X6Plan { int v, S; };
-X6Plan x6_plan(const drnmi_conv_args& p, bool split_ok) {
-  // the partials are [split][m][cout] rows written as float4: only cout % 4 == 0 splits
-  if (p.cout % 4 != 0) split_ok = false;
-  if (p.tile >= 0) {
-    const int v = p.tile % kNumX6;
-    int S = p.tile / kNumX6;
-    if (!split_ok || S < 1) S = 1;
-    if (S > p.k_pad / kBK) S = p.k_pad / kBK;
-    return {v, S};
-  }
-  const int v0 = x6_auto_variant(p);
-  if (!split_ok) return {v0, 1};
-  const int cus = x6_num_cus();
-  const int64_t M = static_cast<int64_t>(p.n) * p.ho * p.wo;
-  const int nk = p.k_pad / kBK;
-  const double out_s = static_cast<double>(M) * p.cout * 4.0 * (p.res != nullptr ? 2 : 1) / 4.5e12;
-  auto cost = [&](int v, int S) {
-    const int64_t tiles = ((M + kX6Bpx[v] - 1) / kX6Bpx[v]) * ((p.cout + kX6Bco[v] - 1) / kX6Bco[v]);
-    const int64_t slots = static_cast<int64_t>(cus) * kX6Occ[v];
-    const int64_t rounds = (tiles * S + slots - 1) / slots;
-    double t = static_cast<double>(rounds) * ((nk + S - 1) / S) * kX6Step[v] + out_s;
-    if (S > 1) t += 2.0 * S * static_cast<double>(M) * p.cout * 4.0 / 4e12 + 4e-6;
-    return t;
-  };
-  const double c0 = cost(v0, 1);
-  X6Plan best{v0, 1};
-  double bc = c0;
-  // Only the auto variant's split counts: with the two-per-CU 128 x 128 tile as a candidate (<= two
-  // rounds of it) the plan moved 1/3 of the step's conv_x6 launches onto it and the step's conv_x6
-  // time did not move (19.52 -> 19.57 ms, profiles/r8_finetune/x6_plan_v4.txt); variant 4 stays a
-  // forced tile for A/B runs.
-  const int cands[1] = {v0};
-  for (int v : cands) {
-    if ((p.cout + kX6Bco[v] - 1) / kX6Bco[v] * kX6Bco[v] > p.cout_pad) continue;
-    for (int S = 1; S <= 4 && (S == 1 || nk / S >= 8); ++S) {
-      const int64_t tiles = ((M + kX6Bpx[v] - 1) / kX6Bpx[v]) * ((p.cout + kX6Bco[v] - 1) / kX6Bco[v]);
-      if (kX6Occ[v] == 2 && tiles * S > 2 * 2 * static_cast<int64_t>(cus)) continue;
-      const double c = cost(v, S);
-      if (c < 0.95 * c0 && c < bc) {
-        best = {v, S};
-        bc = c;
-      }
-    }
-  }
-  return best;
-}
-// the workspace a training launch of this geometry needs (its plan with splits allowed); a plan
-// that differs from the inference default without splitting asks for a token 256 B, since a
-// launch takes the training plan exactly when it is given a workspace
-int64_t x6_workspace_bytes(const drnmi_conv_args& p) {
-  const X6Plan pl = x6_plan(p, true);
-  if (pl.S > 1) return static_cast<int64_t>(pl.S) * p.n * p.ho * p.wo * p.cout * 4;
-  return pl.v != x6_plan(p, false).v ? 256 : 0;
-}
-
-}  // namespace
 
 bool x6_conv_supported(const drnmi_conv_args& p) {
   return p.dtype == DRNMI_F32X3 && p.out_dtype == DRNMI_F32 && p.cin >= kBK && (p.cin & (p.cin - 1)) == 0 &&
@@ -707,78 +626,6 @@ bool x6_conv_supported(const drnmi_conv_args& p) {
           // wider NHWC rows (the labels head's 20-float seg logits rows): 16-B aligned, no
           // residual (a residual is read with the output's own packed layout)
           (p.y_sp > p.cout && p.y_sp % 4 == 0 && p.y_sn % 4 == 0 && p.res == nullptr));
-}
-
-int64_t x6_conv_workspace_bytes(const drnmi_conv_args& p) {
-  return x6_conv_supported(p) ? x6_workspace_bytes(p) : 0;
-}
-
-// rows of BN-statistics partials a launch with these arguments writes (0: it cannot -- split K)
-int64_t x6_conv_stats_rows(const drnmi_conv_args& p) {
-  if (!x6_conv_supported(p)) return 0;
-  const X6Plan pl = x6_plan(p, p.ws != nullptr);
-  if (pl.S > 1) return 0;
-  const int64_t M = static_cast<int64_t>(p.n) * p.ho * p.wo;
-  return (M + kX6Bpx[pl.v] - 1) / kX6Bpx[pl.v] * (kX6Bpx[pl.v] / 64);
-}
-
-int x6_conv_dispatch(const drnmi_conv_args& p, hipStream_t s) {
-  if (!x6_conv_supported(p)) return DRNMI_ENOTSUP;
-  const X6Plan pl = x6_plan(p, p.ws != nullptr);
-  const int v = pl.v;
-  // every weight row a tile's DMA reads must exist in each plane
-  if ((p.cout + kX6Bco[v] - 1) / kX6Bco[v] * kX6Bco[v] > p.cout_pad) return DRNMI_EINVAL;
-  if (3 * static_cast<int64_t>(p.cout_pad) * p.k_pad >= (int64_t(1) << 31)) return DRNMI_EINVAL;
-  const int S = pl.S;
-  if (S > 1 && p.stats != nullptr) return DRNMI_EINVAL;   // statistics only from an unsplit launch
-  if (p.stats != nullptr && (reinterpret_cast<uintptr_t>(p.stats) & 7) != 0) return DRNMI_EINVAL;
-  if (S > 1 && p.ws_bytes < x6_workspace_bytes(p)) return DRNMI_EINVAL;
-  if (S > 1 && (reinterpret_cast<uintptr_t>(p.ws) & 15) != 0) return DRNMI_EINVAL;
-  hipError_t e;
-  if (p.ks == 2) {        // the 2x2 parity-class kernels of a stride-2 conv's data gradient
-    switch (v) {
-      case 0: e = launch_x6<2, 128, 2, 4>(p, S, s); break;
-      case 1: e = launch_x6<2, 128, 1, 4>(p, S, s); break;
-      case 2: e = launch_x6<2, 64, 1, 4>(p, S, s); break;
-      case 3: e = launch_x6<2, 64, 2, 4>(p, S, s); break;
-      case 4: e = launch_x6<2, 64, 2, 2>(p, S, s); break;
-      default: e = launch_x6<2, 32, 2, 2>(p, S, s); break;
-    }
-  } else if (p.ks == 3) {
-    switch (v) {
-      case 0: e = launch_x6<3, 128, 2, 4>(p, S, s); break;
-      case 1: e = launch_x6<3, 128, 1, 4>(p, S, s); break;
-      case 2: e = launch_x6<3, 64, 1, 4>(p, S, s); break;
-      case 3: e = launch_x6<3, 64, 2, 4>(p, S, s); break;
-      case 4: e = launch_x6<3, 64, 2, 2>(p, S, s); break;
-      default: e = launch_x6<3, 32, 2, 2>(p, S, s); break;
-    }
-  } else {
-    switch (v) {
-      case 0: e = launch_x6<1, 128, 2, 4>(p, S, s); break;
-      case 1: e = launch_x6<1, 128, 1, 4>(p, S, s); break;
-      case 2: e = launch_x6<1, 64, 1, 4>(p, S, s); break;
-      case 3: e = launch_x6<1, 64, 2, 4>(p, S, s); break;
-      case 4: e = launch_x6<1, 64, 2, 2>(p, S, s); break;
-      default: e = launch_x6<1, 32, 2, 2>(p, S, s); break;
-    }
-  }
-  return static_cast<int>(e);
-}
-
-const char* x6_conv_name(const drnmi_conv_args& p) {
-  if (!x6_conv_supported(p)) return nullptr;
-  static const char* n3[kNumX6] = {"conv_x6_kernel<3, 128, 2, 4>", "conv_x6_kernel<3, 128, 1, 4>",
-                                   "conv_x6_kernel<3, 64, 1, 4>", "conv_x6_kernel<3, 64, 2, 4>",
-                                   "conv_x6_kernel<3, 64, 2, 2>", "conv_x6_kernel<3, 32, 2, 2>"};
-  static const char* n1[kNumX6] = {"conv_x6_kernel<1, 128, 2, 4>", "conv_x6_kernel<1, 128, 1, 4>",
-                                   "conv_x6_kernel<1, 64, 1, 4>", "conv_x6_kernel<1, 64, 2, 4>",
-                                   "conv_x6_kernel<1, 64, 2, 2>", "conv_x6_kernel<1, 32, 2, 2>"};
-  static const char* n2[kNumX6] = {"conv_x6_kernel<2, 128, 2, 4>", "conv_x6_kernel<2, 128, 1, 4>",
-                                   "conv_x6_kernel<2, 64, 1, 4>", "conv_x6_kernel<2, 64, 2, 4>",
-                                   "conv_x6_kernel<2, 64, 2, 2>", "conv_x6_kernel<2, 32, 2, 2>"};
-  const int v = x6_plan(p, p.ws != nullptr).v;
-  return p.ks == 3 ? n3[v] : p.ks == 2 ? n2[v] : n1[v];
 }
 
 }  // namespace drnmi

@@ -957,71 +957,40 @@ static bool stem_dma_ok(const drnmi_conv_args& p) {
          static_cast<int64_t>(p.n) * p.ho * p.wo * 16 * 2 < (int64_t(1) << 31) && p.pad == 3 && p.w >= 8;
 }
 
+#define PATCH_ROW(...) DRNMI_KERNEL_ROW(patch_conv_kernel, launch_patch, __VA_ARGS__)
+#define PATCH_DMA_ROW(...) DRNMI_KERNEL_ROW(patch_dma_kernel, launch_patch_dma, __VA_ARGS__)
+
 // fp32x (DRNMI_F32X3 in, fp32 NHWC out): the full-resolution small-channel layers
-static int patch_x6_dispatch(const drnmi_conv_args& p, hipStream_t s) {
-  if (p.out_dtype != DRNMI_F32 || p.dil != 1 || p.res != nullptr || p.y_sc != 1 || p.y_sp != p.cout)
-    return DRNMI_ENOTSUP;
-  hipError_t e;
-  if (p.src_u8) {
-    if (p.cin != 4 || p.cout != 16 || p.ks != 7 || p.stride != 1 || p.k != 224 || p.k_pad != 224)
-      return DRNMI_ENOTSUP;
-    e = launch_patch<4, 16, 7, 1, 4, 64, true, true>(p, s);
-  } else if (p.cin == 8 && p.cout == 16 && p.ks == 7 && p.stride == 1) {
-    e = launch_patch<8, 16, 7, 1, 4, 64, false, true>(p, s);
-  } else if (p.cin == 16 && p.cout == 16 && p.ks == 3 && p.stride == 1) {
-    e = launch_patch<16, 16, 3, 1, 4, 64, false, true>(p, s);
-  } else if (p.cin == 16 && p.cout == 32 && p.ks == 3 && p.stride == 2) {
-    e = launch_patch<16, 32, 3, 2, 4, 32, false, true>(p, s);
-  } else {
-    return DRNMI_ENOTSUP;
-  }
-  return static_cast<int>(e);
+static const ConvKernel* patch_x6_kernel(const drnmi_conv_args& p) {
+  static const ConvKernel stem_u8 = PATCH_ROW(4, 16, 7, 1, 4, 64, true, true), stem = PATCH_ROW(8, 16, 7, 1, 4, 64, false, true),
+                          c16 = PATCH_ROW(16, 16, 3, 1, 4, 64, false, true), c16s2 = PATCH_ROW(16, 32, 3, 2, 4, 32, false, true);
+  if (p.out_dtype != DRNMI_F32 || p.dil != 1 || p.res != nullptr || p.y_sc != 1 || p.y_sp != p.cout) return nullptr;
+  if (p.src_u8)
+    return p.cin != 4 || p.cout != 16 || p.ks != 7 || p.stride != 1 || p.k != 224 || p.k_pad != 224 ? nullptr : &stem_u8;
+  if (p.cin == 8 && p.cout == 16 && p.ks == 7 && p.stride == 1) return &stem;
+  if (p.cin == 16 && p.cout == 16 && p.ks == 3 && p.stride == 1) return &c16;
+  if (p.cin == 16 && p.cout == 32 && p.ks == 3 && p.stride == 2) return &c16s2;
+  return nullptr;
 }
 
-int patch_conv_dispatch(const drnmi_conv_args& p, hipStream_t s) {
-  if (p.dtype == DRNMI_F32X3) return patch_x6_dispatch(p, s);
-  if (p.dtype == DRNMI_F32) return patch_f32_dispatch(p, s);       // exact fp32 (patch_f32.hip)
-  if (p.dtype != DRNMI_BF16 || p.out_dtype != DRNMI_BF16 || p.dil != 1 || p.res != nullptr) return DRNMI_ENOTSUP;
-  if (p.y_sc != 1 || p.y_sp != p.cout) return DRNMI_ENOTSUP;            // packed NHWC output
-  hipError_t e;
+const ConvKernel* patch_kernel(const drnmi_conv_args& p) {
+  static const ConvKernel stem_dma{"stem_dma_kernel", &launch_unsplit<&launch_stem_dma>},
+                          stem_u8 = PATCH_ROW(4, 16, 7, 1, 4, 64, true), stem = PATCH_ROW(8, 16, 7, 1, 4, 64, false),
+                          c16_dma = PATCH_DMA_ROW(16, 16, 1, 4, 64), c16s2_dma = PATCH_DMA_ROW(16, 32, 2, 4, 32),
+                          c16 = PATCH_ROW(16, 16, 3, 1, 4, 64, false), c16s2 = PATCH_ROW(16, 32, 3, 2, 4, 64, false),
+                          c32s2 = PATCH_ROW(32, 64, 3, 2, 2, 64, false);
+  if (p.dtype == DRNMI_F32X3) return patch_x6_kernel(p);
+  if (p.dtype == DRNMI_F32) return patch_f32_kernel_row(p);       // exact fp32 (patch_f32.hip)
+  if (p.dtype != DRNMI_BF16 || p.out_dtype != DRNMI_BF16 || p.dil != 1 || p.res != nullptr) return nullptr;
+  if (p.y_sc != 1 || p.y_sp != p.cout) return nullptr;            // packed NHWC output
   if (p.src_u8) {
-    if (p.cin != 4 || p.cout != 16 || p.ks != 7 || p.stride != 1 || p.k != 224 || p.k_pad != 224)
-      return DRNMI_ENOTSUP;
-    e = stem_dma_ok(p) ? launch_stem_dma(p, s) : launch_patch<4, 16, 7, 1, 4, 64, true>(p, s);
-  } else if (p.cin == 8 && p.cout == 16 && p.ks == 7 && p.stride == 1) {
-    e = launch_patch<8, 16, 7, 1, 4, 64, false>(p, s);
-  } else if (p.cin == 16 && p.cout == 16 && p.ks == 3 && p.stride == 1 && dma_ok(p)) {
-    e = launch_patch_dma<16, 16, 1, 4, 64>(p, s);
-  } else if (p.cin == 16 && p.cout == 32 && p.ks == 3 && p.stride == 2 && dma_ok(p)) {
-    e = launch_patch_dma<16, 32, 2, 4, 32>(p, s);
-  } else if (p.cin == 16 && p.cout == 16 && p.ks == 3 && p.stride == 1) {
-    e = launch_patch<16, 16, 3, 1, 4, 64, false>(p, s);
-  } else if (p.cin == 16 && p.cout == 32 && p.ks == 3 && p.stride == 2) {
-    e = launch_patch<16, 32, 3, 2, 4, 64, false>(p, s);
-  } else if (p.cin == 32 && p.cout == 64 && p.ks == 3 && p.stride == 2) {
-    e = launch_patch<32, 64, 3, 2, 2, 64, false>(p, s);
-  } else {
-    return DRNMI_ENOTSUP;
+    if (p.cin != 4 || p.cout != 16 || p.ks != 7 || p.stride != 1 || p.k != 224 || p.k_pad != 224) return nullptr;
+    return stem_dma_ok(p) ? &stem_dma : &stem_u8;
   }
-  return static_cast<int>(e);
-}
-
-const char* patch_conv_name(const drnmi_conv_args& p) {
-  if (p.dtype == DRNMI_F32X3) {
-    if (p.src_u8) return "patch_conv_kernel<4, 16, 7, 1, 4, 64, true, true>";
-    if (p.cin == 8 && p.cout == 16 && p.ks == 7) return "patch_conv_kernel<8, 16, 7, 1, 4, 64, false, true>";
-    if (p.cin == 16 && p.cout == 16 && p.ks == 3) return "patch_conv_kernel<16, 16, 3, 1, 4, 64, false, true>";
-    if (p.cin == 16 && p.cout == 32 && p.ks == 3) return "patch_conv_kernel<16, 32, 3, 2, 4, 32, false, true>";
-    return nullptr;
-  }
-  if (p.dtype == DRNMI_F32) return patch_f32_name(p);
-  if (p.src_u8) return stem_dma_ok(p) ? "stem_dma_kernel" : "patch_conv_kernel<4, 16, 7, 1, 4, 64, true>";
-  if (p.cin == 8 && p.cout == 16 && p.ks == 7) return "patch_conv_kernel<8, 16, 7, 1, 4, 64, false>";
-  if (p.cin == 16 && p.cout == 16 && p.ks == 3 && p.stride == 1)
-    return dma_ok(p) ? "patch_dma_kernel<16, 16, 1, 4, 64>" : "patch_conv_kernel<16, 16, 3, 1, 4, 64, false>";
-  if (p.cin == 16 && p.cout == 32 && p.ks == 3 && p.stride == 2)
-    return dma_ok(p) ? "patch_dma_kernel<16, 32, 2, 4, 32>" : "patch_conv_kernel<16, 32, 3, 2, 4, 64, false>";
-  if (p.cin == 32 && p.cout == 64 && p.ks == 3 && p.stride == 2) return "patch_conv_kernel<32, 64, 3, 2, 2, 64, false>";
+  if (p.cin == 8 && p.cout == 16 && p.ks == 7 && p.stride == 1) return &stem;
+  if (p.cin == 16 && p.cout == 16 && p.ks == 3 && p.stride == 1) return dma_ok(p) ? &c16_dma : &c16;
+  if (p.cin == 16 && p.cout == 32 && p.ks == 3 && p.stride == 2) return dma_ok(p) ? &c16s2_dma : &c16s2;
+  if (p.cin == 32 && p.cout == 64 && p.ks == 3 && p.stride == 2) return &c32s2;
   return nullptr;
 }
 
@@ -1047,3 +1016,15 @@ int stem_l1_dispatch(const drnmi_conv_args& p, const drnmi_conv_args& q, hipStre
 }
 
 }  // namespace drnmi
+
+using namespace drnmi;
+
+extern "C" int drnmi_stem_layer1(const drnmi_conv_args* stem, const drnmi_conv_args* next, void* stream) {
+  if (stem == nullptr || next == nullptr) return DRNMI_EINVAL;
+  return stem_l1_dispatch(*stem, *next, reinterpret_cast<hipStream_t>(stream));
+}
+
+extern "C" const char* drnmi_stem_layer1_kernel_name(const drnmi_conv_args* stem, const drnmi_conv_args* next) {
+  if (stem == nullptr || next == nullptr || !stem_l1_ok(*stem, *next)) return nullptr;
+  return "stem_l1_kernel";
+}

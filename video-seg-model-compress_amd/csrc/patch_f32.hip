@@ -274,26 +274,13 @@ static int f32_shape(const drnmi_conv_args& p) {
   return -1;
 }
 
-int patch_f32_dispatch(const drnmi_conv_args& p, hipStream_t s) {
-  hipError_t e;
-  switch (f32_shape(p)) {
-    case 0: e = launch_patch_f32<0, 16, 7, 1, 4, 64>(p, s); break;
-    case 1: e = launch_patch_f32<1, 16, 7, 1, 4, 64>(p, s); break;
-    case 2: e = launch_patch_f32<2, 16, 3, 1, 4, 64>(p, s); break;
-    case 3: e = launch_patch_f32<2, 32, 3, 2, 4, 32>(p, s); break;
-    default: return DRNMI_ENOTSUP;
-  }
-  return static_cast<int>(e);
-}
-
-const char* patch_f32_name(const drnmi_conv_args& p) {
-  switch (f32_shape(p)) {
-    case 0: return "patch_f32_kernel<0, 16, 7, 1, 4, 64>";
-    case 1: return "patch_f32_kernel<1, 16, 7, 1, 4, 64>";
-    case 2: return "patch_f32_kernel<2, 16, 3, 1, 4, 64>";
-    case 3: return "patch_f32_kernel<2, 32, 3, 2, 4, 32>";
-    default: return nullptr;
-  }
+const ConvKernel* patch_f32_kernel_row(const drnmi_conv_args& p) {
+  static const ConvKernel k[4] = {DRNMI_KERNEL_ROW(patch_f32_kernel, launch_patch_f32, 0, 16, 7, 1, 4, 64),
+                                  DRNMI_KERNEL_ROW(patch_f32_kernel, launch_patch_f32, 1, 16, 7, 1, 4, 64),
+                                  DRNMI_KERNEL_ROW(patch_f32_kernel, launch_patch_f32, 2, 16, 3, 1, 4, 64),
+                                  DRNMI_KERNEL_ROW(patch_f32_kernel, launch_patch_f32, 2, 32, 3, 2, 4, 32)};
+  const int shape = f32_shape(p);
+  return shape < 0 ? nullptr : &k[shape];
 }
 
 }  // namespace drnmi

@@ -12,6 +12,9 @@ from .build import LIB_PATH
 
 DRNMI_F32, DRNMI_BF16, DRNMI_U8, DRNMI_I64, DRNMI_I8, DRNMI_F32X3 = 0, 1, 2, 3, 4, 5
 ALGO_IGEMM, ALGO_PATCH = 0, 1
+# include/drnmi.h enum drnmi_tile: the ids tests and micro-benchmarks force
+TILE_AUTO, TILE_DMA128, TILE_PP256, TILE_HALO, TILE_STRIP, TILE_STAG = -1, 4, 16, 17, 18, 19
+TILE_S2ROW, TILE_S1X2ROW, TILE_W1, TILE_W1H = 20, 21, 22, 23
 HIST_BINS = 32768        # include/drnmi.h DRNMI_HIST_BINS
 
 _STATUS = {-1: "DRNMI_EINVAL (bad shape/stride/dtype)", -2: "DRNMI_ENOTSUP (no kernel for this config)"}
@@ -70,6 +73,7 @@ class WgradArgs(ctypes.Structure):
 _VP, _I32, _I64, _F32 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_float
 SIGNATURES = {
     "drnmi_conv2d_bn_act": (ctypes.c_int, [ctypes.POINTER(ConvArgs), _VP]),
+    "drnmi_conv_status": (ctypes.c_int, [ctypes.POINTER(ConvArgs)]),
     "drnmi_conv_tile_name": (ctypes.c_char_p, [ctypes.c_int]),
     "drnmi_conv_kernel_name": (ctypes.c_char_p, [ctypes.POINTER(ConvArgs)]),
     "drnmi_stem_layer1": (ctypes.c_int, [ctypes.POINTER(ConvArgs), ctypes.POINTER(ConvArgs), _VP]),

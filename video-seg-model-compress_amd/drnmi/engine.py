@@ -528,47 +528,40 @@ FUSE_FRONT = True
 FUSE_BLOCK64 = True
 
 
-def _route_name(nd: ConvNode, cin_stride: int, cin2: int = 0, k_pad: int | None = None) -> str:
-    """Kernel the bf16 launch of `nd` (optionally with a fused cin2-channel second input, weight
-    rows of k_pad columns) goes to, probed on a 16x16 map through drnmi_conv_kernel_name
-    (routing does not depend on size)."""
+def _probe_args(nd: ConvNode, cin_stride: int, k: int, k_pad: int) -> _lib.ConvArgs:
+    """drnmi_conv_args of the bf16 auto-routed launch of `nd` on a 16x16 map, data pointers NULL
+    (routing reads neither them nor the size): dense NHWC bf16 output, no scale."""
     c = nd.conv
     a = _lib.ConvArgs()
     a.n, a.h, a.w, a.cin = 1, 16, 16, cin_stride
     a.ks, a.stride, a.pad, a.dil = c.kernel_size[0], c.stride[0], c.padding[0], c.dilation[0]
     a.ho = _conv_out(16, a.ks, a.stride, a.pad, a.dil)
     a.wo = a.ho
-    a.cout, a.cout_pad = c.out_channels, nd.cout_pad
-    a.k = a.ks * a.ks * cin_stride + cin2
-    a.k_pad = a.k if k_pad is None else k_pad
+    a.cout, a.cout_pad, a.k, a.k_pad = c.out_channels, nd.cout_pad, k, k_pad
     a.dtype, a.out_dtype, a.y_sp, a.y_sc = _lib.DRNMI_BF16, _lib.DRNMI_BF16, c.out_channels, 1
-    a.scale = None
-    a.tile, a.algo = -1, _lib.ALGO_IGEMM
+    a.tile, a.algo = _lib.TILE_AUTO, _lib.ALGO_IGEMM
+    return a
+
+
+def _route_name(nd: ConvNode, cin_stride: int, cin2: int = 0, k_pad: int | None = None) -> str:
+    """Kernel the bf16 launch of `nd` (optionally with a fused cin2-channel second input, weight
+    rows of k_pad columns) goes to, probed through drnmi_conv_kernel_name."""
+    k = nd.conv.kernel_size[0] ** 2 * cin_stride + cin2
+    a = _probe_args(nd, cin_stride, k, k if k_pad is None else k_pad)
     if cin2:
-        a.x2, a.cin2, a.h2, a.w2, a.stride2 = 1, cin2, 16 * c.stride[0], 16 * c.stride[0], 1
+        a.x2, a.cin2, a.h2, a.w2, a.stride2 = 1, cin2, 16 * a.stride, 16 * a.stride, 1
     name = _lib.load().drnmi_conv_kernel_name(ctypes.byref(a))
     return name.decode() if name is not None else ""
 
 
 def _fused_init_route(nd: ConvNode, cin_stride: int) -> bool:
     """True when the bf16 launch of `nd` goes to conv_big / conv_pp / conv_halo (the kernels
-    that take scale = NULL and seed the accumulators with shift + residual).  Routing does not
-    depend on the spatial size, so a 16x16 probe decides it."""
+    that take scale = NULL and seed the accumulators with shift + residual)."""
     if _uses_patch(nd, cin_stride, "bf16"):
         return False
-    c = nd.conv
-    a = _lib.ConvArgs()
-    a.n, a.h, a.w, a.cin = 1, 16, 16, cin_stride
-    a.ks, a.stride, a.pad, a.dil = c.kernel_size[0], c.stride[0], c.padding[0], c.dilation[0]
-    a.ho = _conv_out(16, a.ks, a.stride, a.pad, a.dil)
-    a.wo = a.ho
-    a.cout, a.cout_pad, a.k, a.k_pad = c.out_channels, nd.cout_pad, nd.k, nd.k_pad
-    a.dtype = _lib.DRNMI_BF16
+    a = _probe_args(nd, cin_stride, nd.k, nd.k_pad)
     if nd.out_fp32_nchw:
         a.out_dtype, a.y_sp, a.y_sc = _lib.DRNMI_F32, 1, a.ho * a.wo
-    else:
-        a.out_dtype, a.y_sp, a.y_sc = _lib.DRNMI_BF16, c.out_channels, 1
-    a.tile, a.algo = -1, _lib.ALGO_IGEMM
     name = _lib.load().drnmi_conv_kernel_name(ctypes.byref(a))
     return name is not None and name.decode().startswith(("conv_big", "conv_pp", "conv_halo"))
 
