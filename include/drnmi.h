@@ -110,7 +110,11 @@ typedef struct drnmi_conv_args {
    * (the K range split over gridDim.y workgroups per tile, their partial sums land here and a
    * second kernel adds them in split order and applies the epilogue).  Size:
    * drnmi_conv_workspace_bytes (0 = the plan is the inference one: pass NULL).  ws = NULL keeps
-   * the inference plan (the inference engine's launches); other dtypes ignore it. */
+   * the inference plan (the inference engine's launches).  DRNMI_F32 launches of the implicit GEMM
+   * read only whether it is set: with one (any 16-B aligned pointer, nothing is written) a conv of
+   * K >= 1024 sums K in chains of 256 folded into a second fp32 accumulator, which keeps its
+   * error against float64 at that of a blocked fp32 sum; without, K is one fmaf chain, the order
+   * the fp32 inference parity is pinned in.  Other dtypes ignore it. */
   void* ws;
   int64_t ws_bytes;
   /* Optional train-mode BN statistics of the stored output (F32X3 conv_x6 launches that do not
@@ -589,6 +593,19 @@ int drnmi_conv_wgrad_f32(const drnmi_wgrad_args* args, void* stream);
  * bf16 split of dy and x, the six products above 2^-24 on the bf16 MFMA, fp32 accumulation);
  * same arguments, workspace and errors.  semantic_seg.py:166-230 backward. */
 int drnmi_conv_wgrad_f32x3(const drnmi_wgrad_args* args, void* stream);
+/* Host-only: the launch drnmi_conv_wgrad_f32 (x6 = 0) or drnmi_conv_wgrad_f32x3 (x6 = 1) makes for
+ * these arguments, from the launcher's own decision (no pointer is read, nothing runs).  kernel:
+ * DRNMI_WGRAD_*; splits: the pixel splits whose partials the reduce sums (wave splits for the direct
+ * kernel); pix_per_split: pixels per split, a multiple of 32 (the last split is ragged when
+ * n*ho*wo % pix_per_split != 0; unused by the direct kernel); reduce: 0 = one thread per output,
+ * 1 = the grouped reduce (>= 32 splits).  Out pointers may be NULL.  DRNMI_EINVAL on bad geometry. */
+#define DRNMI_WGRAD_F32 0     /* wgrad_kernel<false>: exact-f32 MFMA, 64 x 64 tile            */
+#define DRNMI_WGRAD_X6 1      /* wgrad_kernel<true>: split-bf16, 64 x 64 tile                 */
+#define DRNMI_WGRAD_BIG 2     /* wgrad_x6_big_kernel: split-bf16, 128 x 128 tile              */
+#define DRNMI_WGRAD_PRE 3     /* wgrad_dy_split_kernel + wgrad_x6_pre_kernel (K >= 1024)      */
+#define DRNMI_WGRAD_DIRECT 4  /* wgrad_x6_direct_kernel: cout <= 32, wo % 32 == 0             */
+int drnmi_conv_wgrad_plan(const drnmi_wgrad_args* args, int32_t x6, int32_t* kernel, int32_t* splits,
+                          int64_t* pix_per_split, int32_t* reduce);
 /* fp32 w[n] -> bf16 out[3][n] with w = out[0] + out[1] + out[2] exactly (round to nearest even at
  * each step): the three weight planes of a DRNMI_F32X3 launch. */
 int drnmi_split3_bf16(const float* w, int64_t n, void* out, void* stream);

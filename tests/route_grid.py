@@ -149,7 +149,11 @@ def _parts():
 
 def grid():
     parts = [build(d) for d in _parts()]
-    return np.concatenate([p[0] for p in parts]), np.concatenate([p[1] for p in parts])
+    # into zeroed memory: np.concatenate copies field by field and leaves the record's four padding
+    # bytes as it finds them, and digest() reads them
+    args = np.zeros(sum(len(p[0]) for p in parts), dtype=ARGS)
+    np.concatenate([p[0] for p in parts], out=args)
+    return args, np.concatenate([p[1] for p in parts])
 
 
 def digest(args, entry):

@@ -12,7 +12,12 @@
 // Both operands are register-staged into double-buffered LDS (one barrier per K-step)
 // and consumed by MFMA:
 //   bf16 mode: v_mfma_f32_16x16x32_bf16, fp32 accumulate (perf mode)
-//   fp32 mode: v_mfma_f32_16x16x4_f32 — an exact fp32 fmaf chain (parity mode)
+//   fp32 mode: v_mfma_f32_16x16x4_f32 — an exact fp32 fmaf chain (parity mode).  A launch given
+//     drnmi_conv_args.ws (the training plan: the fine-tune's forward and data-gradient convs) folds
+//     the chain into a second accumulator every 256 k (kFoldSteps) from K = 1024 on: one chain over
+//     K = 4608 erred up to 10 x a blocked fp32 sum against float64 (profiles/train_audit), the
+//     folded one ~1.5 x.  Inference launches (ws = NULL) and shorter K keep the single chain, bit
+//     for bit: the fp32 mode's labels are pinned against the reference in that order.
 // The per-lane K permutation (lane holds k = 8*(lane>>4) + j) is identical for A and B,
 // so one LDS image and one fragment read serve both MFMA shapes.
 //
@@ -28,6 +33,8 @@ namespace {
 
 constexpr int kBK = 32;
 constexpr int kThreads = 256;
+constexpr int kFoldSteps = 8;       // fp32 mode: K steps per chain before it is folded (256 k)
+constexpr int kFoldMinSteps = 32;   // ... in a training launch of at least this many K steps (K >= 1024)
 
 template <typename T>
 __device__ __forceinline__ void mma_step(f32x4& acc, const T* a, const T* b);
@@ -72,7 +79,7 @@ __device__ __forceinline__ int xcd_remap(int bid, int nwg) {
 }
 
 template <typename T, int BM, int BN, int WAVES_M, int WAVES_N, int KS>
-__global__ void __launch_bounds__(kThreads)
+__global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(sizeof(T) == 4 ? 2 : 1)))
 conv_igemm_kernel(const drnmi_conv_args p) {
   constexpr int PAD = sizeof(T) == 2 ? 8 : 4;  // breaks the power-of-two row stride
   constexpr int LDK = kBK + PAD;
@@ -191,7 +198,15 @@ conv_igemm_kernel(const drnmi_conv_args p) {
 #pragma unroll
     for (int j = 0; j < FN; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
 
+  constexpr bool kFold = sizeof(T) == 4;
+  f32x4 tot[kFold ? FM : 1][kFold ? FN : 1];
+#pragma unroll
+  for (int i = 0; i < (kFold ? FM : 1); ++i)
+#pragma unroll
+    for (int j = 0; j < (kFold ? FN : 1); ++j) tot[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+
   const int nk = p.k_pad / kBK;
+  const bool fold = kFold && p.ws != nullptr && nk >= kFoldMinSteps;
   load_tiles(0);
   store_tiles(0);
   __syncthreads();
@@ -211,6 +226,17 @@ conv_igemm_kernel(const drnmi_conv_args p) {
       for (int fn = 0; fn < FN; ++fn) {
         const T* bp = Bs + (wn * WTN + fn * 16 + frag_row) * LDK + frag_k;
         mma_step<T>(acc[fm][fn], ap, bp);
+      }
+    }
+    if constexpr (kFold) {
+      if (fold && (kt % kFoldSteps == kFoldSteps - 1 || !more)) {
+#pragma unroll
+        for (int fm = 0; fm < FM; ++fm)
+#pragma unroll
+          for (int fn = 0; fn < FN; ++fn) {
+            tot[fm][fn] += acc[fm][fn];
+            acc[fm][fn] = more ? f32x4{0.f, 0.f, 0.f, 0.f} : tot[fm][fn];
+          }
       }
     }
     if (more) store_tiles(cur ^ 1);

@@ -2122,6 +2122,53 @@ extern "C" int64_t drnmi_conv_wgrad_workspace_bytes(const drnmi_wgrad_args* a) {
   return wgrad_partials_bytes(*a, splits) + pre;
 }
 
+// The one launch decision of a weight gradient: wgrad_launch runs it and drnmi_conv_wgrad_plan
+// reports it.  kernel: DRNMI_WGRAD_* (include/drnmi.h); full_splits: the split count whose
+// partials precede the dy planes of the pre kernel in the workspace.
+struct WgradRoute {
+  int kernel;
+  int splits;
+  int64_t per;
+  int reduce;        // 0 wgrad_reduce_kernel, 1 wgrad_reduce_grouped_kernel
+  int full_splits;
+};
+static WgradRoute wgrad_route(const drnmi_wgrad_args& a, bool x6) {
+  WgradRoute r{};
+  const bool big = x6 && wgrad_big_ok(a);
+  wgrad_plan(a, big, &r.splits, &r.per);
+  if (x6 && !big && wgrad_direct_ok(a)) {
+    r.kernel = DRNMI_WGRAD_DIRECT;
+    r.splits = wgrad_direct_splits(a);
+  } else if (big && wgrad_pre_ok(a)) {
+    r.kernel = DRNMI_WGRAD_PRE;
+    int64_t per;
+    wgrad_plan(a, false, &r.full_splits, &per);
+    int s2;
+    wgrad_plan(a, true, &s2, &per);
+    if (s2 > r.full_splits) r.full_splits = s2;
+  } else if (big) {
+    r.kernel = DRNMI_WGRAD_BIG;
+  } else {
+    r.kernel = x6 ? DRNMI_WGRAD_X6 : DRNMI_WGRAD_F32;
+  }
+  const int64_t total = static_cast<int64_t>(a.cout) * a.ks * a.ks * a.cin_stride;
+  // the grouped form where one thread per output would leave the chip mostly idle on a long chain
+  r.reduce = (r.splits >= 4 * kRedGrp && total <= 2048 * kThreads) ? 1 : 0;
+  return r;
+}
+
+extern "C" int drnmi_conv_wgrad_plan(const drnmi_wgrad_args* a, int32_t x6, int32_t* kernel, int32_t* splits,
+                                     int64_t* pix_per_split, int32_t* reduce) {
+  const int rc = wgrad_check(a);
+  if (rc != DRNMI_OK) return rc;
+  const WgradRoute r = wgrad_route(*a, x6 != 0);
+  if (kernel != nullptr) *kernel = r.kernel;
+  if (splits != nullptr) *splits = r.splits;
+  if (pix_per_split != nullptr) *pix_per_split = r.per;
+  if (reduce != nullptr) *reduce = r.reduce;
+  return DRNMI_OK;
+}
+
 static int wgrad_launch(const drnmi_wgrad_args* a, bool x6, void* stream) {
   const int rc = wgrad_check(a);
   if (rc != DRNMI_OK) return rc;
@@ -2143,37 +2190,29 @@ static int wgrad_launch(const drnmi_wgrad_args* a, bool x6, void* stream) {
   p.ho = a->ho; p.wo = a->wo; p.ks = a->ks; p.stride = a->stride; p.pad = a->pad; p.dil = a->dil;
   p.K = a->ks * a->ks * a->cin_stride;
   p.M = static_cast<int64_t>(a->n) * a->ho * a->wo;
-  const bool big = x6 && wgrad_big_ok(*a);
-  int splits;
-  wgrad_plan(*a, big, &splits, &p.pix_per_split);
+  const WgradRoute r = wgrad_route(*a, x6);
+  const int splits = r.splits;
+  p.pix_per_split = r.per;
   const dim3 grid((p.K + kWT - 1) / kWT, (a->cout + kWT - 1) / kWT, splits);
-  if (x6 && !big && wgrad_direct_ok(*a)) {
-    splits = wgrad_direct_splits(*a);
+  const dim3 g2((p.K + kWT2 - 1) / kWT2, (a->cout + kWT2 - 1) / kWT2, splits);
+  if (r.kernel == DRNMI_WGRAD_DIRECT) {
     const dim3 gd(static_cast<unsigned>(wgrad_direct_tiles(*a)), static_cast<unsigned>(splits / 4));
     if (a->cout <= 16) hipLaunchKernelGGL(wgrad_x6_direct_kernel<1>, gd, dim3(kThreads), 0, s, p, a->cin);
     else hipLaunchKernelGGL(wgrad_x6_direct_kernel<2>, gd, dim3(kThreads), 0, s, p, a->cin);
-  } else if (big && wgrad_pre_ok(*a)) {
+  } else if (r.kernel == DRNMI_WGRAD_PRE) {
     WgradPreP q{};
     q.p = p;
     q.Mp = (p.M + kWM - 1) / kWM * kWM;
     q.Cp = (a->cout + kPreRows - 1) / kPreRows * kPreRows;
-    int full_splits;
-    int64_t per;
-    wgrad_plan(*a, false, &full_splits, &per);
-    int s2;
-    wgrad_plan(*a, true, &s2, &per);
-    if (s2 > full_splits) full_splits = s2;
-    bf16_t* dyt = reinterpret_cast<bf16_t*>(reinterpret_cast<char*>(a->ws) + wgrad_partials_bytes(*a, full_splits));
+    bf16_t* dyt = reinterpret_cast<bf16_t*>(reinterpret_cast<char*>(a->ws) + wgrad_partials_bytes(*a, r.full_splits));
     q.dyt = dyt;
     const int64_t blocks = (q.Mp / 32) * (q.Cp / 64);
     hipLaunchKernelGGL(wgrad_dy_split_kernel, dim3(static_cast<unsigned>(blocks < 8192 ? blocks : 8192)), dim3(kThreads),
                        0, s, a->dy, a->dy_stride, a->cout, p.M, q.Mp, q.Cp, dyt);
-    const dim3 g2((p.K + kWT2 - 1) / kWT2, (a->cout + kWT2 - 1) / kWT2, splits);
     hipLaunchKernelGGL(wgrad_x6_pre_kernel, g2, dim3(kThreads), 0, s, q);
-  } else if (big) {
-    const dim3 g2((p.K + kWT2 - 1) / kWT2, (a->cout + kWT2 - 1) / kWT2, splits);
+  } else if (r.kernel == DRNMI_WGRAD_BIG) {
     hipLaunchKernelGGL(wgrad_x6_big_kernel, g2, dim3(kThreads), 0, s, p);
-  } else if (x6) {
+  } else if (r.kernel == DRNMI_WGRAD_X6) {
     hipLaunchKernelGGL(wgrad_kernel<true>, grid, dim3(kThreads), 0, s, p);
   } else {
     hipLaunchKernelGGL(wgrad_kernel<false>, grid, dim3(kThreads), 0, s, p);
@@ -2181,8 +2220,7 @@ static int wgrad_launch(const drnmi_wgrad_args* a, bool x6, void* stream) {
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return static_cast<int>(e);
   const int64_t total = static_cast<int64_t>(a->cout) * p.K;
-  // the grouped form where one thread per output would leave the chip mostly idle on a long chain
-  if (splits >= 4 * kRedGrp && total <= 2048 * kThreads)
+  if (r.reduce)
     hipLaunchKernelGGL(wgrad_reduce_grouped_kernel, dim3(static_cast<unsigned>((total + kRedOut - 1) / kRedOut)),
                        dim3(kThreads), 0, s, p.ws, splits, a->cout, a->cin, a->cin_stride, a->ks, p.K, a->dw,
                        a->accumulate);

@@ -122,6 +122,9 @@ SIGNATURES = {
     "drnmi_bn_stats_partials_f32": (ctypes.c_int, [_VP, _I64, _I64, _I32, _F32, _F32, _VP, _VP, _VP, _VP, _VP, _VP]),
     "drnmi_conv_wgrad_f32": (ctypes.c_int, [ctypes.POINTER(WgradArgs), _VP]),
     "drnmi_conv_wgrad_f32x3": (ctypes.c_int, [ctypes.POINTER(WgradArgs), _VP]),
+    "drnmi_conv_wgrad_plan": (ctypes.c_int, [ctypes.POINTER(WgradArgs), _I32, ctypes.POINTER(ctypes.c_int32),
+                                             ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int64),
+                                             ctypes.POINTER(ctypes.c_int32)]),
     "drnmi_split3_bf16": (ctypes.c_int, [_VP, ctypes.c_int64, _VP, _VP]),
     "drnmi_zero_insert_f32": (ctypes.c_int, [_VP, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _VP, _VP]),
     "drnmi_up8_lsm_bwd_f32": (ctypes.c_int, [_VP, _VP, _VP, _VP, _F32, _I32, _I32, _I32, _I32, _VP, _VP, _VP]),
@@ -147,6 +150,20 @@ SIGNATURES = {
     "drnmi_pack_table_check": (ctypes.c_int, [_VP, _I32, ctypes.POINTER(ctypes.c_int64)]),
     "drnmi_pack_conv_weights_batched": (ctypes.c_int, [_VP, _I32, _I64, _VP]),
 }
+WGRAD_KERNELS = ("wgrad_kernel<false>", "wgrad_kernel<true>", "wgrad_x6_big_kernel", "wgrad_x6_pre_kernel",
+                 "wgrad_x6_direct_kernel")      # DRNMI_WGRAD_* of drnmi_conv_wgrad_plan
+WGRAD_REDUCES = ("wgrad_reduce_kernel", "wgrad_reduce_grouped_kernel")
+
+
+def wgrad_plan(args: "WgradArgs", x6: bool):
+    """drnmi_conv_wgrad_plan as (kernel name, splits, pix_per_split, reduce kernel name)."""
+    k, s, r = ctypes.c_int32(), ctypes.c_int32(), ctypes.c_int32()
+    per = ctypes.c_int64()
+    check(load().drnmi_conv_wgrad_plan(ctypes.byref(args), 1 if x6 else 0, ctypes.byref(k), ctypes.byref(s),
+                                       ctypes.byref(per), ctypes.byref(r)), "wgrad plan")
+    return WGRAD_KERNELS[k.value], s.value, per.value, WGRAD_REDUCES[r.value]
+
+
 ABI_VERSION = 5          # include/drnmi.h DRNMI_ABI_VERSION
 
 _lib = None

@@ -90,7 +90,11 @@ class TrainRunner:
         self.grad_scale = 1.0           # multiplies dL/dlogprobs (DDP averaging: 1 / world_size)
         self._flat = None               # flat gradient buffer (views = param.grad)
         self._flat_params = None
-        self.debug_value_grads = None   # dict -> filled with {value: NHWC grad clone} (diagnostics)
+        # diagnostics: record(kind, node name, dict) after every launch of forward / backward, with
+        # what the launch read and wrote (tensors the step overwrites or frees are cloned on the
+        # stream first).  None: no clone, no query, no synchronisation -- the step is unchanged.
+        self.record = None
+        self._last_conv = None
         # batched re-pack (drnmi_pack_conv_weights_batched): after the first step has allocated every
         # packed buffer, each forward re-packs all forward and dgrad weights (+ fp32x planes) in one
         # launch instead of ~4 launches per layer; the table is rebuilt when a buffer moves
@@ -113,6 +117,13 @@ class TrainRunner:
         if self._zeros is None or self._zeros.numel() < n:
             self._zeros = torch.zeros(max(n, 4096), dtype=torch.float32, device=device)
         return self._zeros
+
+    def _rec(self, kind, name, **items):
+        self.record(kind, name, items)
+
+    @staticmethod
+    def _snap(t):
+        return None if t is None else t.detach().clone()
 
     def ordered_params(self):
         """Parameters in the order backward finishes them (seg first, then nodes reversed)."""
@@ -315,18 +326,27 @@ class TrainRunner:
             a.dtype = _lib.DRNMI_F32X3           # fp32x: conv_x6 (fp32 in/out, bf16 weight planes)
         a.tile, a.algo = -1, algo
         lib = _lib.load()
+        nb = 0
         if wx is not None and algo == _lib.ALGO_IGEMM and split and X6_SPLIT_K:
             # split-K scratch for the launches whose tiles would leave CUs idle (the 1/8-res layers)
             nb = lib.drnmi_conv_workspace_bytes(ctypes.byref(a))
             if nb > 0:
                 ws = self._ws("_cv_ws", nb, y.device)
                 a.ws, a.ws_bytes = ws.data_ptr(), ws.numel()
+        if wx is None and algo == _lib.ALGO_IGEMM:
+            # exact fp32: a workspace marks the training plan (long K summed in folded chains); unused
+            ws = self._ws("_cv_ws", 256, y.device)
+            a.ws, a.ws_bytes = ws.data_ptr(), ws.numel()
         rows = 0
         if want_stats and wx is not None and algo == _lib.ALGO_IGEMM:
             rows = lib.drnmi_conv_stats_rows(ctypes.byref(a))
             if rows > 0:
                 a.stats = self._ws("_st_ws", 2 * rows * cout * 8, y.device).data_ptr()
         _lib.check(lib.drnmi_conv2d_bn_act(ctypes.byref(a), ctypes.c_void_p(stream)), what)
+        if self.record is not None:
+            kn = lib.drnmi_conv_kernel_name(ctypes.byref(a))
+            self._last_conv = {"kernel": kn.decode() if kn else None, "x3": wx is not None,
+                               "split_k": max(1, nb // (4 * n * ho * wo * cout)) if nb > 0 else 1}
         return max(rows, 0)
 
     # ------------------------------------------------------------------ forward
@@ -361,6 +381,8 @@ class TrainRunner:
                            logits, (cout * oh * ow, 1, oh * ow), st.shift, None, n, oh, ow, stream, nd.name, st.wfx)
                 vals[nd.dst] = logits
                 per_node.append(None)
+                if self.record is not None:
+                    self._rec("conv", nd.name, x=vals[nd.src], y=logits, **self._last_conv)
                 continue
             cs = self.cstride[nd.dst]
             if cs != cout:
@@ -376,6 +398,9 @@ class TrainRunner:
                                 _lib.ALGO_PATCH if st.patch else _lib.ALGO_IGEMM, want_stats=FUSED_BN_STATS)
             mean = torch.empty(cs, dtype=torch.float32, device=dev)
             invstd = torch.empty(cs, dtype=torch.float32, device=dev)
+            if self.record is not None:
+                self._rec("conv", nd.name, x=vals[nd.src], y=y, **self._last_conv)
+                run0 = [self._snap(b) for b in (bn.running_mean, bn.running_var, bn.num_batches_tracked)]
             if g_rows > 0:
                 # the epilogue wrote [2][g_rows][cout] partials (row stride = cout); cs == cout here
                 # (checked above), so the finalize reads them with the same channel count
@@ -398,6 +423,11 @@ class TrainRunner:
                                             ctypes.c_void_p(stream)), f"bn_act {nd.name}")
             vals[nd.dst] = z
             per_node.append((y, mean, invstd) if save else None)
+            if self.record is not None:
+                run1 = [self._snap(b) for b in (bn.running_mean, bn.running_var, bn.num_batches_tracked)]
+                self._rec("bn_stats", nd.name, y=y, mean=mean, invstd=invstd, fused=g_rows > 0, before=run0,
+                          after=run1)
+                self._rec("bn_act", nd.name, y=y, mean=mean, invstd=invstd, res=res, z=z)
         lh, lw = shapes["logits"]
         logprobs = torch.empty(n, logits.shape[1], 8 * lh, 8 * lw, dtype=torch.float32, device=dev)
         if self.model.use_torch_up:      # UpsamplingBilinear2d(8) head (lmodels/drnseg.py:285-287)
@@ -410,6 +440,8 @@ class TrainRunner:
             _lib.check(lib.drnmi_up8_logsoftmax_argmax(logits.data_ptr(), up.data_ptr(), logprobs.data_ptr(), None,
                                                        _lib.DRNMI_U8, n, logits.shape[1], lh, lw,
                                                        ctypes.c_void_p(stream)), "up8_logsoftmax")
+        if self.record is not None:
+            self._rec("head", None, logits=logits, logprobs=logprobs, up=up)
         saved = None
         if save:
             saved = {"vals": vals, "shapes": shapes, "nodes": per_node, "n": n, "up": up}
@@ -439,6 +471,9 @@ class TrainRunner:
                                                  _vp(saved["up"]), float(self.grad_scale), n, ncls, lh, lw, _vp(du),
                                                  _vp(dlog), sp), "up8_lsm_bwd")
         del du
+        if self.record is not None:
+            self._rec("head_bwd", None, g_lp=glp, g_logits=glg, logprobs=logprobs, up=saved["up"],
+                      grad_scale=float(self.grad_scale), dlog=self._snap(dlog))
         grads = {}          # value -> NHWC fp32 gradient buffer
         for idx in range(len(self.nodes) - 1, -1, -1):
             nd, st = self.nodes[idx], self.state[idx]
@@ -454,18 +489,22 @@ class TrainRunner:
                 dy = torch.empty(rows, dys, dtype=torch.float32, device=dev)
                 _lib.check(lib.drnmi_nchw_to_nhwc(dlog.data_ptr(), dy.data_ptr(), n, cout, oh, ow, dys, F32, sp),
                            "seg grad nhwc")
+                if self.record is not None:
+                    dy_rec = self._snap(dy)
+                    self._rec("seg_nhwc", nd.name, dlog=self._snap(dlog), dy=dy_rec)
                 if c.bias is not None and c.bias.requires_grad:
                     ws = self._ws("_red_ws", lib.drnmi_reduce_workspace_bytes(rows, dys), dev)
+                    before = self._snap(c.bias.grad) if self.record is not None and acc[id(c.bias)] else None
                     _lib.check(lib.drnmi_channel_sum_f32(_vp(dy), rows, dys, cout, _vp(c.bias.grad),
                                                          1 if acc[id(c.bias)] else 0, _vp(ws), sp), "seg bias grad")
                     done.append(c.bias)
+                    if self.record is not None:
+                        self._rec("bias_grad", nd.name, dy=dy_rec, before=before, after=self._snap(c.bias.grad))
             else:
                 dys = self.cstride[nd.dst]
                 dz = grads.pop(nd.dst, None)
                 if dz is None:
                     raise RuntimeError(f"no gradient reached {nd.name}")
-                if self.debug_value_grads is not None:
-                    self.debug_value_grads[nd.dst] = dz.detach().clone()
                 y, mean, invstd = saved["nodes"][idx]
                 z = vals[nd.dst]
                 bn = nd.bn
@@ -481,6 +520,10 @@ class TrainRunner:
                 gw, gb = bn.weight, bn.bias
                 ws = self._ws("_red_ws", lib.drnmi_reduce_workspace_bytes(rows, dys), dev)
                 gacc = 1 if (gw.requires_grad and acc[id(gw)]) else 0
+                if self.record is not None:
+                    bn0 = dict(dz=self._snap(dz), dres_before=self._snap(dres) if dres_acc else None,
+                               dgamma_before=self._snap(gw.grad) if gacc else None,
+                               dbeta_before=self._snap(gb.grad) if gacc and gb.requires_grad else None)
                 if nd.relu and not nd.res:
                     # residual-free BN + ReLU: the mask is recomputed from y (z is not read)
                     _lib.check(lib.drnmi_bn_relu_bwd_y_f32(
@@ -497,6 +540,12 @@ class TrainRunner:
                     raise RuntimeError("BN weight/bias grads must be both set or both None")
                 done += [q for q in (gw, gb) if q.requires_grad]
                 dy = dz
+                if self.record is not None:
+                    dy_rec = self._snap(dy)
+                    self._rec("bn_bwd", nd.name, z=z, y=y, mean=mean, invstd=invstd, dy=dy_rec, dres=self._snap(dres),
+                              dgamma=self._snap(gw.grad) if gw.requires_grad else None,
+                              dbeta=self._snap(gb.grad) if gb.requires_grad else None,
+                              from_y=bool(nd.relu and not nd.res), **bn0)
             # weight gradient
             if c.weight.requires_grad:
                 wa = _lib.WgradArgs()
@@ -515,8 +564,12 @@ class TrainRunner:
                 ws = self._ws("_wg_ws", nb, dev)
                 wa.ws, wa.ws_bytes = ws.data_ptr(), ws.numel()
                 wg = lib.drnmi_conv_wgrad_f32x3 if x3 else lib.drnmi_conv_wgrad_f32
+                before = self._snap(c.weight.grad) if self.record is not None and wa.accumulate else None
                 _lib.check(wg(ctypes.byref(wa), sp), f"wgrad {nd.name}")
                 done.append(c.weight)
+                if self.record is not None:
+                    self._rec("wgrad", nd.name, dy=dy_rec, x=vals[nd.src], before=before,
+                              after=self._snap(c.weight.grad), x3=x3, plan=_lib.wgrad_plan(wa, x3))
             if self.grad_ready is not None and done:
                 self.grad_ready(done)
             # data gradient (not needed for the network input)
@@ -533,16 +586,21 @@ class TrainRunner:
                 else:
                     out = torch.empty(n * ih * iw, cs_src, dtype=torch.float32, device=dev)
                 flat = out.view(-1)
+                fill = "prev" if prev is not None else "zeros" if len(classes) < 4 else "empty"
                 for (a_, b_, ksc, planes) in classes:
                     ho_c, wo_c = (ih - a_ + 1) // 2, (iw - b_ + 1) // 2
                     if ho_c <= 0 or wo_c <= 0:
                         continue
                     base = (a_ * iw + b_) * cs_src
                     view = flat[base:]
+                    before = self._snap(out) if self.record is not None else None
                     self._conv(dy, dys, oh, ow, None, ksc * ksc * dys, ksc * ksc * dys, st.rows_d, cin, ksc, 1, 0,
                                1, view, (ih * iw * cs_src, 2 * cs_src, 1), self._zeros_f32(st.rows_d, dev),
                                view if prev is not None else None, n, ho_c, wo_c, stream,
                                f"dgrad {nd.name} class {a_}{b_}", planes, y_sr=2 * iw * cs_src, split=False)
+                    if self.record is not None:
+                        self._rec("dgrad", nd.name, form="class", cls=(a_, b_), fill=fill, dy=dy_rec, before=before,
+                                  after=self._snap(out), **self._last_conv)
                 grads[nd.src] = out
             elif nd.src != "input":
                 dys_d = self._pack_dgrad(nd, st, dev, sp)
@@ -559,10 +617,15 @@ class TrainRunner:
                 prev = grads.get(nd.src)
                 out = prev if prev is not None else torch.empty(n * ih * iw, cs_src, dtype=torch.float32, device=dev)
                 patch = st.dpatch and prev is None       # the patch kernels take no residual
+                before = self._snap(prev) if self.record is not None else None
                 self._conv(src, dys, hu, wu, st.wd, st.kd, st.kd_pad, st.rows_d, cin, ks, 1, pad_d, d, out,
                            (ih * iw * cs_src, cs_src, 1), self._zeros_f32(st.rows_d, dev), prev, n, ih, iw,
                            stream, f"dgrad {nd.name}", st.wdx if (patch or not st.dpatch) else None,
                            _lib.ALGO_PATCH if patch else _lib.ALGO_IGEMM)
+                if self.record is not None:
+                    self._rec("dgrad", nd.name, form="zero_insert" if s > 1 else "s1", cls=None,
+                              fill="prev" if prev is not None else "empty", dy=dy_rec, before=before,
+                              after=self._snap(out), **self._last_conv)
                 grads[nd.src] = out
             del dy
 
