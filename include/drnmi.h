@@ -250,6 +250,21 @@ int drnmi_basic_block64(const void* x, const void* pack, void* y, int32_t n, int
 int drnmi_video_front_u8(const uint8_t* frames, const void* pack, void* y, int32_t n, int32_t h, int32_t w,
                          void* stream);
 
+/* Fused 16-channel BasicBlock (lmodels/drn.py:49-65 with inplanes = planes = 16, stride 1, dilation 1,
+ * no downsample: DRN-C layer1, lmodels/drn.py:127-128):
+ *   y = relu(bn2(conv3x3(relu(bn1(conv3x3(x))))) + x), bf16 NHWC [n][h][w][16] in and out, eval BN
+ *   (scale folded into the weights, shift added; fp32 accumulation; the intermediate rounded to bf16).
+ * The intermediate never reaches HBM (csrc/block16.hip).  `pack`: device copy of the blob that the
+ * HOST function drnmi_block16_pack(w1, scale1, shift1, w2, scale2, shift2, out) builds from the two
+ * convs' OIHW fp32 weights [16][16][3][3] and per-channel BN scale / shift (fp32 [16] each);
+ * drnmi_block16_pack_bytes() bytes.  drnmi_block16_supported: n, h, w >= 1 and n * h * w * 32 < 2^31.
+ * x and y must not alias.  Arguments are validated before any HIP call. */
+int64_t drnmi_block16_pack_bytes(void);
+int drnmi_block16_pack(const float* w1, const float* scale1, const float* shift1, const float* w2,
+                       const float* scale2, const float* shift2, void* out_host);
+int drnmi_block16_supported(int32_t n, int32_t h, int32_t w);
+int drnmi_basic_block16(const void* x, const void* pack, void* y, int32_t n, int32_t h, int32_t w, void* stream);
+
 /* Block-sparsity map of packed weights [rows_pad][k_pad] (dtype F32 or BF16): one bit per
  * 16-row x 32-column unit, bit = 1 iff any element of the unit is nonzero (+-0 count as zero);
  * layout: row-block rb owns words [rb*W, rb*W + W), W = ceil(k_pad / 32 / 32), unit ku at bit

@@ -4,7 +4,8 @@ Reference API (kept): semantic_seg.py:126-164 / lmodels/drnseg.py:268-305
   DRNSeg(model_name, classes, pretrained_model=None, pretrained=True, use_torch_up=False)
   forward(x: fp32 [B,3,H,W]) -> (log_probs fp32 [B,C,8h,8w], logits fp32 [B,C,h,w])
   optim_parameters()  -> layer + seg params (up excluded)
-  state_dict keys     layer.{0..8}.*, seg.weight, seg.bias, up.weight
+  state_dict keys     layer.{0..8}.*, seg.weight, seg.bias, up.weight  (DRN-C, drn_c_26 / 42 / 58:
+                      layer.0.weight, layer.1.*, layer.{3..10}.*: the stem is three bare children)
                       (load_state_dict also accepts the seg_video "base." prefix,
                        log.txt:18-170, and a DataParallel/DDP "module." prefix)
 
@@ -21,7 +22,7 @@ Differences by design:
     6 products, for every conv with cin >= 32; parity gates as fp32, ~3x faster), "bf16"
     (perf mode, fp32 accumulation) or "int8" (W8A8 for the cin >= 64 convs,
     config C5; needs calibrate_int8() or load_int8_state() first — the reference has no
-    quantisation, so this mode is ours) via set_precision().
+    quantisation, so this mode is ours; DRN-D only) via set_precision().
   * segment(frames_u8) is the fused seg_video path (seg_video_old_no_plot.py:157-169:
     normalise -> model(img)[0] -> torch.max(final, 1)) producing uint8 labels without
     materialising the 19-plane log-prob tensor.  segment(render="color" | "overlay") also returns
@@ -82,6 +83,7 @@ class DRNSeg(nn.Module):
             self.up = up
         self.use_torch_up = bool(use_torch_up)
         self.model_name = model_name
+        self.arch = model.arch       # "D" or "C" (lmodels/drn.py:119)
         self.classes = classes
         self.precision = "fp32"
         self.block_sparse = False    # opt-in: measured slower than dense below ~60 % zero units
@@ -254,6 +256,10 @@ class DRNSeg(nn.Module):
     def set_precision(self, precision: str) -> "DRNSeg":
         if precision not in ("fp32", "fp32x", "bf16", "int8"):
             raise ValueError("precision must be 'fp32', 'fp32x', 'bf16' or 'int8'")
+        if precision == "int8" and self.arch != "D":
+            # the int8 launches are pinned bit for bit by an oracle that restates DRN-D only
+            raise NotImplementedError(f"precision 'int8' covers the DRN-D family only; {self.model_name} "
+                                      "runs in 'fp32', 'fp32x' or 'bf16'")
         self.precision = precision
         return self
 

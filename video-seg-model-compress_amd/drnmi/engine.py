@@ -1,4 +1,4 @@
-"""Execution engine: packs a DRN-D + seg head into HIP-kernel launch plans.
+"""Execution engine: packs a DRN-D or DRN-C trunk + seg head into HIP-kernel launch plans.
 
 The reference runs DRNSeg.forward as ~70 ATen ops per frame (lmodels/drnseg.py:
 295-299 -> lmodels/drn.py:213-259).  Here the same network is lowered once into a
@@ -131,8 +131,26 @@ def lower_drnseg(layer: nn.Sequential, seg: nn.Conv2d, prefix: str = "layer") ->
         g.channels[name] = c
         return name
 
-    for li, stage in enumerate(layer):
+    children = list(layer)
+    stage_no = 0                 # DRN's layer number: "layer0" is the stem output on both families
+    for li, stage in enumerate(children):
         sname = f"{prefix}.{li}"
+        if isinstance(stage, nn.Conv2d):
+            # arch C stem (lmodels/drn.py:121-125): bare conv1 / bn1 / relu children, state_dict keys
+            # layer.0.weight, layer.1.*; the ReLU (index 2) closes DRN's layer0
+            if li + 2 >= len(children) or not isinstance(children[li + 1], nn.BatchNorm2d) or \
+                    not isinstance(children[li + 2], nn.ReLU):
+                raise TypeError(f"bare conv at {sname} must be followed by BatchNorm2d and ReLU")
+            dst = new(stage.out_channels)
+            g.nodes.append(ConvNode(sname, stage, children[li + 1], cur, dst, relu=True))
+            cur = dst
+            continue
+        if isinstance(stage, nn.BatchNorm2d):
+            continue                              # folded into the bare conv before it
+        if isinstance(stage, nn.ReLU):
+            g.stage_outputs[f"layer{stage_no}"] = cur
+            stage_no += 1
+            continue
         mods = list(stage)
         if mods and isinstance(mods[0], nn.Conv2d):
             # conv-bn-relu triples (layer0 stem, _make_conv_layers)
@@ -172,7 +190,8 @@ def lower_drnseg(layer: nn.Sequential, seg: nn.Conv2d, prefix: str = "layer") ->
                     cur = out
                 else:
                     raise TypeError(f"unsupported block {type(blk)} at {bname}")
-        g.stage_outputs[f"layer{li}"] = cur
+        g.stage_outputs[f"layer{stage_no}"] = cur
+        stage_no += 1
     logits = "logits"
     g.channels[logits] = seg.out_channels
     g.nodes.append(ConvNode("seg", seg, None, cur, logits, relu=False, out_fp32_nchw=True))
@@ -325,6 +344,8 @@ class PackedNet:
             self.front_eligible = self._front_shapes_ok()
             self.block64_pairs = self._block64_pairs()
             self._block64_packs = {}
+            self.block16_pairs = self._block16_pairs()
+            self._block16_packs = {}
 
     def _front_shapes_ok(self) -> bool:
         """The fused video front (drnmi_video_front_u8: layer0 + layer1 + layer2 of every DRN-D,
@@ -380,6 +401,46 @@ class PackedNet:
                                               out.ctypes.data_as(ctypes.c_void_p)), "block64_pack")
             t = torch.from_numpy(out).to(self.device)
             self._block64_packs[i] = t
+        return t
+
+    def _block16_pairs(self) -> list[int]:
+        """Node indices i where nodes i, i+1 are a plain 16-channel BasicBlock (lmodels/drn.py:49-65:
+        conv3x3 16 -> 16 + BN + ReLU, conv3x3 + BN + residual = the block input + ReLU, stride 1,
+        dilation 1, no downsample: DRN-C layer1) in bf16: drnmi_basic_block16 runs them as one launch."""
+        if self.base != "bf16" or not FUSE_BLOCK16:
+            return []
+        nodes = self.graph.nodes
+        out = []
+        for i in range(len(nodes) - 1):
+            a, b = nodes[i], nodes[i + 1]
+            ok = True
+            for nd in (a, b):
+                c = nd.conv
+                ok &= (c.in_channels, c.out_channels, c.kernel_size[0], c.stride[0], c.padding[0], c.dilation[0],
+                       c.groups) == (16, 16, 3, 1, 1, 1, 1) and nd.bn is not None and nd.relu and not nd.i8 \
+                    and not nd.x6 and not nd.out_fp32_nchw and not nd.fused and nd.fused_into < 0
+            ok = ok and a.res is None and b.src == a.dst and b.res == a.src and \
+                all(self.cstride[v] == 16 for v in (a.src, a.dst, b.dst)) and \
+                self.value_code(a.src) == self.value_code(a.dst) == self.value_code(b.dst) == _lib.DRNMI_BF16
+            if ok and (not out or out[-1] + 1 < i):
+                out.append(i)
+        return out
+
+    def block16_pack(self, i: int) -> torch.Tensor:
+        """Device copy of drnmi_block16_pack for the block at nodes i, i+1 (cleared by every repack)."""
+        t = self._block16_packs.get(i)
+        if t is None:
+            import numpy as np
+            lib = _lib.load()
+            arrs = []
+            for nd in self.graph.nodes[i:i + 2]:
+                arrs += [nd.conv.weight.detach().float().cpu().contiguous().numpy(),
+                         nd.scale[:16].float().cpu().contiguous().numpy(), nd.shift[:16].float().cpu().contiguous().numpy()]
+            out = np.zeros(int(lib.drnmi_block16_pack_bytes()), dtype=np.uint8)
+            _lib.check(lib.drnmi_block16_pack(*[x.ctypes.data_as(ctypes.c_void_p) for x in arrs],
+                                              out.ctypes.data_as(ctypes.c_void_p)), "block16_pack")
+            t = torch.from_numpy(out).to(self.device)
+            self._block16_packs[i] = t
         return t
 
     def front_pack(self, mean, std, bgr: bool) -> torch.Tensor:
@@ -526,6 +587,8 @@ FUSE_STEM = True
 FUSE_FRONT = True
 # 64-channel BasicBlocks (D-22 layer3.1) as one drnmi_basic_block64 launch (False: two conv launches)
 FUSE_BLOCK64 = True
+# 16-channel BasicBlocks (DRN-C layer1) as one drnmi_basic_block16 launch (False: two conv launches)
+FUSE_BLOCK16 = True
 
 
 def _probe_args(nd: ConvNode, cin_stride: int, k: int, k_pad: int) -> _lib.ConvArgs:
@@ -613,6 +676,17 @@ class Plan:
         for i in range(len(g.nodes)):
             for v in reads_of[i]:
                 last_use[v] = i
+        lib = _lib.load()
+        # fused 16-channel BasicBlocks (DRN-C layer1): conv1's output has no other reader.  Decided
+        # before the buffers: that output stays in LDS, so it gets no HBM buffer (16 channels at full
+        # resolution, 512 MB at 8 x 1024 x 2048)
+        self.block16 = {}
+        for i in getattr(packed, "block16_pairs", []):
+            if self.fuse and not any(g.nodes[i].dst in reads_of[j] for j in range(len(g.nodes)) if j != i + 1) and \
+                    not packed.quant_after.get(i) and \
+                    lib.drnmi_block16_supported(n, *self.shapes[g.nodes[i].dst]):
+                self.block16[i] = packed.block16_pack(i)
+        self._lds_vals = {g.nodes[i].dst for i in self.block16}
         self.bufs = {}
         pool = {}
         self.bufs["input"] = torch.empty(n * h * w * 8, dtype=packed.tdtype, device=dev)
@@ -623,8 +697,8 @@ class Plan:
             self.bufs[v] = lst.pop() if lst else torch.empty(numel, dtype=td, device=dev)
 
         for i, nd in enumerate(g.nodes):
-            if i in self.skip:
-                continue                          # computed inside the block's last conv
+            if i in self.skip or i in self.block16:
+                continue                          # computed inside the block's last conv / kept in LDS
             oh, ow = self.shapes[nd.dst]
             if nd.out_fp32_nchw:
                 self.bufs[nd.dst] = torch.empty(n, nd.conv.out_channels, oh, ow, dtype=torch.float32, device=dev)
@@ -639,7 +713,8 @@ class Plan:
                         pool.setdefault((t.numel(), t.dtype), []).append(t)
         self.keep_all = keep_all
         self._reads_of = reads_of
-        self.args = [None if i in self.skip else self._conv_args(nd) for i, nd in enumerate(g.nodes)]
+        self.args = [None if i in self.skip or i in self.block16 else self._conv_args(nd)
+                     for i, nd in enumerate(g.nodes)]
         self.stem_u8 = self._stem_u8_args()
         self.stem_fused = self._stem_fusable(reads_of)
         self.front_fused = self._front_fusable(reads_of)
@@ -647,7 +722,6 @@ class Plan:
         self._norm = None                          # (mean, std, bgr) of the last ingest_u8
         # fused 64-channel BasicBlocks: the first conv's output has no other reader
         self.block64 = {}
-        lib = _lib.load()
         for i in getattr(packed, "block64_pairs", []):
             # (int8 nets: the block output's int8 copy for layer4 is quantised after the launch)
             if self.fuse and not any(g.nodes[i].dst in reads_of[j] for j in range(len(g.nodes)) if j != i + 1) and \
@@ -713,7 +787,8 @@ class Plan:
             return
         j = prod[0]
         a = self.args[j]
-        if a is None or j in self.block64 or (j - 1) in self.block64 or j <= 2 or self.packed.quant_after.get(j):
+        if a is None or j in self.block64 or (j - 1) in self.block64 or j in self.block16 or (j - 1) in self.block16 \
+                or j <= 2 or self.packed.quant_after.get(j):
             return
         if any(nodes[j].dst in self._reads_of[k] for k in range(len(nodes)) if k != i):
             return
@@ -775,7 +850,8 @@ class Plan:
         ih, iw = self.shapes[nd.src]
         oh, ow = self.shapes[nd.dst]
         a = _lib.ConvArgs()
-        a.x = self.bufs[nd.x_val].data_ptr()
+        # (conv2 of a fused 16-channel block: its input has no buffer; these args only name the launch's row)
+        a.x = None if nd.x_val in self._lds_vals else self.bufs[nd.x_val].data_ptr()
         a.wgt = nd.wpk.data_ptr()
         a.scale = None if nd.scale_folded else nd.scale.data_ptr()
         a.shift = nd.shift.data_ptr()
@@ -833,7 +909,7 @@ class Plan:
         if skip != self.skip:
             raise RuntimeError("repack changed the downsample fusion of a live plan")
         for i, nd in enumerate(nodes):
-            if i in self.skip:
+            if i in self.skip or i in self.block16:
                 continue
             self.args[i] = self._conv_args(nd)
         self.front_pack_t = None
@@ -841,6 +917,8 @@ class Plan:
             self.front_pack_t = self.packed.front_pack(*self._norm)
         for i in list(self.block64):
             self.block64[i] = self.packed.block64_pack(i)
+        for i in list(self.block16):
+            self.block16[i] = self.packed.block16_pack(i)
         self._setup_seg_nhwc()
         if self.stem_u8 is not None:
             nd = self.packed.graph.nodes[0]
@@ -857,10 +935,24 @@ class Plan:
         front = self.src == "u8" and self.front_fused
         fused_stem = self.src == "u8" and self.stem_fused and not front
         nodes = self.packed.graph.nodes
-        blocks = self.block64
+        blocks, blocks16 = self.block64, self.block16
         for i, (a, nd) in enumerate(zip(self.args, nodes)):
             if a is None or (i == 1 and fused_stem) or (front and i in (1, 2)) or (i - 1) in blocks:
                 continue                          # folded into another launch
+            # (conv1 of a fused 16-channel BasicBlock has args None: it runs with its conv2)
+            if (i - 1) in blocks16:               # conv1 + conv2 as one launch, reported under conv2's index
+                                                  # (block64 reports under conv1's)
+                if timing_hook is not None:
+                    timing_hook(i, nd, True)
+                h, w = self.shapes[nd.dst]
+                _lib.check(lib.drnmi_basic_block16(self.bufs[nodes[i - 1].x_val].data_ptr(), blocks16[i - 1].data_ptr(),
+                                                   self.bufs[nd.dst].data_ptr(), self.n, h, w,
+                                                   ctypes.c_void_p(stream)), f"basic_block16 {nodes[i - 1].name}")
+                if timing_hook is not None:
+                    timing_hook(i, nd, False)
+                for v in self.packed.quant_after.get(i, ()):
+                    self._quantize(lib, v, stream)
+                continue
             if i in blocks:                       # conv1 + conv2 of a 64-channel BasicBlock
                 if timing_hook is not None:
                     timing_hook(i, nd, True)

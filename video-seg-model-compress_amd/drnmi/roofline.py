@@ -106,6 +106,13 @@ def launch_work(plan, video: bool = True):
         mid = plan.n * hb * wb * 64 * esz
         rows[i] = (rows[i][0], rows[i][1] + rows[i + 1][1], rows[i][2] + rows[i + 1][2] - 3 * mid)
         rows[i + 1] = (rows[i + 1][0], 0.0, 0.0)
+    for i in getattr(plan, "block16", {}):
+        # a 16-channel BasicBlock in one launch (drnmi_basic_block16), reported under the second
+        # conv's index: the same three tensor passes saved
+        hb, wb = plan.shapes[nodes[i].dst]
+        mid = plan.n * hb * wb * 16 * esz
+        rows[i + 1] = (rows[i + 1][0], rows[i][1] + rows[i + 1][1], rows[i][2] + rows[i + 1][2] - 3 * mid)
+        rows[i] = (rows[i][0], 0.0, 0.0)
     segf = getattr(plan, "seg_fused", None)
     if video and segf is not None and plan.labels_path() == "seg2":
         # the seg classifier in the last conv's epilogue (drnmi_conv_stag_seg): the conv's output is
