@@ -2,7 +2,6 @@
 step times of both plans interleaved on one device, and the per-launch table of each (HIP events
 through DRNSeg.timing_hook).  python scripts/drn_c_micro.py [--batch 8 --height 1024 --width 2048]"""
 import argparse
-import ctypes
 import os
 import sys
 
@@ -25,18 +24,11 @@ def make(fuse, n, h, w):
 
 
 def launch_names(plan):
+    """Kernel name per hook index of the segment() path (the head last)."""
     lib = _lib.load()
-    names = []
-    for i, a in enumerate(plan.args):
-        if (i - 1) in plan.block16:
-            names.append("block16_kernel")
-        elif a is None or i in plan.block16:
-            names.append("")
-        else:
-            a = plan.stem_u8 if i == 0 and plan.stem_u8 is not None else a
-            if i == plan.seg_idx and plan.labels_path() != "nchw":
-                a = plan.seg_nhwc_args
-            names.append(lib.drnmi_conv_kernel_name(ctypes.byref(a)).decode())
+    names = [""] * len(plan.args)
+    for l in plan.launches("u8", plan.labels_path() != "nchw"):
+        names[l.row] = l.kernel_name(lib)
     return names + ["head"]
 
 

@@ -6,7 +6,7 @@ at wo % 256 == 0.  This module runs the plan DRNSeg.segment() really ships (fuse
 on thin, wide frames that take the headline routing, snapshots through DRNSeg.timing_hook what
 every launch read and wrote, and re-computes each launch on the CPU from the launch's own inputs:
 
-  capture(cfg)        one GPU run per configuration (cached): a list of Launch records
+  capture(cfg)        one GPU run per configuration (cached): a list of LaunchRec records
   check_launch(rec)   float64 (bf16 launches) or oracle/int8_oracle.py (int8 launches) reference of
                       one record and its gate; returns the figures it measured
 
@@ -17,7 +17,6 @@ and the MFMA order are two valid fp32 orders that may err in opposite directions
 """
 from __future__ import annotations
 
-import ctypes
 import re
 from dataclasses import dataclass, field
 
@@ -103,7 +102,7 @@ class ConvRec:
 
 
 @dataclass
-class Launch:
+class LaunchRec:
     index: int
     name: str            # node name, "head" for the head
     kind: str            # "front" | "block64" | "conv" | "seg_conv" | "head"
@@ -383,14 +382,14 @@ def check_head(d: dict) -> dict:
     return st
 
 
-def check_quant(rec: Launch) -> int:
+def check_quant(rec: LaunchRec) -> int:
     """The bf16 -> int8 copies this launch read, against Q.quantize_i8 of their producer's output."""
     for v, q, src, inv in rec.quant:
         np.testing.assert_array_equal(q, Q.quantize_i8(src, F32(inv)), err_msg=f"quantize_i8 {v}")
     return len(rec.quant)
 
 
-def check_launch(rec: Launch) -> dict:
+def check_launch(rec: LaunchRec) -> dict:
     st = {"front": lambda: check_front(rec.data), "block64": lambda: check_block64(rec.data),
           "conv": lambda: check_conv(rec.conv), "seg_conv": lambda: check_seg_conv(rec.conv),
           "head": lambda: check_head(rec.data)}[rec.kind]()
@@ -409,33 +408,21 @@ def _np(t: torch.Tensor) -> np.ndarray:
 
 
 def snapshot_hook(plan, labels, ins: dict, outs: dict, order: list):
-    """DRNSeg.timing_hook that copies to the host what launch i reads (before it) and what it
-    writes (after it): plan._reads_of[i] (for a fused node x_val and the downsample's input, in
-    int8 nets the q:<v> copies), the partial logits for the head; the output of the front is
-    layer2's value, of a block64 pair the second conv's, of the seg-fused conv the partials."""
-    nodes = plan.packed.graph.nodes
+    """DRNSeg.timing_hook that copies to the host what the launch reporting under index i reads
+    (before it) and what it writes (after it): the reads / writes of its entry in
+    plan.launches("u8", True) (in int8 nets the q:<v> copies among the reads); the head (nd None)
+    reads the partial logits and writes the labels."""
+    by_row = {l.row: l for l in plan.launches("u8", True)}
 
     def hook(i, nd, start):
         if labels.is_cuda:
             torch.cuda.synchronize()
         if start:
             order.append(i)
-            if nd is None:
-                ins[i] = {"seg_part": plan.bufs["seg_part"].cpu().clone()}
-            elif i == 0:
-                ins[i] = {}
-            else:
-                ins[i] = {v: plan.bufs[v].cpu().clone() for v in plan._reads_of[i]}
-        elif nd is None:
-            outs[i] = labels.cpu().clone()
-        elif i == 0:
-            outs[i] = plan.bufs[nodes[2].dst].cpu().clone()
-        elif i in plan.block64:
-            outs[i] = plan.bufs[nodes[i + 1].dst].cpu().clone()
-        elif i == plan.seg_fused["conv"]:
-            outs[i] = plan.bufs["seg_part"].cpu().clone()
+            reads = ("seg_part",) if nd is None else by_row[i].reads
+            ins[i] = {v: plan.bufs[v].cpu().clone() for v in reads}
         else:
-            outs[i] = plan.bufs[nd.dst].cpu().clone()
+            outs[i] = (labels if nd is None else plan.bufs[by_row[i].writes[0]]).cpu().clone()
     return hook
 
 
@@ -477,9 +464,9 @@ def build_records(m, plan, frames_np: np.ndarray, ins: dict, outs: dict, order: 
     pk, nodes, lib = plan.packed, plan.packed.graph.nodes, L.load()
     dev = pk.device
     assert order == sorted(outs) and order[-1] == len(nodes)
-    produced = {}                      # value -> snapshot of it right after its producer
-    for i in order[:-1]:
-        produced[nodes[2].dst if i == 0 else nodes[i + 1].dst if i in plan.block64 else nodes[i].dst] = outs[i]
+    by_row = {l.row: l for l in plan.launches("u8", True)}
+    assert order[:-1] == list(by_row)
+    produced = {by_row[i].writes[0]: outs[i] for i in order[:-1]}   # value -> snapshot right after its producer
     lh, lw = plan.shapes["logits"]
     seg = nodes[plan.seg_idx]
     recs = []
@@ -487,28 +474,30 @@ def build_records(m, plan, frames_np: np.ndarray, ins: dict, outs: dict, order: 
         nd = nodes[i] if i < len(nodes) else None
         if nd is None:
             sf = plan.seg_fused
-            recs.append(Launch(i, "head", "head", "up8_labels_tile_kernel", "head", data={
+            recs.append(LaunchRec(i, "head", "head", "up8_labels_tile_kernel", "head", data={
                 "part": _np(ins[i]["seg_part"]).reshape(2, n, lh, lw, plan.SEG_NHWC_CS)[..., :19],
                 "bias": _np(seg.shift[:19]), "scale": _np(seg.scale[:19]) if sf["i8"] else None,
                 "up": _np(m._up_plane(dev)), "got": _np(outs[i])}))
             continue
-        if i == 0:
-            recs.append(Launch(0, nd.name, "front", "front3_kernel", "front", data={
+        launch = by_row[i]
+        kernel = launch.kernel_name(lib)
+        if launch.kind == "front":
+            recs.append(LaunchRec(0, nd.name, "front", kernel, "front", data={
                 "frames": frames_np, "blob": plan.front_pack_t.cpu().numpy(),
                 "got": _np(outs[0]).reshape(n, (h + 1) // 2, (w + 1) // 2, 32)}))
             continue
-        if i in plan.block64:
+        if launch.kind == "block64":
             bh, bw = plan.shapes[nd.dst]
             p = []
             for b in nodes[i:i + 2]:
                 p += [b.conv.weight.detach().float().cpu(), b.scale[:64].float().cpu(), b.shift[:64].float().cpu()]
-            recs.append(Launch(i, nd.name, "block64", "block64_kernel", group_of(nd.name), data={
+            recs.append(LaunchRec(i, nd.name, "block64", kernel, group_of(nd.name), data={
                 "x": ins[i][nd.x_val].view(n, bh, bw, 64), "p": tuple(p),
                 "got": outs[i].view(n, bh, bw, 64).float()}))
             continue
         a = plan.args[i]
-        segf = i == plan.seg_fused["conv"]
-        kernel = (lib.drnmi_conv_stag_seg_kernel_name if segf else lib.drnmi_conv_kernel_name)(ctypes.byref(a)).decode()
+        segf = launch.kind == "conv_seg"
+        assert segf or launch.kind == "conv", launch.kind
         fused = nd.fused if plan.fuse else None
         c = nd.conv
         ih, iw = plan.shapes[nd.src]
@@ -542,7 +531,7 @@ def build_records(m, plan, frames_np: np.ndarray, ins: dict, outs: dict, order: 
             r.got = (o.view(torch.int16).numpy().view(np.uint16) if r.out == "bf16" else o.numpy()).reshape(n, oh, ow, cout)
         else:
             r.got = _np(outs[i]).reshape(n, oh, ow, cout)
-        rec = Launch(i, nd.name, "seg_conv" if segf else "conv", kernel, group_of(nd.name), conv=r)
+        rec = LaunchRec(i, nd.name, "seg_conv" if segf else "conv", kernel, group_of(nd.name), conv=r)
         for v in sorted(ins[i]):
             if v.startswith("q:"):
                 rec.quant.append((v[2:], ins[i][v].numpy(), _np(produced[v[2:]]), 1.0 / float(pk.act_scales[v[2:]])))

@@ -340,12 +340,9 @@ class PackedNet:
                 full[:w.shape[0]] = wp.reshape(w.shape[0], STEM_U8_K)
                 # (fp32 / fp32x: the f32 weights in the same kh*32 + kw*4 + c layout, patch_f32.hip SRC 0)
                 self.stem_u8_w = full.to(self.tdtype).contiguous()
-            self._front_packs = {}
+            self._packs = {}                  # front_pack / block_pack blobs on the device, by key
             self.front_eligible = self._front_shapes_ok()
-            self.block64_pairs = self._block64_pairs()
-            self._block64_packs = {}
-            self.block16_pairs = self._block16_pairs()
-            self._block16_packs = {}
+            self.block_pairs = {c: self._block_pairs(c) for c in (16, 64)}
 
     def _front_shapes_ok(self) -> bool:
         """The fused video front (drnmi_video_front_u8: layer0 + layer1 + layer2 of every DRN-D,
@@ -363,11 +360,13 @@ class PackedNet:
                 return False
         return nodes[1].src == nodes[0].dst and nodes[2].src == nodes[1].dst and self.cstride[nodes[2].dst] == 32
 
-    def _block64_pairs(self) -> list[int]:
-        """Node indices i where nodes i, i+1 are a plain 64-channel BasicBlock (lmodels/drn.py:49-65:
-        conv3x3 64 -> 64 + BN + ReLU, conv3x3 + BN + residual = the block input + ReLU, stride 1,
-        dilation 1, no downsample) in bf16: drnmi_basic_block64 runs them as one launch."""
-        if self.base != "bf16" or not FUSE_BLOCK64 or self.block_sparse:
+    def _block_pairs(self, c: int) -> list[int]:
+        """Node indices i where nodes i, i+1 are a plain c-channel BasicBlock (lmodels/drn.py:49-65:
+        conv3x3 c -> c + BN + ReLU, conv3x3 + BN + residual = the block input + ReLU, stride 1,
+        dilation 1, no downsample) in bf16: drnmi_basic_block64 (D-22 layer3.1; not with block-sparse
+        packing) / drnmi_basic_block16 (DRN-C layer1) runs them as one launch."""
+        on = FUSE_BLOCK64 and not self.block_sparse if c == 64 else FUSE_BLOCK16
+        if self.base != "bf16" or not on:
             return []
         nodes = self.graph.nodes
         out = []
@@ -375,93 +374,44 @@ class PackedNet:
             a, b = nodes[i], nodes[i + 1]
             ok = True
             for nd in (a, b):
-                c = nd.conv
-                ok &= (c.in_channels, c.out_channels, c.kernel_size[0], c.stride[0], c.padding[0], c.dilation[0],
-                       c.groups) == (64, 64, 3, 1, 1, 1, 1) and nd.bn is not None and nd.relu and not nd.i8 \
+                cv = nd.conv
+                ok &= (cv.in_channels, cv.out_channels, cv.kernel_size[0], cv.stride[0], cv.padding[0], cv.dilation[0],
+                       cv.groups) == (c, c, 3, 1, 1, 1, 1) and nd.bn is not None and nd.relu and not nd.i8 \
                     and not nd.x6 and not nd.out_fp32_nchw and not nd.fused and nd.fused_into < 0
             ok = ok and a.res is None and b.src == a.dst and b.res == a.src and \
-                all(self.cstride[v] == 64 for v in (a.src, a.dst, b.dst)) and \
+                all(self.cstride[v] == c for v in (a.src, a.dst, b.dst)) and \
                 self.value_code(a.src) == self.value_code(a.dst) == self.value_code(b.dst) == _lib.DRNMI_BF16
             if ok and (not out or out[-1] + 1 < i):
                 out.append(i)
         return out
 
-    def block64_pack(self, i: int) -> torch.Tensor:
-        """Device copy of drnmi_block64_pack for the block at nodes i, i+1 (cleared by every repack)."""
-        t = self._block64_packs.get(i)
+    def _pack_blob(self, key, what: str, nodes, rows, vectors=(), flags=()) -> torch.Tensor:
+        """Device copy of drnmi_<what>_pack over `nodes`' weights and the first `rows` entries of
+        their scale and shift, then `vectors` (float32 host arrays) and `flags` (ints) as the entry
+        point takes them (cached under `key`; cleared by every repack)."""
+        t = self._packs.get(key)
         if t is None:
             import numpy as np
             lib = _lib.load()
             arrs = []
-            for nd in self.graph.nodes[i:i + 2]:
+            for nd in nodes:
                 arrs += [nd.conv.weight.detach().float().cpu().contiguous().numpy(),
-                         nd.scale[:64].float().cpu().contiguous().numpy(), nd.shift[:64].float().cpu().contiguous().numpy()]
-            out = np.zeros(int(lib.drnmi_block64_pack_bytes()), dtype=np.uint8)
-            _lib.check(lib.drnmi_block64_pack(*[x.ctypes.data_as(ctypes.c_void_p) for x in arrs],
-                                              out.ctypes.data_as(ctypes.c_void_p)), "block64_pack")
-            t = torch.from_numpy(out).to(self.device)
-            self._block64_packs[i] = t
+                         nd.scale[:rows].float().cpu().contiguous().numpy(), nd.shift[:rows].float().cpu().contiguous().numpy()]
+            arrs += [np.asarray(v, dtype=np.float32) for v in vectors]
+            out = np.zeros(int(getattr(lib, f"drnmi_{what}_pack_bytes")()), dtype=np.uint8)
+            _lib.check(getattr(lib, f"drnmi_{what}_pack")(*[x.ctypes.data_as(ctypes.c_void_p) for x in arrs], *flags,
+                                                          out.ctypes.data_as(ctypes.c_void_p)), f"{what}_pack")
+            t = self._packs[key] = torch.from_numpy(out).to(self.device)
         return t
 
-    def _block16_pairs(self) -> list[int]:
-        """Node indices i where nodes i, i+1 are a plain 16-channel BasicBlock (lmodels/drn.py:49-65:
-        conv3x3 16 -> 16 + BN + ReLU, conv3x3 + BN + residual = the block input + ReLU, stride 1,
-        dilation 1, no downsample: DRN-C layer1) in bf16: drnmi_basic_block16 runs them as one launch."""
-        if self.base != "bf16" or not FUSE_BLOCK16:
-            return []
-        nodes = self.graph.nodes
-        out = []
-        for i in range(len(nodes) - 1):
-            a, b = nodes[i], nodes[i + 1]
-            ok = True
-            for nd in (a, b):
-                c = nd.conv
-                ok &= (c.in_channels, c.out_channels, c.kernel_size[0], c.stride[0], c.padding[0], c.dilation[0],
-                       c.groups) == (16, 16, 3, 1, 1, 1, 1) and nd.bn is not None and nd.relu and not nd.i8 \
-                    and not nd.x6 and not nd.out_fp32_nchw and not nd.fused and nd.fused_into < 0
-            ok = ok and a.res is None and b.src == a.dst and b.res == a.src and \
-                all(self.cstride[v] == 16 for v in (a.src, a.dst, b.dst)) and \
-                self.value_code(a.src) == self.value_code(a.dst) == self.value_code(b.dst) == _lib.DRNMI_BF16
-            if ok and (not out or out[-1] + 1 < i):
-                out.append(i)
-        return out
-
-    def block16_pack(self, i: int) -> torch.Tensor:
-        """Device copy of drnmi_block16_pack for the block at nodes i, i+1 (cleared by every repack)."""
-        t = self._block16_packs.get(i)
-        if t is None:
-            import numpy as np
-            lib = _lib.load()
-            arrs = []
-            for nd in self.graph.nodes[i:i + 2]:
-                arrs += [nd.conv.weight.detach().float().cpu().contiguous().numpy(),
-                         nd.scale[:16].float().cpu().contiguous().numpy(), nd.shift[:16].float().cpu().contiguous().numpy()]
-            out = np.zeros(int(lib.drnmi_block16_pack_bytes()), dtype=np.uint8)
-            _lib.check(lib.drnmi_block16_pack(*[x.ctypes.data_as(ctypes.c_void_p) for x in arrs],
-                                              out.ctypes.data_as(ctypes.c_void_p)), "block16_pack")
-            t = torch.from_numpy(out).to(self.device)
-            self._block16_packs[i] = t
-        return t
+    def block_pack(self, c: int, i: int) -> torch.Tensor:
+        """drnmi_block64_pack / drnmi_block16_pack for the c-channel block at nodes i, i+1."""
+        return self._pack_blob((c, i), f"block{c}", self.graph.nodes[i:i + 2], c)
 
     def front_pack(self, mean, std, bgr: bool) -> torch.Tensor:
-        """Device copy of drnmi_front_pack for these weights and this normalisation (cached per
-        (mean, std, bgr); cleared by every repack)."""
+        """drnmi_front_pack for these weights and this normalisation."""
         key = (tuple(float(v) for v in mean), tuple(float(v) for v in std), bool(bgr))
-        t = self._front_packs.get(key)
-        if t is None:
-            import numpy as np
-            lib = _lib.load()
-            arrs = []
-            for nd in self.graph.nodes[:3]:
-                arrs += [nd.conv.weight.detach().float().cpu().contiguous().numpy(),
-                         nd.scale.float().cpu().contiguous().numpy(), nd.shift.float().cpu().contiguous().numpy()]
-            arrs += [np.asarray(key[0], dtype=np.float32), np.asarray(key[1], dtype=np.float32)]
-            out = np.zeros(int(lib.drnmi_front_pack_bytes()), dtype=np.uint8)
-            _lib.check(lib.drnmi_front_pack(*[a.ctypes.data_as(ctypes.c_void_p) for a in arrs], 1 if bgr else 0,
-                                            out.ctypes.data_as(ctypes.c_void_p)), "front_pack")
-            t = torch.from_numpy(out).to(self.device)
-            self._front_packs[key] = t
-        return t
+        return self._pack_blob(key, "front", self.graph.nodes[:3], None, key[:2], (1 if bgr else 0,))
 
 
     def _fuse_downsamples(self):
@@ -638,6 +588,41 @@ def _conv_out(h, k, s, p, d):
 LABELS_NHWC = True
 SEG_FUSE = True
 
+# launch kind -> (C entry point, how many drnmi_conv_args lead its arguments, the library's name
+# query over those structs or, without one, the kernel's fixed name)
+LAUNCH_KINDS = {"conv": ("drnmi_conv2d_bn_act", 1, "drnmi_conv_kernel_name"),
+                "stem_layer1": ("drnmi_stem_layer1", 2, "drnmi_stem_layer1_kernel_name"),
+                "conv_seg": ("drnmi_conv_stag_seg", 1, "drnmi_conv_stag_seg_kernel_name"),
+                "front": ("drnmi_video_front_u8", 0, "front3_kernel"),
+                "block64": ("drnmi_basic_block64", 0, "block64_kernel"),
+                "block16": ("drnmi_basic_block16", 0, "block16_kernel")}
+
+
+@dataclass
+class Launch:
+    """One C call of Plan.run_backbone (Plan.launches)."""
+    row: int             # node index it reports under: timing_hook, roofline.launch_work, bench's table
+    kind: str            # key of LAUNCH_KINDS
+    nodes: tuple         # node indices it computes
+    reads: tuple         # plan.bufs keys it reads (the u8 stem and front read the caller's frames: none) ...
+    writes: tuple        # ... and writes
+    quant: tuple         # values quantised to their int8 copy "q:<v>" right after it
+    argv: tuple          # the entry point's arguments before the stream; the arg structs by reference to
+                         # the plan's own instances (plan.args, stem_u8, seg_nhwc_args), read when it runs
+    live: object = None  # front: argv made per call (the frame pointer and front_pack_t change per ingest)
+    what: str = ""
+
+    def issue(self, lib, stream):
+        argv = self.argv if self.live is None else self.live()
+        _lib.check(getattr(lib, LAUNCH_KINDS[self.kind][0])(*argv, stream), self.what)
+
+    def kernel_name(self, lib) -> str:
+        _, structs, name = LAUNCH_KINDS[self.kind]
+        if structs:
+            name = getattr(lib, name)(*self.argv[:structs])
+            name = "" if name is None else name.decode()
+        return name
+
 
 class Plan:
     """Launch plan for one (batch, H, W, precision): shapes, buffers, C-ABI arg structs."""
@@ -676,16 +661,19 @@ class Plan:
         for i in range(len(g.nodes)):
             for v in reads_of[i]:
                 last_use[v] = i
+        self.keep_all = keep_all
+        self._reads_of = reads_of
         lib = _lib.load()
-        # fused 16-channel BasicBlocks (DRN-C layer1): conv1's output has no other reader.  Decided
-        # before the buffers: that output stays in LDS, so it gets no HBM buffer (16 channels at full
-        # resolution, 512 MB at 8 x 1024 x 2048)
-        self.block16 = {}
-        for i in getattr(packed, "block16_pairs", []):
-            if self.fuse and not any(g.nodes[i].dst in reads_of[j] for j in range(len(g.nodes)) if j != i + 1) and \
-                    not packed.quant_after.get(i) and \
-                    lib.drnmi_block16_supported(n, *self.shapes[g.nodes[i].dst]):
-                self.block16[i] = packed.block16_pack(i)
+        # fused BasicBlocks, keyed by conv1's index: conv1's output has no other reader and no int8
+        # copy (int8 nets: the block output's copy for layer4 is quantised after the launch).  Decided
+        # before the buffers: a 16-channel block's intermediate (DRN-C layer1) stays in LDS, so it gets
+        # no HBM buffer (16 channels at full resolution, 512 MB at 8 x 1024 x 2048)
+        self.block16, self.block64 = {}, {}
+        for c, admitted in ((16, self.block16), (64, self.block64)):
+            for i in packed.block_pairs[c]:
+                if self.fuse and self._only_reader(i, i + 1) and not packed.quant_after.get(i) and \
+                        getattr(lib, f"drnmi_block{c}_supported")(n, *self.shapes[g.nodes[i].dst]):
+                    admitted[i] = packed.block_pack(c, i)
         self._lds_vals = {g.nodes[i].dst for i in self.block16}
         self.bufs = {}
         pool = {}
@@ -711,25 +699,40 @@ class Plan:
                     if last_use.get(v) == i and v in self.bufs and v != nd.dst:
                         t = self.bufs[v]
                         pool.setdefault((t.numel(), t.dtype), []).append(t)
-        self.keep_all = keep_all
-        self._reads_of = reads_of
-        self.args = [None if i in self.skip or i in self.block16 else self._conv_args(nd)
-                     for i, nd in enumerate(g.nodes)]
+        self.args = self._all_args()
         self.stem_u8 = self._stem_u8_args()
-        self.stem_fused = self._stem_fusable(reads_of)
-        self.front_fused = self._front_fusable(reads_of)
         self.front_pack_t = None
         self._norm = None                          # (mean, std, bgr) of the last ingest_u8
-        # fused 64-channel BasicBlocks: the first conv's output has no other reader
-        self.block64 = {}
-        for i in getattr(packed, "block64_pairs", []):
-            # (int8 nets: the block output's int8 copy for layer4 is quantised after the launch)
-            if self.fuse and not any(g.nodes[i].dst in reads_of[j] for j in range(len(g.nodes)) if j != i + 1) and \
-                    not packed.quant_after.get(i) and \
-                    lib.drnmi_block64_supported(n, *self.shapes[g.nodes[i].dst]):
-                self.block64[i] = packed.block64_pack(i)
-        self._setup_seg_nhwc()
         self.src = "nchw"
+        self._decide_front()
+        self._setup_seg()
+
+    def _only_reader(self, i: int, j: int) -> bool:
+        """Node j's launch is the only one that reads node i's output."""
+        v = self.packed.graph.nodes[i].dst
+        return not any(v in r for k, r in self._reads_of.items() if k != j)
+
+    def _all_args(self) -> list:
+        """Index-aligned with the nodes; None for a folded downsample and for conv1 of a fused
+        16-channel block (conv2 keeps its args: they name the block's row)."""
+        return [None if i in self.skip or i in self.block16 else self._conv_args(nd)
+                for i, nd in enumerate(self.packed.graph.nodes)]
+
+    def _decide_front(self):
+        """How the uint8-frame path starts.  front_fused: layer0..layer2 as one drnmi_video_front_u8
+        launch, when the packed net takes it, each intermediate has exactly one reader and no int8
+        copy, and the frame shape is supported.  stem_fused (only run when the front is not): the u8
+        stem and layer1 as one drnmi_stem_layer1 launch, when layer1 is the stem output's only reader
+        and the library takes the pair."""
+        pk, lib = self.packed, _lib.load()
+        nodes, q = pk.graph.nodes, pk.quant_after
+        self.front_fused = bool(
+            self.fuse and pk.front_eligible and self._only_reader(0, 1) and self._only_reader(1, 2)
+            and not (q.get(0) or q.get(1) or q.get(2)) and lib.drnmi_front_supported(self.n, self.h, self.w))
+        self.stem_fused = bool(
+            FUSE_STEM and self.fuse and self.stem_u8 is not None and len(nodes) > 1 and self.args[1] is not None
+            and nodes[1].x_val == nodes[0].dst and self._only_reader(0, 1) and not q.get(0)
+            and lib.drnmi_stem_layer1_kernel_name(ctypes.byref(self.stem_u8), ctypes.byref(self.args[1])) is not None)
 
     # labels-only video path: the seg conv writes fp32 NHWC rows of SEG_NHWC_CS floats (16-B
     # stores instead of 19 strided planes) and drnmi_up8_labels_nhwc reads them; same values,
@@ -739,58 +742,54 @@ class Plan:
     # and drnmi_up8_labels_nhwc_wide; the seg classifier is not folded into the last conv there.
     SEG_NHWC_CS = 20
 
-    def _setup_seg_nhwc(self):
+    def _setup_seg(self):
+        """The labels-only forms of the seg conv (they hold weight pointers: redone after a repack).
+        seg_nhwc_args: its launch writing the NHWC rows.  seg_fused: the classifier folded into its
+        producer's epilogue (drnmi_conv_stag_seg) when that producer is a launch of one 512-channel
+        conv on the w1 / staggered tile whose output nothing else reads: bf16 nets (fp32 partial
+        logits, bias added by the head) and int8 nets (the int8 seg conv on the producer's int8
+        output: int32 partials, the seg conv's dequant applied by the head)."""
+        self._launches = {}
         self.seg_idx, self.seg_nhwc_args, self.seg_fused = -1, None, None
         self.seg_classes, self.seg_cs = 19, self.SEG_NHWC_CS
-        nodes = self.packed.graph.nodes
+        pk, lib = self.packed, _lib.load()
+        nodes = pk.graph.nodes
         idx = [i for i, nd in enumerate(nodes) if nd.out_fp32_nchw]
         if len(idx) != 1 or self.args[idx[0]] is None:
             return
         i = idx[0]
-        nd, a0 = nodes[i], self.args[i]
-        classes = nd.conv.out_channels
-        if nd.conv.kernel_size[0] != 1 or not 1 <= classes <= 256:
+        seg = nodes[i]
+        classes = seg.conv.out_channels
+        if seg.conv.kernel_size[0] != 1 or not 1 <= classes <= 256:
             return
         wide = classes != 19
-        if wide and self.packed.precision not in ("bf16", "int8"):
+        if wide and pk.precision not in ("bf16", "int8"):
             return                               # fp32 / fp32x plans keep the logits planes
         cs = (classes + 3) // 4 * 4 if wide else self.SEG_NHWC_CS
-        lh, lw = self.shapes[nd.dst]
+        lh, lw = self.shapes[seg.dst]
         a = _lib.ConvArgs()
-        ctypes.pointer(a)[0] = a0
+        ctypes.pointer(a)[0] = self.args[i]
         a.y_sn, a.y_sp, a.y_sc = lh * lw * cs, cs, 1
-        name = _lib.load().drnmi_conv_kernel_name(ctypes.byref(a))   # (routing does not read a.y)
+        name = lib.drnmi_conv_kernel_name(ctypes.byref(a))   # (routing does not read a.y)
         if name is None or not name.decode().startswith(("conv_big_kernel", "conv_i8_kernel", "conv_i8_occ2_kernel",
                                                         "conv_x6_kernel")):
             return
         if "logits_nhwc" not in self.bufs:      # only plans whose seg conv writes the NHWC rows
-            self.bufs["logits_nhwc"] = torch.empty(self.n * lh * lw * cs, dtype=torch.float32,
-                                                   device=self.packed.device)
+            self.bufs["logits_nhwc"] = torch.empty(self.n * lh * lw * cs, dtype=torch.float32, device=pk.device)
         a.y = self.bufs["logits_nhwc"].data_ptr()
         self.seg_idx, self.seg_nhwc_args = i, a
         self.seg_classes, self.seg_cs = classes, cs
-        if not wide:
-            self._setup_seg_fused(i)
-
-    def _setup_seg_fused(self, i: int):
-        """The seg classifier folded into its producer's epilogue (drnmi_conv_stag_seg) when that
-        producer is a 512-channel staggered-tile conv whose output nothing else reads: bf16 nets
-        (fp32 partial logits, bias added by the head) and int8 nets (the int8 seg conv on the
-        producer's int8 output: int32 partials, the seg conv's dequant applied by the head)."""
-        self.seg_fused = None
-        if not SEG_FUSE or not self.fuse:
+        if wide or not SEG_FUSE or not self.fuse or seg.x_val != seg.src or seg.r_val:
             return
-        nodes = self.packed.graph.nodes
-        seg = nodes[i]
-        prod = [j for j, nd in enumerate(nodes) if nd.dst == seg.x_val and j not in self.skip]
-        if len(prod) != 1 or seg.x_val != seg.src or seg.r_val:
+        # the launch that writes the seg conv's input, on the labels-only list without this fusion:
+        # one that already computes several nodes (front, block, folded downsample) is left alone
+        prod = [l for l in self._build_launches("u8" if self.stem_u8 is not None else "nchw", True)
+                if seg.x_val in l.writes]
+        if len(prod) != 1 or len(prod[0].nodes) != 1:
             return
-        j = prod[0]
+        j = prod[0].row
         a = self.args[j]
-        if a is None or j in self.block64 or (j - 1) in self.block64 or j in self.block16 or (j - 1) in self.block16 \
-                or j <= 2 or self.packed.quant_after.get(j):
-            return
-        if any(nodes[j].dst in self._reads_of[k] for k in range(len(nodes)) if k != i):
+        if pk.quant_after.get(j) or not self._only_reader(j, i):
             return
         i8 = seg.i8 and nodes[j].i8
         if i8 != (seg.i8 or nodes[j].i8) or (not i8 and not seg.scale_folded):
@@ -799,14 +798,14 @@ class Plan:
             return
         if i8 and a.out_dtype != _lib.DRNMI_I8:
             return
-        name = _lib.load().drnmi_conv_kernel_name(ctypes.byref(a))
-        # (a plain 512-channel launch runs conv_w1 unfused; fused, drnmi_conv_stag_seg's staggered tile)
+        name = lib.drnmi_conv_kernel_name(ctypes.byref(a))
+        # (unfused, the 512-channel launch runs conv_w1 or the staggered tile; fused, drnmi_conv_stag_seg
+        # runs conv_w1(_i8)_seg_kernel, and the staggered seg tile only where tile 19 is forced)
         if name is None or name.decode() not in (("conv_i8_stag_kernel", "conv_w1_i8_kernel") if i8 else ("conv_stag_kernel", "conv_w1_kernel")):
             return
-        lh, lw = self.shapes[seg.dst]
         if "seg_part" not in self.bufs:
             self.bufs["seg_part"] = torch.empty(2 * self.n * lh * lw * self.SEG_NHWC_CS,
-                                                dtype=torch.int32 if i8 else torch.float32, device=self.packed.device)
+                                                dtype=torch.int32 if i8 else torch.float32, device=pk.device)
         self.seg_fused = {"conv": j, "seg_w": seg.wpk.data_ptr(), "seg_k_pad": seg.k_pad, "seg_rows": seg.cout_pad,
                           "bias": seg.shift.data_ptr(), "i8": i8, "scale": seg.scale.data_ptr()}
 
@@ -817,32 +816,59 @@ class Plan:
             return "nchw"
         return "seg2" if self.seg_fused is not None else "nhwc"
 
-    def _front_fusable(self, reads_of) -> bool:
-        """layer0..layer2 run as one drnmi_video_front_u8 launch on the u8 path when the packed net
-        takes it, each intermediate has exactly one reader and the frame shape is supported."""
-        pk = self.packed
-        nodes = pk.graph.nodes
-        if not (self.fuse and getattr(pk, "front_eligible", False)):
-            return False
-        for i in (0, 1):
-            if any(nodes[i].dst in reads_of[j] for j in range(len(nodes)) if j != i + 1) or pk.quant_after.get(i):
-                return False
-        if pk.quant_after.get(2):
-            return False
-        return bool(_lib.load().drnmi_front_supported(self.n, self.h, self.w))
+    def launches(self, src: str, labels_only: bool = False) -> list:
+        """The Launch list run_backbone issues for frames ingested as `src` ("u8" / "nchw") with or
+        without the labels-only seg forms; built on first use, dropped by refresh_weight_ptrs."""
+        key = (src, bool(labels_only))
+        if key not in self._launches:
+            self._launches[key] = self._build_launches(*key)
+        return self._launches[key]
 
-    def _stem_fusable(self, reads_of) -> bool:
-        """The u8 stem and layer1 can run as one launch (drnmi_stem_layer1) when layer1 is the
-        stem output's only reader and the library takes the pair."""
-        nodes = self.packed.graph.nodes
-        if not (FUSE_STEM and self.fuse and self.stem_u8 is not None and len(nodes) > 1):
-            return False
-        if self.args[1] is None or nodes[1].x_val != nodes[0].dst:
-            return False
-        if any(nodes[0].dst in reads_of[i] for i in range(2, len(nodes))) or self.packed.quant_after.get(0):
-            return False
-        lib = _lib.load()
-        return lib.drnmi_stem_layer1_kernel_name(ctypes.byref(self.stem_u8), ctypes.byref(self.args[1])) is not None
+    def _build_launches(self, src: str, labels_only: bool) -> list:
+        """Walks the nodes once and says for each which launch computes it.  A launch reports under
+        `row`: the front and stem + layer1 under 0, a 64-channel block under conv1's index, a
+        16-channel block under conv2's (conv1 has no args to name a row with), a conv with a folded
+        downsample or the seg classifier under its own."""
+        pk, bufs, ref = self.packed, self.bufs, ctypes.byref
+        nodes = pk.graph.nodes
+        u8 = src == "u8"
+        nhwc = labels_only and self.seg_nhwc_args is not None
+        segf = self.seg_fused if nhwc else None
+        out, done = [], set(self.skip)
+
+        def ptr(v):
+            return bufs[v].data_ptr()
+
+        def add(row, kind, nds, reads, writes, argv, live=None):
+            done.update(nds)
+            quant = tuple(v for k in nds for v in pk.quant_after.get(k, ()))
+            out.append(Launch(row, kind, nds, tuple(v for v in reads if v), writes, quant, argv, live,
+                              f"{kind} {nodes[row].name}"))
+
+        for i, nd in enumerate(nodes):
+            if i in done:
+                continue                          # folded into another launch
+            fused = nd.fused if self.fuse else None
+            reads = () if u8 and i == 0 else (nd.x_val, fused["x2_val"] if fused else nd.r_val)
+            c = 64 if i in self.block64 else 16 if i in self.block16 else 0
+            if u8 and i == 0 and self.front_fused:
+                add(0, "front", (0, 1, 2), reads, (nodes[2].dst,), None,
+                    lambda y=ptr(nodes[2].dst): (self.stem_u8.x, self.front_pack_t.data_ptr(), y, self.n, self.h, self.w))
+            elif u8 and i == 0 and self.stem_fused:
+                add(0, "stem_layer1", (0, 1), reads, (nodes[1].dst,), (ref(self.stem_u8), ref(self.args[1])))
+            elif c:
+                y, pack = nodes[i + 1].dst, (self.block64 if c == 64 else self.block16)[i]
+                add(i if c == 64 else i + 1, f"block{c}", (i, i + 1), (nd.x_val,), (y,),
+                    (ptr(nd.x_val), pack.data_ptr(), ptr(y), self.n, *self.shapes[y]))
+            elif segf is not None and i == segf["conv"]:
+                add(i, "conv_seg", (i, self.seg_idx), reads, ("seg_part",),
+                    (ref(self.args[i]), segf["seg_w"], segf["seg_k_pad"], segf["seg_rows"], ptr("seg_part")))
+            elif nhwc and i == self.seg_idx:
+                add(i, "conv", (i,), reads, ("logits_nhwc",), (ref(self.seg_nhwc_args),))
+            else:
+                add(i, "conv", (fused["ds"], i) if fused else (i,), reads, (nd.dst,),
+                    (ref(self.stem_u8 if u8 and i == 0 else self.args[i]),))
+        return out
 
     def _conv_args(self, nd: ConvNode) -> _lib.ConvArgs:
         pk = self.packed
@@ -908,105 +934,42 @@ class Plan:
         skip = {i for i, nd in enumerate(nodes) if self.fuse and nd.fused_into >= 0}
         if skip != self.skip:
             raise RuntimeError("repack changed the downsample fusion of a live plan")
-        for i, nd in enumerate(nodes):
-            if i in self.skip or i in self.block16:
-                continue
-            self.args[i] = self._conv_args(nd)
+        self.args = self._all_args()
         self.front_pack_t = None
         if self._norm is not None and self.front_fused:   # a u8 plan may run again without a new ingest
             self.front_pack_t = self.packed.front_pack(*self._norm)
-        for i in list(self.block64):
-            self.block64[i] = self.packed.block64_pack(i)
-        for i in list(self.block16):
-            self.block16[i] = self.packed.block16_pack(i)
-        self._setup_seg_nhwc()
+        for c, packs in ((16, self.block16), (64, self.block64)):
+            for i in packs:
+                packs[i] = self.packed.block_pack(c, i)
         if self.stem_u8 is not None:
-            nd = self.packed.graph.nodes[0]
             self.stem_u8.wgt = self.packed.stem_u8_w.data_ptr()
-            self.stem_u8.scale = nd.scale.data_ptr()
-            self.stem_u8.shift = nd.shift.data_ptr()
+            self.stem_u8.scale = nodes[0].scale.data_ptr()
+            self.stem_u8.shift = nodes[0].shift.data_ptr()
+        self._setup_seg()                          # (also drops the launch lists built on the old pointers)
 
     # ------------------------------------------------------------------ execution
     def run_backbone(self, stream: int, timing_hook=None, labels_only: bool = False):
         """labels_only: the seg conv writes the NHWC logits for head_labels_nhwc (when the plan has
-        that form, seg_nhwc_args); the NCHW logits buffer is then not written."""
+        that form, seg_nhwc_args), or is folded into its producer (seg_fused); the NCHW logits buffer
+        is then not written.  timing_hook(row, node of that row, before) brackets every launch; the
+        int8 copies of its outputs are quantised after the closing call."""
         lib = _lib.load()
-        segf = self.seg_fused if labels_only and self.seg_nhwc_args is not None else None
-        front = self.src == "u8" and self.front_fused
-        fused_stem = self.src == "u8" and self.stem_fused and not front
         nodes = self.packed.graph.nodes
-        blocks, blocks16 = self.block64, self.block16
-        for i, (a, nd) in enumerate(zip(self.args, nodes)):
-            if a is None or (i == 1 and fused_stem) or (front and i in (1, 2)) or (i - 1) in blocks:
-                continue                          # folded into another launch
-            # (conv1 of a fused 16-channel BasicBlock has args None: it runs with its conv2)
-            if (i - 1) in blocks16:               # conv1 + conv2 as one launch, reported under conv2's index
-                                                  # (block64 reports under conv1's)
-                if timing_hook is not None:
-                    timing_hook(i, nd, True)
-                h, w = self.shapes[nd.dst]
-                _lib.check(lib.drnmi_basic_block16(self.bufs[nodes[i - 1].x_val].data_ptr(), blocks16[i - 1].data_ptr(),
-                                                   self.bufs[nd.dst].data_ptr(), self.n, h, w,
-                                                   ctypes.c_void_p(stream)), f"basic_block16 {nodes[i - 1].name}")
-                if timing_hook is not None:
-                    timing_hook(i, nd, False)
-                for v in self.packed.quant_after.get(i, ()):
-                    self._quantize(lib, v, stream)
-                continue
-            if i in blocks:                       # conv1 + conv2 of a 64-channel BasicBlock
-                if timing_hook is not None:
-                    timing_hook(i, nd, True)
-                h, w = self.shapes[nd.dst]
-                _lib.check(lib.drnmi_basic_block64(self.bufs[nd.x_val].data_ptr(), blocks[i].data_ptr(),
-                                                   self.bufs[nodes[i + 1].dst].data_ptr(), self.n, h, w,
-                                                   ctypes.c_void_p(stream)), f"basic_block64 {nd.name}")
-                if timing_hook is not None:
-                    timing_hook(i, nd, False)
-                for v in self.packed.quant_after.get(i + 1, ()):
-                    self._quantize(lib, v, stream)
-                continue
-            if front and i == 0:
-                if timing_hook is not None:
-                    timing_hook(0, nd, True)
-                _lib.check(lib.drnmi_video_front_u8(self.stem_u8.x, self.front_pack_t.data_ptr(),
-                                                    self.bufs[self.packed.graph.nodes[2].dst].data_ptr(),
-                                                    self.n, self.h, self.w, ctypes.c_void_p(stream)), "video_front_u8")
-                if timing_hook is not None:
-                    timing_hook(0, nd, False)
-                continue
-            if i == 0 and self.src == "u8":
-                a = self.stem_u8
-            if labels_only and i == self.seg_idx and self.seg_nhwc_args is not None:
-                if segf is not None:
-                    continue                      # folded into its producer's epilogue
-                a = self.seg_nhwc_args
-            if segf is not None and i == segf["conv"]:
-                if timing_hook is not None:
-                    timing_hook(i, nd, True)
-                _lib.check(lib.drnmi_conv_stag_seg(ctypes.byref(a), segf["seg_w"], segf["seg_k_pad"], segf["seg_rows"],
-                                                   self.bufs["seg_part"].data_ptr(), ctypes.c_void_p(stream)),
-                           f"conv_stag_seg {nd.name}")
-                if timing_hook is not None:
-                    timing_hook(i, nd, False)
-                continue
+        stream = ctypes.c_void_p(stream)
+        for l in self.launches(self.src, labels_only):
             if timing_hook is not None:
-                timing_hook(i, nd, True)
-            if i == 0 and fused_stem:
-                _lib.check(lib.drnmi_stem_layer1(ctypes.byref(a), ctypes.byref(self.args[1]), ctypes.c_void_p(stream)),
-                           "stem_layer1")
-            else:
-                _lib.check(lib.drnmi_conv2d_bn_act(ctypes.byref(a), ctypes.c_void_p(stream)), f"conv {nd.name}")
+                timing_hook(l.row, nodes[l.row], True)
+            l.issue(lib, stream)
             if timing_hook is not None:
-                timing_hook(i, nd, False)
-            for v in self.packed.quant_after.get(i, ()):
+                timing_hook(l.row, nodes[l.row], False)
+            for v in l.quant:
                 self._quantize(lib, v, stream)
 
-    def _quantize(self, lib, v: str, stream: int):
+    def _quantize(self, lib, v: str, stream: ctypes.c_void_p):
         """bf16 value -> its int8 copy "q:<v>" (include/drnmi.h drnmi_quantize_i8)."""
         src, dst = self.bufs[v], self.bufs["q:" + v]
         _lib.check(lib.drnmi_quantize_i8(src.data_ptr(), self.packed.value_code(v), dst.data_ptr(), dst.numel(),
-                                         1.0 / float(self.packed.act_scales[v]), ctypes.c_void_p(stream)),
-                   f"quantize_i8 {v}")
+                                         1.0 / float(self.packed.act_scales[v]), stream), f"quantize_i8 {v}")
 
     def ingest_nchw(self, x: torch.Tensor, stream: int):
         self.src = "nchw"

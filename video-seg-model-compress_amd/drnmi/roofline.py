@@ -64,69 +64,45 @@ def node_peaks(plan):
 
 
 def launch_work(plan, video: bool = True):
-    """node_work re-cut along the launches the plan really issues (rows stay index-aligned
-    with plan.args; an absorbed node's row becomes (name, 0, 0)):
-      * a 1x1 downsample folded into its block's last conv (plan.skip, lmodels/drn.py:181-186):
-        its FLOPs and its input + weight bytes move into that launch, and the residual tensor
-        is neither written by the downsample nor read by the conv;
-      * the fused front launch (plan.front_fused: layer0 + layer1 + layer2) or else the fused
-        stem + layer1 launch (plan.stem_fused, drn.py:132-137 + :201-211; video=True: the
-        uint8-frame segment() path): the 16-channel full-resolution intermediates are neither
-        written nor read back."""
-    rows = list(node_work(plan))
-    nodes = plan.packed.graph.nodes
+    """node_work re-cut along the launches the plan really issues (Plan.launches; rows stay
+    index-aligned with plan.args, a launch fills its `row`, an absorbed node's row becomes
+    (name, 0, 0)).  video=True: the uint8-frame segment() path with its fused front or stem + layer1
+    and the labels-only seg forms; False: frames ingested as NCHW, full logits.
+    A launch's FLOPs are the sum over its nodes, its bytes that sum minus the passes the fusion
+    removes: a value written and read only inside the launch (the front's and the stem's 16-channel
+    intermediates, a block's, the residual a folded 1x1 downsample would have written,
+    lmodels/drn.py:181-186) costs neither its write nor its reads, and a value several nodes of the
+    launch read (a fused block's input: conv1 and the residual) is read once."""
+    per_node = node_work(plan)
+    nodes, channels = plan.packed.graph.nodes, plan.packed.graph.channels
+    # (the plan's element size: every fused launch runs bf16, or fp32 nodes, never int8 ones)
     esz = 2 if plan.packed.base == "bf16" else 4
-    for i in sorted(getattr(plan, "skip", ())):
-        j = nodes[i].fused_into
-        n_, fj, bj = rows[j]
-        oh, ow = plan.shapes[nodes[j].dst]
-        res_b = plan.n * oh * ow * nodes[j].conv.out_channels * (1 if nodes[j].i8 else esz)
-        fi, bi = rows[i][1], rows[i][2]
-        rows[j] = (n_, fj + fi, bj - res_b + (bi - res_b))
-        rows[i] = (rows[i][0], 0.0, 0.0)
-    if video and getattr(plan, "front_fused", False):
-        # layer0 + layer1 + layer2 in one launch (drnmi_video_front_u8): neither full-resolution
-        # 16-channel intermediate is written or read back
-        mid = 0.0
-        for k in (0, 1):
-            hk, wk = plan.shapes[nodes[k].dst]
-            mid += plan.n * hk * wk * nodes[k].conv.out_channels * esz
-        rows[0] = (rows[0][0], rows[0][1] + rows[1][1] + rows[2][1], rows[0][2] + rows[1][2] + rows[2][2] - 2 * mid)
-        rows[1] = (rows[1][0], 0.0, 0.0)
-        rows[2] = (rows[2][0], 0.0, 0.0)
-    elif video and getattr(plan, "stem_fused", False):
-        h0, w0 = plan.shapes[nodes[0].dst]
-        mid = plan.n * h0 * w0 * nodes[0].conv.out_channels * esz
-        rows[0] = (rows[0][0], rows[0][1] + rows[1][1], rows[0][2] + rows[1][2] - 2 * mid)
-        rows[1] = (rows[1][0], 0.0, 0.0)
-    for i in getattr(plan, "block64", {}):
-        # a 64-channel BasicBlock in one launch (drnmi_basic_block64): the intermediate is neither
-        # written nor read back, and the block input is read once (conv1 and the residual)
-        hb, wb = plan.shapes[nodes[i].dst]
-        mid = plan.n * hb * wb * 64 * esz
-        rows[i] = (rows[i][0], rows[i][1] + rows[i + 1][1], rows[i][2] + rows[i + 1][2] - 3 * mid)
-        rows[i + 1] = (rows[i + 1][0], 0.0, 0.0)
-    for i in getattr(plan, "block16", {}):
-        # a 16-channel BasicBlock in one launch (drnmi_basic_block16), reported under the second
-        # conv's index: the same three tensor passes saved
-        hb, wb = plan.shapes[nodes[i].dst]
-        mid = plan.n * hb * wb * 16 * esz
-        rows[i + 1] = (rows[i + 1][0], rows[i][1] + rows[i + 1][1], rows[i][2] + rows[i + 1][2] - 3 * mid)
-        rows[i] = (rows[i][0], 0.0, 0.0)
-    segf = getattr(plan, "seg_fused", None)
-    if video and segf is not None and plan.labels_path() == "seg2":
-        # the seg classifier in the last conv's epilogue (drnmi_conv_stag_seg): the conv's output is
-        # neither written nor read back, nor are the fp32 logits; the two partial-logit planes are
-        # written by it and read by the head instead
-        j, i = segf["conv"], plan.seg_idx
-        oh, ow = plan.shapes[nodes[j].dst]
-        act = plan.n * oh * ow * nodes[j].conv.out_channels * (1 if nodes[j].i8 else esz)   # int8 nets: int8
-        lh, lw = plan.shapes[nodes[i].dst]
-        logits = plan.n * lh * lw * nodes[i].conv.out_channels * 4
-        part = 2 * plan.n * lh * lw * plan.SEG_NHWC_CS * 4
-        rows[j] = (rows[j][0], rows[j][1] + rows[i][1], rows[j][2] + rows[i][2] - 2 * act - logits + part)
-        rows[i] = (rows[i][0], 0.0, 0.0)
-        rows[-1] = (rows[-1][0], rows[-1][1], rows[-1][2] - logits + part)
+    rows = [(name, 0.0, 0.0) for name, _, _ in per_node]
+    rows[-1] = per_node[-1]
+    labels_only = video and plan.labels_path() != "nchw"
+    for l in plan.launches("u8" if video and plan.stem_u8 is not None else "nchw", labels_only):
+        flops = sum(per_node[k][1] for k in l.nodes)
+        nbytes = sum(per_node[k][2] for k in l.nodes)
+        if l.kind == "conv_seg":
+            # not the rule above: the classifier in the last conv's epilogue (drnmi_conv_stag_seg) trades
+            # the fp32 logits for two partial-logit planes, which it writes and the head reads instead
+            # (so the head's row moves too), and the conv's output it keeps back is int8 in int8 nets
+            j, i = l.nodes
+            oh, ow = plan.shapes[nodes[j].dst]
+            act = plan.n * oh * ow * nodes[j].conv.out_channels * (1 if nodes[j].i8 else esz)
+            lh, lw = plan.shapes[nodes[i].dst]
+            logits = plan.n * lh * lw * nodes[i].conv.out_channels * 4
+            part = 2 * plan.n * lh * lw * plan.SEG_NHWC_CS * 4
+            nbytes += part - 2 * act - logits
+            rows[-1] = (rows[-1][0], rows[-1][1], rows[-1][2] - logits + part)
+        else:
+            reads = [v for k in l.nodes for v in (nodes[k].src, nodes[k].res) if v]
+            inside = {nodes[k].dst for k in l.nodes} - set(l.writes)
+            for v in set(reads):
+                h, w = plan.shapes[v]
+                passes = reads.count(v) + 1 if v in inside else reads.count(v) - 1
+                nbytes -= passes * plan.n * h * w * channels[v] * esz
+        rows[l.row] = (rows[l.row][0], flops, nbytes)
     return rows
 
 
