@@ -30,17 +30,40 @@ extern "C" {
  * against another header must not pass them: check drnmi_abi_version() == DRNMI_ABI_VERSION and
  * drnmi_conv_args_size() == sizeof(drnmi_conv_args) once after loading the library (drnmi/_lib.py
  * does, and refuses a mismatched library). */
-#define DRNMI_ABI_VERSION 5
+#define DRNMI_ABI_VERSION 6
 int32_t drnmi_abi_version(void);
 int64_t drnmi_conv_args_size(void);
 
-enum drnmi_dtype { DRNMI_F32 = 0, DRNMI_BF16 = 1, DRNMI_U8 = 2, DRNMI_I64 = 3, DRNMI_I8 = 4, DRNMI_F32X3 = 5 };
+enum drnmi_dtype { DRNMI_F32 = 0, DRNMI_BF16 = 1, DRNMI_U8 = 2, DRNMI_I64 = 3, DRNMI_I8 = 4, DRNMI_F32X3 = 5,
+                   DRNMI_F8 = 6 };
 /* DRNMI_F32X3 (conv dtype only, the "fp32x" precision mode): x, res and y are fp32 NHWC as in
  * DRNMI_F32, wgt is three bf16 planes [3][cout_pad][k_pad] with w = w1 + w2 + w3 (an exact split
  * of the fp32 weight), and the conv runs fp32-accurate arithmetic on the bf16 MFMA pipe: each
  * fp32 activation is split the same way in registers and the six products above 2^-24 are
  * accumulated in fp32 (csrc/conv_x6.hip).  Requires cin >= 32 (power of two), ks 1 or 3,
  * out_dtype DRNMI_F32. */
+/* DRNMI_F8 (the "fp8" precision mode; version 6): OCP e4m3fn bytes (maximum 448, no infinities,
+ * round to nearest even).  The arithmetic, stated once for the kernels and for tests/fp8_ref.py:
+ *   element    e4m3(v) = the e4m3fn value nearest to clamp(v, -448, 448), ties to even; the clamp is
+ *              done in fp32 before the conversion, so saturation does not depend on the conversion
+ *              instruction's mode (torch: v.clamp(-448, 448).to(torch.float8_e4m3fn)).
+ *   weights    per output channel: a = absmax(row), q = e4m3(w * 448 / a), s_w = a / 448 (1 for an
+ *              all-zero row); packed [cout_pad][k_pad], k = (kh*ks + kw)*cin + ci.
+ *   activations per tensor.  A calibrated scale s (DRNSeg._act_scales, "clip = 127 s", shared with
+ *              int8) gives the fp8 scale s8 = s * 127 / 448: q = e4m3(x * (1 / s8)).
+ *   launch     dtype = DRNMI_F8: x, wgt, res are e4m3 bytes; scale non-NULL = s_w * s8_x * bn_scale.
+ *              acc = fp32 sum of the exact products (v_mfma_f32_16x16x128_f8f6f4, K in steps of 128);
+ *              v = acc * scale[co] + shift[co] (fmul then fadd, no contraction);
+ *              v += f32(res) * res_scale (residual, if any); ReLU (if set);
+ *              out_dtype DRNMI_F8 stores e4m3(v * out_scale), DRNMI_BF16 / DRNMI_F32 store v with
+ *              the strided forms of the int8 launches (NCHW logits, NHWC rows with y_sp = cs).
+ *              drnmi_conv_args does not grow: scale, res_scale and out_scale are reused.
+ *   kernels    cin >= 64 (power of two), ks 1 or 3, cout_pad % 128 == 0, k_pad == k: conv_f8_kernel
+ *              (any stride / dilation / ragged tiles; the 1x1s on its two-workgroups-per-CU form
+ *              conv_f8_occ2_kernel); whole 256-pixel output rows of a stride-1 3x3
+ *              with cin % 256 == 0 and cout % 256 == 0 take the strip-staged conv_f8_stag_kernel
+ *              (DRNMI_TILE_STAG forces it).  DRNMI_TILE_W1 / DRNMI_TILE_W1H, drnmi_conv_stag_seg, a
+ *              unit mask and a fused second input have no fp8 form: DRNMI_ENOTSUP. */
 
 enum drnmi_status {
   DRNMI_OK = 0,
@@ -298,6 +321,11 @@ int drnmi_weight_unit_mask(const void* wgt, int32_t dtype, int32_t rows_pad, int
  *     n == 0: DRNMI_OK, nothing launched. */
 #define DRNMI_HIST_BINS 32768
 int drnmi_quantize_i8(const void* x, int32_t dtype, int8_t* y, int64_t n, float inv_scale, void* stream);
+/* The fp8 sibling (DRNMI_F8 above): y[i] = e4m3(x[i] * inv_scale) over n elements, x BF16 or F32, one
+ * fp32 multiply, the clamp to +-448, round to nearest even; any n >= 1 (16 elements per lane, a
+ * scalar tail).  NULL pointers, x or y not 16-byte aligned, n <= 0, another dtype or a non-positive
+ * inv_scale: DRNMI_EINVAL before any HIP call.  One streaming kernel on the caller's stream, no allocation (graph-capturable). */
+int drnmi_quantize_f8(const void* x, int32_t dtype, int64_t n, float inv_scale, uint8_t* y, void* stream);
 int drnmi_absmax(const void* x, int32_t dtype, int64_t n, float* out, void* stream);
 int drnmi_abs_histogram(const void* x, int32_t dtype, int64_t n, int64_t* hist, void* stream);
 

@@ -51,6 +51,19 @@ __device__ __forceinline__ void split3(const float4& lo4, const float4& hi4, bf1
   b3 = __builtin_bit_cast(bf16x8, make_uint4(u3[0], u3[1], u3[2], u3[3]));
 }
 
+// OCP e4m3fn bytes (include/drnmi.h DRNMI_F8).  f8_t tags the element type of the fp8 kernels.
+struct f8_t { uint8_t v; };
+constexpr float kF8Max = 448.f;
+__device__ __forceinline__ float f8_clamp(float v) { return fminf(fmaxf(v, -kF8Max), kF8Max); }
+// four values -> four e4m3 bytes (byte j = value j): the clamp, then two v_cvt_pk_fp8_f32 (RNE)
+__device__ __forceinline__ uint32_t pk_f8x4(float a, float b, float c, float d) {
+  int w = __builtin_amdgcn_cvt_pk_fp8_f32(f8_clamp(a), f8_clamp(b), 0, false);
+  w = __builtin_amdgcn_cvt_pk_fp8_f32(f8_clamp(c), f8_clamp(d), w, true);
+  return static_cast<uint32_t>(w);
+}
+template <int J>
+__device__ __forceinline__ float f8_to_f32(uint32_t w) { return __builtin_amdgcn_cvt_f32_fp8(static_cast<int>(w), J); }
+
 template <typename T> struct Elem;
 template <> struct Elem<float> {
   static constexpr int kDtype = DRNMI_F32;

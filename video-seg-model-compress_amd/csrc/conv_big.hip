@@ -48,6 +48,10 @@ __device__ __forceinline__ void conv_big_body(const drnmi_conv_args& p) {
   using K = KT<T>;
   using C = BigCfg<WCO, WC, NST, BK, NWP, K::ESZ>;
   static_assert(!SPARSE || K::ESZ == 2, "unit skipping: bf16 only");
+  // fp8: one MFMA covers a whole row (128 B, or a 64-B row in its low half): one substep per K step
+  constexpr bool F8 = kIsF8<T>;
+  static_assert(!F8 || (!STRIP && !X2 && !PERSIST), "fp8: the plain per-tap gather");
+  constexpr int NSUB = F8 ? 1 : C::SUB;
   static_assert(!STRIP || (KS == 3 && NST == 2 && C::ROWB == 128 && !PERSIST && !SPARSE && !X2 && C::NW == 8),
                 "strip mode: the 256 x 256 3x3 instantiations with 128-B rows (bf16 BK 64, int8 BK 128)");
   constexpr int CE = 16 / K::ESZ;   // elements per 16-B chunk
@@ -263,20 +267,30 @@ __device__ __forceinline__ void conv_big_body(const drnmi_conv_args& p) {
       // last group re-fetches its own strip, identical bytes, into the buffer being read)
       const int sg = (t / 3 + 1 < ngroups) ? t / 3 + 1 : ngroups - 1;
       constexpr int GL = STRIP ? C::A_INSTR + 2 : C::GLDS;
-      constexpr int NG = C::SUB * C::GR;
+      constexpr int NG = NSUB * C::GR;
       constexpr int PPG = (GL + C::GR - 1) / C::GR;   // DMA pieces per group (first substep)
       const StepP sp = step_params(kt_at(t + NST - 1 < nlive ? t + NST - 1 : nlive - 1));
       const int nst = (t + NST - 1) % NST;
       constexpr int PFD = 1;                     // fragment prefetch distance in MFMA groups
       constexpr int NAF = PFD + 1;               // A-fragment ring depth
       typename K::frag af[NAF][C::FPG], bfr[2][C::FN];
-      auto load_a = [&](typename K::frag (&dst)[C::FPG], int q) {
+      // fp8: the lane group's 32 B of row r -- chunks fq and 4 + fq of a 128-B row, or chunk fq of a
+      // 64-B row over zeros (e4m3 +0: those K positions add nothing)
+      [[maybe_unused]] auto read_f8 = [&](const char* base, int r) {
+        const i32x4 lo = *reinterpret_cast<const i32x4*>(base + r * C::ROWB + swzb<C::ROWB>(r, fq) * 16);
+        i32x4 hi = i32x4{0, 0, 0, 0};
+        if constexpr (C::ROWB == 128) hi = *reinterpret_cast<const i32x4*>(base + r * C::ROWB + swzb<C::ROWB>(r, 4 + fq) * 16);
+        if constexpr (F8) return K::join(lo, hi);
+        else return lo;
+      };
+      auto load_a =[&](typename K::frag (&dst)[C::FPG], int q) {
         const int c = (q / C::GR) * 4 + fq;
 #pragma unroll
         for (int h = 0; h < C::FPG; ++h) {
           const int r = wc * WCO + ((q % C::GR) * C::FPG + h) * 16 + fr;
           // unconditional: a branch around an LDS read makes the compiler fall back to lgkmcnt(0)
-          dst[h] = *reinterpret_cast<const typename K::frag*>(sa + r * C::ROWB + swzb<C::ROWB>(r, c) * 16);
+          if constexpr (F8) dst[h] = read_f8(sa, r);
+          else dst[h] = *reinterpret_cast<const typename K::frag*>(sa + r * C::ROWB + swzb<C::ROWB>(r, c) * 16);
         }
       };
       auto load_b = [&](typename K::frag (&dst)[C::FN], int sub) {
@@ -284,7 +298,9 @@ __device__ __forceinline__ void conv_big_body(const drnmi_conv_args& p) {
 #pragma unroll
         for (int fn = 0; fn < C::FN; ++fn) {
           const int r = wp * C::PXW + fn * 16 + fr;
-          if constexpr (STRIP) {
+          if constexpr (F8) {
+            dst[fn] = read_f8(sb, r);
+          } else if constexpr (STRIP) {
             const int R = r + kwd;
             dst[fn] = *reinterpret_cast<const typename K::frag*>(sb + R * C::ROWB + (c ^ (R & 7)) * 16);
           } else {
@@ -357,6 +373,13 @@ __device__ __forceinline__ void conv_big_body(const drnmi_conv_args& p) {
              cur_co0 + C::BCO <= p.cout;
       if (x4) store_tile_x4<C::FM, WCO, C::FN>(p, acc, cur_px0, cur_co0, wc, wp, fr, fq);
       else store_tile<C::FM, WCO, C::FN, DEFER>(p, acc, cur_px0, cur_co0, wc, wp, fr, fq);
+    } else if constexpr (F8) {
+      // whole tile of a dense, 16-B aligned e4m3 NHWC output: 16-B pieces
+      const bool x4 = C::FM % 4 == 0 && p.out_dtype == DRNMI_F8 && p.y_sc == 1 && p.y_sp == p.cout &&
+          p.y_sn == static_cast<int64_t>(p.ho) * p.wo * p.cout && ((reinterpret_cast<uintptr_t>(p.y) | reinterpret_cast<uintptr_t>(p.res)) & 15) == 0 &&
+          cur_px0 + kBPX <= p.n * p.ho * p.wo && cur_co0 + C::BCO <= p.cout;
+      if (x4) store_tile_f8_x4<C::FM, WCO, C::FN>(p, acc, cur_px0, cur_co0, wc, wp, fr, fq);
+      else store_tile_f8<C::FM, WCO, C::FN>(p, acc, cur_px0, cur_co0, wc, wp, fr, fq);
     } else {
       bool x4 = false;
       if constexpr (C::FM % 4 == 0)
@@ -398,6 +421,22 @@ template <int KS, int WCO, int WC, int NST, int BK>
 __global__ void __launch_bounds__(64 * 4 * WC, 1)
 conv_i8_kernel(const drnmi_conv_args p) {
   conv_big_body<int8_t, KS, WCO, WC, NST, BK, false, 4, false>(p);
+}
+
+// fp8 (DRNMI_F8, OCP e4m3): the same pipeline and LDS image over e4m3 bytes, BK channels per K
+// step as the int8 rows, v_mfma_f32_16x16x128_f8f6f4 into fp32 accumulators (one MFMA per fragment
+// pair and K step: KT<f8_t>), store_tile_f8 epilogue
+template <int KS, int WCO, int WC, int NST, int BK>
+__global__ void __launch_bounds__(64 * 4 * WC, 1)
+conv_f8_kernel(const drnmi_conv_args p) {
+  conv_big_body<f8_t, KS, WCO, WC, NST, BK, false, 4, false>(p);
+}
+
+// ... and at two workgroups per CU for the 1x1s, as conv_i8_occ2_kernel (64-B rows: the K-64 step)
+template <int KS, int WCO, int WC, int NST, int BK>
+__global__ void __launch_bounds__(64 * 4 * WC, 2) __attribute__((amdgpu_waves_per_eu(2, 2)))
+conv_f8_occ2_kernel(const drnmi_conv_args p) {
+  conv_big_body<f8_t, KS, WCO, WC, NST, BK, false, 4, false>(p);
 }
 
 // the same body at two workgroups per CU (register budget 256, 2 x 24 KB of LDS with 64-B rows):
@@ -685,6 +724,29 @@ hipError_t launch_i8(const drnmi_conv_args& p, hipStream_t s) {
   return hipGetLastError();
 }
 
+template <int KS, int WCO, int WC, int NST, int BK, bool OCC2 = false>
+hipError_t launch_f8(const drnmi_conv_args& p, hipStream_t s) {
+  using C = BigCfg<WCO, WC, NST, BK, 4, 1>;
+  void (*kernel)(const drnmi_conv_args);
+  if constexpr (OCC2) kernel = &conv_f8_occ2_kernel<KS, WCO, WC, NST, BK>;
+  else kernel = &conv_f8_kernel<KS, WCO, WC, NST, BK>;
+  static bool attr_set = false;
+  if (!attr_set) {
+    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, C::LDS);
+    if (e != hipSuccess) return e;
+    attr_set = true;
+  }
+  const int64_t M = static_cast<int64_t>(p.n) * p.ho * p.wo;
+  const int64_t blocks = ((M + kBPX - 1) / kBPX) * ((p.cout + C::BCO - 1) / C::BCO);
+  hipLaunchKernelGGL(kernel, dim3(static_cast<unsigned>(blocks)), dim3(C::THREADS), C::LDS, s, p);
+  return hipGetLastError();
+}
+
+template <int KS, int WCO, int WC, int NST, int BK>
+hipError_t launch_f8_occ2(const drnmi_conv_args& p, hipStream_t s) {
+  return launch_f8<KS, WCO, WC, NST, BK, true>(p, s);
+}
+
 template <int KS, int WCO, int WC, int NST, int BK>
 hipError_t launch_i8_occ2(const drnmi_conv_args& p, hipStream_t s) {
   return launch_i8<KS, WCO, WC, NST, BK, true>(p, s);
@@ -768,6 +830,18 @@ const I8Variant& i8_variant_row(int v) {
   return k[v];
 }
 
+// the int8 rows' tiles
+const I8Variant& f8_variant_row(int v) {
+  static const I8Variant k[5] = {
+    {256, I8_ROWS(conv_f8_kernel, launch_f8, 128, 2, 2, 128)},             // 2 x 64 KB
+    {128, I8_ROWS(conv_f8_kernel, launch_f8, 128, 1, 3, 128)},             // 3 x 48 KB
+    {256, I8_ROWS(conv_f8_kernel, launch_f8, 128, 2, 4, 64)},              // 4 x 32 KB, K-64 steps
+    {128, I8_ROWS(conv_f8_kernel, launch_f8, 128, 1, 4, 64)},              // 4 x 24 KB, K-64 steps
+    {128, I8_ROWS(conv_f8_occ2_kernel, launch_f8_occ2, 128, 1, 2, 64)},    // 2 x 24 KB, K-64 steps, 2 WGs / CU
+  };
+  return k[v];
+}
+
 // a 256-pixel tile is a run of one output row, the strip of 256 + 2 dil rows fits its buffer
 bool strip_ok(const drnmi_conv_args& p) {
   return p.ks == 3 && p.stride == 1 && p.pad == p.dil && p.dil >= 1 && p.dil <= 4 && p.wo % kBPX == 0 &&
@@ -799,6 +873,19 @@ bool i8_conv_supported(const drnmi_conv_args& p) {
          p.cout_pad % 128 == 0 && (p.ks == 1 || p.ks == 3) && p.k == p.ks * p.ks * p.cin && p.k_pad == p.k &&
          static_cast<int64_t>(p.n) * p.h * p.w * p.cin < (int64_t(1) << 31) && p.h < 16384 && p.w < 16384 &&
          (p.out_dtype == DRNMI_F32 || p.out_dtype == DRNMI_BF16 || p.out_dtype == DRNMI_I8);
+}
+
+// fp8: the int8 family's shapes (e4m3 bytes, a non-NULL scale)
+bool f8_conv_supported(const drnmi_conv_args& p) {
+  return p.dtype == DRNMI_F8 && p.scale != nullptr && p.cin >= 64 && (p.cin & (p.cin - 1)) == 0 &&
+         p.cout_pad % 128 == 0 && (p.ks == 1 || p.ks == 3) && p.k == p.ks * p.ks * p.cin && p.k_pad == p.k &&
+         p.x2 == nullptr && p.unit_mask == nullptr &&
+         static_cast<int64_t>(p.n) * p.h * p.w * p.cin < (int64_t(1) << 31) && p.h < 16384 && p.w < 16384 &&
+         (p.out_dtype == DRNMI_F32 || p.out_dtype == DRNMI_BF16 || p.out_dtype == DRNMI_F8);
+}
+// fp8 staggered strip tile: the int8 one's geometry (128-channel K steps walked in pairs of tap groups)
+bool f8_stag_ok(const drnmi_conv_args& p) {
+  return p.cout % 256 == 0 && p.cin % 256 == 0 && p.cout <= p.cout_pad && strip_ok(p);
 }
 
 // int8 strip-staged B: the 256 x 256 tile with 128-B rows (i8_variant_row(0): cin >= 128, cout % 256 == 0)

@@ -174,6 +174,22 @@ ConvRoute i8_route(const drnmi_conv_args& p) {
   return take(&v.k[ks3]);
 }
 
+// --- fp8 (DRNMI_F8): conv_f8_kernel on the int8 rows' tiles (128-B rows at cin >= 128, the K-64
+// step shape at cin == 64); the row-aligned 3x3 launches i8_stag_ok's geometry admits take the
+// strip-staged conv_f8_stag_kernel (DRNMI_TILE_STAG forces it and refuses other shapes).  The
+// one-wave-per-SIMD tiles have no fp8 form.
+ConvRoute f8_route(const drnmi_conv_args& p) {
+  if (!f8_conv_supported(p)) return refuse(DRNMI_ENOTSUP);
+  if (p.tile == DRNMI_TILE_W1 || p.tile == DRNMI_TILE_W1H) return refuse(DRNMI_ENOTSUP);
+  // 1x1: the two-workgroups-per-CU tile, as int8 (i8_variant)
+  const I8Variant& v = f8_variant_row(p.ks == 1 ? kI8Occ2 : (p.cin >= 128 ? 0 : 2) + (p.cout % 256 == 0 ? 0 : 1));
+  if (!rows_exist(p, v.bco)) return refuse(DRNMI_EINVAL);
+  const int ks3 = p.ks == 3;
+  if (ks3 && f8_stag_ok(p)) return take(stag_f8_kernel());
+  if (p.tile == DRNMI_TILE_STAG) return refuse(DRNMI_ENOTSUP);
+  return take(&v.k[ks3]);
+}
+
 // --- conv_x6.  A drnmi_conv_args.tile >= 0 forces variant tile % 6 and, when tile >= 6, tile / 6
 // split-K partitions (tests, micro-benchmarks; split-K only with a caller workspace).
 // 128-channel layers take the two-per-CU 128 x 128 tile: D-22 layer4's five launches 1631-1649 ->
@@ -304,6 +320,8 @@ ConvRoute conv_route(const drnmi_conv_args& p) {
   if (p.k_pad < p.k || p.k_pad % kBK != 0 || p.stride <= 0 || p.dil <= 0 || p.pad < 0) return refuse(DRNMI_EINVAL);
   if (p.dtype == DRNMI_I8) {
     if (p.out_dtype != DRNMI_I8 && p.out_dtype != DRNMI_BF16 && p.out_dtype != DRNMI_F32) return refuse(DRNMI_EINVAL);
+  } else if (p.dtype == DRNMI_F8) {
+    if (p.out_dtype != DRNMI_F8 && p.out_dtype != DRNMI_BF16 && p.out_dtype != DRNMI_F32) return refuse(DRNMI_EINVAL);
   } else if (p.dtype == DRNMI_F32X3) {
     if (p.out_dtype != DRNMI_F32) return refuse(DRNMI_EINVAL);
   } else if ((p.dtype != DRNMI_BF16 && p.dtype != DRNMI_F32) ||
@@ -315,6 +333,7 @@ ConvRoute conv_route(const drnmi_conv_args& p) {
   // bottom / right edge read zeros (an asymmetric pad; conv_x6 bounds-checks every tap)
   if (p.y_sr == 0 && !conv_geometry(p)) return refuse(DRNMI_EINVAL);
   if (p.dtype == DRNMI_I8) return i8_route(p);       // int8: one kernel family
+  if (p.dtype == DRNMI_F8) return f8_route(p);       // fp8: its own family too
   if (p.dtype == DRNMI_F32X3) return x6_route(p);
   if (p.tile >= DRNMI_TILE_DMA128 || (p.tile < 0 && (big_conv_supported(p) || halo_conv_supported(p)))) return big_route(p);
   if (p.x2 != nullptr) return refuse(DRNMI_ENOTSUP);          // fused second input: LDS-DMA kernels only
@@ -338,6 +357,7 @@ struct SegRoute {
 // staggered one (the same partial logits, bit for bit: the bit-identity test).
 SegRoute seg_route(const drnmi_conv_args& p) {
   if (p.algo != DRNMI_ALGO_IGEMM || p.src_u8) return {DRNMI_EINVAL, nullptr};
+  if (p.dtype == DRNMI_F8) return {DRNMI_ENOTSUP, nullptr};   // no seg-fused fp8 form
   const bool i8 = p.dtype == DRNMI_I8;
   // int8 nets: the conv's int8 output (out_dtype I8, quantised with out_scale) feeds int8 seg
   // weights; int32 partials

@@ -67,6 +67,10 @@ struct I8Variant {
 };
 const I8Variant& i8_variant_row(int v);
 constexpr int kI8Occ2 = 4;
+// fp8 (DRNMI_F8): the same five tiles
+const I8Variant& f8_variant_row(int v);
+bool f8_conv_supported(const drnmi_conv_args& p);      // dtype DRNMI_F8, cin >= 64, scale non-NULL
+bool f8_stag_ok(const drnmi_conv_args& p);
 bool big_conv_supported(const drnmi_conv_args& p);
 bool i8_conv_supported(const drnmi_conv_args& p);      // dtype DRNMI_I8, cin >= 64 (config C5)
 bool strip_ok(const drnmi_conv_args& p);
@@ -80,6 +84,7 @@ bool i8_w1h_ok(const drnmi_conv_args& p);
 
 // conv_stag.hip: the strip tile with staggered SIMD partners: 3x3 stride-1, wo % 256 == 0, cin % 128 == 0
 const ConvKernel* stag_kernel(bool i8, bool tile128, bool x2);
+const ConvKernel* stag_f8_kernel();
 const SegKernel* stag_seg_kernel(bool i8);
 // conv_w1.hip: the same tile as 4 waves of 128 x 128 (one per SIMD), and as 128 x 128 tiles of 4
 // waves of 64 x 64 (two workgroups per CU); bit-identical to conv_stag_kernel

@@ -150,6 +150,8 @@ __device__ __forceinline__ void conv_stag_body(const drnmi_conv_args& p, const S
   constexpr int FM = C::FM, GR = FM / 2, AI = C::A_INSTR, BCO = 2 * WCO;
   static_assert(C::ROWB == 128 && C::FN == 4 && (WCO == 128 || WCO == 64) && AI == WCO / 32, "stag tile geometry");
   constexpr int CE = 16 / K::ESZ;
+  constexpr bool F8 = kIsF8<T>;
+  static_assert(!F8 || (!X2 && !SEGF && WCO == 128), "fp8: the 256-channel tile, no fused forms");
   constexpr int AB = C::A_BYTES;                     // 32 KB per A stage
   extern __shared__ __attribute__((aligned(16))) char smem[];
 
@@ -342,7 +344,30 @@ __device__ __forceinline__ void conv_stag_body(const drnmi_conv_args& p, const S
     using IK = std::integral_constant<int, KW>;
     using Z = std::integral_constant<int, 0>;
     using O = std::integral_constant<int, 1>;
-    if constexpr (U == 0) {
+    // fp8: a fragment is a lane group's whole 128-B row share (chunks fq and 4 + fq: a_base / b_base
+    // [0] and [1]) and one MFMA per fragment pair covers the K step, so a phase is half of the
+    // step's channel fragments (FM / 2, one per slot qg) against all four pixel fragments, which
+    // substep 0 reads once and substep 1 reuses from registers.  Plain LDS reads, the next slot's A
+    // fragment issued ahead of this slot's MFMAs; the compiler counts lgkmcnt.  Every read lies in a
+    // phase where the bf16 / int8 form reads the same buffers, so the hazard table above holds; the
+    // DMA pieces, vmcnt waits and barriers below are shared.
+    [[maybe_unused]] auto rd8 = [&](int lo_off, int hi_off) {
+      const i32x4 lo = *reinterpret_cast<const i32x4*>(smem + lo_off);
+      const i32x4 hi = *reinterpret_cast<const i32x4*>(smem + hi_off);
+      if constexpr (F8) return K::join(lo, hi);
+      else return lo;
+    };
+    [[maybe_unused]] auto load_a8 = [&](int fm) {
+      return rd8(a_base[0] + STAGE * AB + fm * 2048, a_base[1] + STAGE * AB + fm * 2048);
+    };
+    if constexpr (F8) {
+      if constexpr (U == 0) {
+#pragma unroll
+        for (int fn = 0; fn < 4; ++fn)
+          bfr[0][fn] = rd8(b_base[KW][0] + GP * kStripBytes + fn * 2048, b_base[KW][1] + GP * kStripBytes + fn * 2048);
+      }
+      af[0][0] = load_a8(U * GR);
+    } else if constexpr (U == 0) {
       load_b(bfr[0], IG{}, IK{}, Z{});
       load_a(af[0], IS{}, Z{}, Z{});
     }
@@ -357,6 +382,12 @@ __device__ __forceinline__ void conv_stag_body(const drnmi_conv_args& p, const S
     };
 #pragma unroll
     for (int qg = 0; qg < GR; ++qg) {
+      if constexpr (F8) {
+        if (qg + 1 < GR) af[(qg + 1) & 1][0] = load_a8(U * GR + qg + 1);
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int fn = 0; fn < 4; ++fn) acc[U * GR + qg][fn] = K::mma(af[qg & 1][0], bfr[0][fn], acc[U * GR + qg][fn]);
+      } else {
       if (qg == 0) group_reads(std::integral_constant<int, 0>{});
       if (qg == 1) group_reads(std::integral_constant<int, 1>{});
       if (qg == 2) group_reads(std::integral_constant<int, 2>{});
@@ -371,6 +402,7 @@ __device__ __forceinline__ void conv_stag_body(const drnmi_conv_args& p, const S
       for (int h = 0; h < 2; ++h)
 #pragma unroll
         for (int fn = 0; fn < 4; ++fn) acc[qg * 2 + h][fn] = K::mma(af[qg & 1][h], bfr[U][fn], acc[qg * 2 + h][fn]);
+      }
       if constexpr (U == 0) { if (qg < AI) issue_a(ta, STAGE ^ 1, qg); }
       if constexpr (KW == 0 && U == 1) { if (qg < 2) issue_next_strip(g, GP ^ 1, qg); }
       if constexpr (KW == 1 && U == 0) { if (qg == 1) issue_next_strip(g, GP ^ 1, 2); }
@@ -525,6 +557,13 @@ __device__ __forceinline__ void conv_stag_body(const drnmi_conv_args& p, const S
   if constexpr (K::ESZ == 2) {
     if (fast_epi) store_tile_x4<FM, WCO, 4>(p, acc, px0, co0, wc, wp, fr, fq);
     else store_tile<FM, WCO, 4, false>(p, acc, px0, co0, wc, wp, fr, fq);
+  } else if constexpr (F8) {
+    // whole tile of a dense, 16-B aligned e4m3 NHWC output (M % 256 == 0, cout % 256 == 0 here): 16-B pieces
+    if (p.out_dtype == DRNMI_F8 && p.y_sc == 1 && p.y_sp == p.cout &&
+          p.y_sn == static_cast<int64_t>(p.ho) * p.wo * p.cout && ((reinterpret_cast<uintptr_t>(p.y) | reinterpret_cast<uintptr_t>(p.res)) & 15) == 0)
+      store_tile_f8_x4<FM, WCO, 4>(p, acc, px0, co0, wc, wp, fr, fq);
+    else
+      store_tile_f8<FM, WCO, 4>(p, acc, px0, co0, wc, wp, fr, fq);
   } else {
     // whole tile of a dense int8 NHWC output (M % 256 == 0 here): 16-B pieces
     if (p.out_dtype == DRNMI_I8 && p.y_sc == 1 && p.y_sp == p.cout && p.y_sn == static_cast<int64_t>(hw_o) * p.cout &&
@@ -545,6 +584,14 @@ conv_stag_kernel(const drnmi_conv_args p) {
 __global__ void __launch_bounds__(512, 1)
 conv_i8_stag_kernel(const drnmi_conv_args p) {
   conv_stag_body<int8_t, false>(p);
+}
+
+// fp8 (DRNMI_F8): e4m3 rows of 128 channels, the int8 LDS image; v_mfma_f32_16x16x128_f8f6f4, one
+// MFMA per fragment pair and K step; store_tile_f8 / store_tile_f8_x4 epilogue (the arithmetic of
+// conv_f8_kernel: the same K order, so the same sums)
+__global__ void __launch_bounds__(512, 1)
+conv_f8_stag_kernel(const drnmi_conv_args p) {
+  conv_stag_body<f8_t, false>(p);
 }
 
 // the 128-channel tile (D-22 layer4: 128 -> 128, with the fused 1x1 stride-2 downsample in
@@ -605,7 +652,7 @@ static hipError_t stag_attrs() {
   static bool attr_set = false;
   if (!attr_set) {
     for (const void* f : {reinterpret_cast<const void*>(&conv_stag_kernel), reinterpret_cast<const void*>(&conv_stag_x2_kernel),
-                          reinterpret_cast<const void*>(&conv_i8_stag_kernel)}) {
+                          reinterpret_cast<const void*>(&conv_i8_stag_kernel), reinterpret_cast<const void*>(&conv_f8_stag_kernel)}) {
       const hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, kStagLds);
       if (e != hipSuccess) return e;
     }
@@ -646,6 +693,11 @@ const ConvKernel* stag_kernel(bool i8, bool tile128, bool x2) {
       {DRNMI_KERNEL_ROW0(conv_stag128_kernel, launch_stag128), DRNMI_KERNEL_ROW0(conv_stag128_x2_kernel, launch_stag128)}};
   static const ConvKernel k8 = DRNMI_KERNEL_ROW0(conv_i8_stag_kernel, launch_stag);
   return i8 ? &k8 : &k[tile128][x2];
+}
+
+const ConvKernel* stag_f8_kernel() {
+  static const ConvKernel k = DRNMI_KERNEL_ROW0(conv_f8_stag_kernel, launch_stag);
+  return &k;
 }
 
 const SegKernel* stag_seg_kernel(bool i8) {

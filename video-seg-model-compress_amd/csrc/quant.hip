@@ -38,6 +38,31 @@ __global__ void __launch_bounds__(256) quantize_kernel(const T* __restrict__ x, 
   }
 }
 
+// fp8 (include/drnmi.h DRNMI_F8): 16 elements per lane per iteration (16-B loads, one 16-B store),
+// x * inv in fp32, the clamp to +-448, packed v_cvt_pk_fp8_f32 (RNE); the last n % 16 elements one
+// lane each
+template <typename T>
+__device__ __forceinline__ uint2 q8_f8(const Vec8<T>& v, float inv) {
+  const T* e = reinterpret_cast<const T*>(&v);
+  float f[8];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) f[j] = __fmul_rn(Elem<T>::to_f32(e[j]), inv);
+  return make_uint2(pk_f8x4(f[0], f[1], f[2], f[3]), pk_f8x4(f[4], f[5], f[6], f[7]));
+}
+template <typename T>
+__global__ void __launch_bounds__(256) quantize_f8_kernel(const T* __restrict__ x, uint8_t* __restrict__ y, int64_t n,
+                                                          float inv) {
+  const int64_t n16 = n / 16;
+  const int64_t stride = static_cast<int64_t>(gridDim.x) * blockDim.x;
+  const int64_t t0 = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
+  for (int64_t i = t0; i < n16; i += stride) {
+    const uint2 a = q8_f8<T>(Vec8<T>::load(x + i * 16), inv), b = q8_f8<T>(Vec8<T>::load(x + i * 16 + 8), inv);
+    *reinterpret_cast<uint4*>(y + i * 16) = make_uint4(a.x, a.y, b.x, b.y);
+  }
+  const int64_t i = n16 * 16 + t0;
+  if (i < n) y[i] = static_cast<uint8_t>(pk_f8x4(__fmul_rn(Elem<T>::to_f32(x[i]), inv), 0.f, 0.f, 0.f) & 0xff);
+}
+
 // max |x| over n8 * 8 elements into *out (as uint bits: |x| >= 0 orders like its bit pattern;
 // NaN (bits above +inf) propagates as the maximum)
 template <typename T>
@@ -181,6 +206,22 @@ extern "C" int drnmi_quantize_i8(const void* x, int32_t dtype, int8_t* y, int64_
                        static_cast<const float*>(x), y, n8, inv_scale);
   else
     return DRNMI_EINVAL;
+  return static_cast<int>(hipGetLastError());
+}
+
+extern "C" int drnmi_quantize_f8(const void* x, int32_t dtype, int64_t n, float inv_scale, uint8_t* y, void* stream) {
+  if (x == nullptr || y == nullptr || n <= 0 || !(inv_scale > 0.f) || (dtype != DRNMI_BF16 && dtype != DRNMI_F32))
+    return DRNMI_EINVAL;
+  // the vector body needs 16-B aligned rows on both sides; torch allocations are
+  if ((reinterpret_cast<uintptr_t>(x) & 15) != 0 || (reinterpret_cast<uintptr_t>(y) & 15) != 0) return DRNMI_EINVAL;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const unsigned blocks = stream_blocks((n + 15) / 16 * 2);
+  if (dtype == DRNMI_BF16)
+    hipLaunchKernelGGL(quantize_f8_kernel<bf16_t>, dim3(blocks), dim3(256), 0, s, static_cast<const bf16_t*>(x), y, n,
+                       inv_scale);
+  else
+    hipLaunchKernelGGL(quantize_f8_kernel<float>, dim3(blocks), dim3(256), 0, s, static_cast<const float*>(x), y, n,
+                       inv_scale);
   return static_cast<int>(hipGetLastError());
 }
 

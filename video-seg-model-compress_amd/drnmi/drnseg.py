@@ -20,7 +20,8 @@ Differences by design:
   * precision: "fp32" (default; the reference's arithmetic, parity mode, exact-fp32
     MFMA), "fp32x" (fp32-accurate arithmetic on the bf16 MFMA pipe: exact 3-way bf16 splits,
     6 products, for every conv with cin >= 32; parity gates as fp32, ~3x faster), "bf16"
-    (perf mode, fp32 accumulation) or "int8" (W8A8 for the cin >= 64 convs,
+    (perf mode, fp32 accumulation), "fp8" (OCP e4m3 weights and activations on the same convs
+    as int8, fp32 accumulation, the int8 calibration's scales; inference only) or "int8" (W8A8 for the cin >= 64 convs,
     config C5; needs calibrate_int8() or load_int8_state() first — the reference has no
     quantisation, so this mode is ours; DRN-D only) via set_precision().
   * segment(frames_u8) is the fused seg_video path (seg_video_old_no_plot.py:157-169:
@@ -254,11 +255,12 @@ class DRNSeg(nn.Module):
 
     # ----------------------------------------------------------------- configuration
     def set_precision(self, precision: str) -> "DRNSeg":
-        if precision not in ("fp32", "fp32x", "bf16", "int8"):
-            raise ValueError("precision must be 'fp32', 'fp32x', 'bf16' or 'int8'")
-        if precision == "int8" and self.arch != "D":
-            # the int8 launches are pinned bit for bit by an oracle that restates DRN-D only
-            raise NotImplementedError(f"precision 'int8' covers the DRN-D family only; {self.model_name} "
+        if precision not in ("fp32", "fp32x", "bf16", "int8", "fp8"):
+            raise ValueError("precision must be 'fp32', 'fp32x', 'bf16', 'int8' or 'fp8'")
+        if precision in ("int8", "fp8") and self.arch != "D":
+            # the int8 launches are pinned bit for bit by an oracle that restates DRN-D only, and fp8
+            # follows int8's layout
+            raise NotImplementedError(f"precision '{precision}' covers the DRN-D family only; {self.model_name} "
                                       "runs in 'fp32', 'fp32x' or 'bf16'")
         self.precision = precision
         return self
@@ -307,11 +309,12 @@ class DRNSeg(nn.Module):
         return self._install_act_scales(scales, "absmax", None)
 
     def _install_act_scales(self, scales, method, percentile):
-        """New activation scales: the int8 pack and plans built on the old ones go."""
+        """New activation scales: the int8 / fp8 packs and plans built on the old ones go."""
         self._act_scales = scales
         self._int8_method, self._int8_percentile = method, percentile
-        self._packed.pop("int8", None)
-        self._plans = {k: p for k, p in self._plans.items() if k[0] != "int8"}
+        for q8 in ("int8", "fp8"):
+            self._packed.pop(q8, None)
+        self._plans = {k: p for k, p in self._plans.items() if k[0] not in ("int8", "fp8")}
         self._pack_key = None
         return scales
 
@@ -453,8 +456,8 @@ class DRNSeg(nn.Module):
                         except RuntimeError:      # the repack changed the plan's launch structure
                             del self._plans[pkey]
             self._pack_key = key
-        if self.precision == "int8" and self._act_scales is None:
-            raise RuntimeError("precision 'int8' needs activation scales: call calibrate_int8(frames) or "
+        if self.precision in ("int8", "fp8") and self._act_scales is None:
+            raise RuntimeError(f"precision '{self.precision}' needs activation scales: call calibrate_int8(frames) or "
                                "load_int8_state(saved) first")
         pk = self._packed.get(self.precision)
         if pk is None:

@@ -31,12 +31,19 @@ K_ALIGN = 32
 COUT_ALIGN = 128
 
 DTYPES = {"fp32": (torch.float32, _lib.DRNMI_F32), "bf16": (torch.bfloat16, _lib.DRNMI_BF16),
-          "fp32x": (torch.float32, _lib.DRNMI_F32)}
+          "fp32x": (torch.float32, _lib.DRNMI_F32),
+          "fp8": (torch.bfloat16, _lib.DRNMI_BF16)}      # fp8: its base (the small-channel layers) is bf16
 # fp32x: fp32 activations everywhere (the fp32 mode's buffers); the convs with cin >= X6_MIN_CIN
 # and ks 1/3 run fp32-accurate split-bf16 arithmetic (csrc/conv_x6.hip, dtype DRNMI_F32X3), the
 # full-resolution small-channel stem / layer1 / layer2 stay on the exact f32 MFMA kernels.
 X6_MIN_CIN = 32
-TORCH_OF_CODE = {_lib.DRNMI_F32: torch.float32, _lib.DRNMI_BF16: torch.bfloat16, _lib.DRNMI_I8: torch.int8}
+TORCH_OF_CODE = {_lib.DRNMI_F32: torch.float32, _lib.DRNMI_BF16: torch.bfloat16, _lib.DRNMI_I8: torch.int8,
+                 _lib.DRNMI_F8: torch.uint8}       # e4m3 values live as raw bytes (.view(torch.float8_e4m3fn) decodes)
+# The 8-bit precisions: the value code of their 8-bit launches.  Both share the layout rules below
+# (PackedNet._int8_layout), the calibrated activation scales ("clip = 127 s") and the bf16 base.
+# fp8 (include/drnmi.h DRNMI_F8): OCP e4m3, maximum 448; the fp8 scale of a tensor is s * 127 / 448.
+Q8_CODES = {"int8": _lib.DRNMI_I8, "fp8": _lib.DRNMI_F8}
+F8_MAX = 448.0
 # W8A8 (config C5): convs whose input channel stride is >= this run on the int8 MFMA kernel
 # (conv_i8_kernel: K steps of 64/128 int8 channels); the full-resolution small-channel layers
 # (stem, layer1-3: ~5 % of D-22's FLOPs) stay bf16.
@@ -221,8 +228,9 @@ class PackedNet:
                            stage_outputs=dict(graph.stage_outputs), channels=dict(graph.channels))
         self.block_sparse = block_sparse
         self.precision = precision
-        # int8 nets run their small-channel layers in bf16: "base" is that precision
-        self.base = "bf16" if precision == "int8" else precision
+        # int8 / fp8 nets run their small-channel layers in bf16: "base" is that precision
+        self.qcode = Q8_CODES.get(precision)       # the net's 8-bit value code (None: no 8-bit launches)
+        self.base = "bf16" if self.qcode is not None else precision
         self.tdtype, self.code = DTYPES[self.base]
         self.device = device
         self.cstride = {"input": 8}
@@ -233,7 +241,7 @@ class PackedNet:
         self.vcode = {}            # value -> dtype code where it differs from self.code
         self.quant_after = {}      # node index -> values quantised (bf16 -> "q:" int8) after it
         self.i8_nodes = set()
-        if precision == "int8":
+        if self.qcode is not None:
             self._int8_layout()
         self.pack()
 
@@ -264,22 +272,28 @@ class PackedNet:
         for i in elig:
             nd = g.nodes[i]
             if not nd.out_fp32_nchw and readers.get(nd.dst) and all(j in elig for j in readers[nd.dst]):
-                self.vcode[nd.dst] = _lib.DRNMI_I8
+                self.vcode[nd.dst] = self.qcode
         need = {v for i in elig for v in (g.nodes[i].src, g.nodes[i].res) if v}
         missing = sorted(v for v in need | set(self.vcode) if v not in self.act_scales)
         if missing:
-            raise RuntimeError(f"int8: no calibrated activation scale for {missing} (DRNSeg.calibrate_int8)")
+            raise RuntimeError(f"{self.precision}: no calibrated activation scale for {missing} (DRNSeg.calibrate_int8)")
         for v in sorted(need):
-            if self.vcode.get(v) != _lib.DRNMI_I8:
+            if self.vcode.get(v) != self.qcode:
                 if v == "input":
-                    raise NotImplementedError("int8 launch reading the network input")
+                    raise NotImplementedError(f"{self.precision} launch reading the network input")
                 self.quant_after.setdefault(producer[v], []).append(v)
         self.i8_nodes = elig
 
     def value_code(self, v: str) -> int:
         if v.startswith("q:"):
-            return _lib.DRNMI_I8
+            return self.qcode if self.qcode is not None else _lib.DRNMI_I8
         return self.vcode.get(v, self.code)
+
+    def act_scale(self, v: str) -> float:
+        """Scale of the 8-bit form of value v: the calibrated s (int8: clip = 127 s), or s * 127 / 448
+        in an fp8 net (the same clip on e4m3's range)."""
+        s = float(self.act_scales[v])
+        return s * 127.0 / F8_MAX if self.qcode == _lib.DRNMI_F8 else s
 
     def pack(self):
         with torch.no_grad():
@@ -311,7 +325,7 @@ class PackedNet:
                 nd.i8, nd.x_val, nd.r_val, nd.res_scale, nd.out_scale = False, nd.src, nd.res, 0.0, 0.0
                 nd.x6 = False
                 if ni in self.i8_nodes:
-                    self._pack_int8(nd, full, scale, cout)
+                    (self._pack_fp8 if self.qcode == _lib.DRNMI_F8 else self._pack_int8)(nd, full, scale, cout)
                     continue
                 if self.precision == "fp32x" and cs >= X6_MIN_CIN and kh in (1, 3):
                     nd.x6 = True
@@ -471,17 +485,34 @@ class PackedNet:
         inv = torch.where(pos, 127.0 / torch.where(pos, a, torch.ones_like(a)), torch.ones_like(a))
         nd.wpk = torch.round(full * inv[:, None]).clamp_(-127, 127).to(torch.int8).contiguous()
         sw = torch.where(pos, a / 127.0, torch.ones_like(a))
-        sx = float(self.act_scales[nd.src])
+        self._q8_fields(nd, sw, bn_scale)
+
+    def _pack_fp8(self, nd: ConvNode, full: torch.Tensor, bn_scale: torch.Tensor, cout: int):
+        """Per-output-channel e4m3 weights (include/drnmi.h DRNMI_F8): a = absmax(row), q = e4m3(w *
+        (448 / a)) stored as bytes, s_w = a / 448 (1 for an all-zero row); the epilogue scale is
+        s_w * s8_x * bn_scale with s8_x = s_x * 127 / 448."""
+        a = full.abs().amax(dim=1)
+        pos = a > 0
+        inv = torch.where(pos, F8_MAX / torch.where(pos, a, torch.ones_like(a)), torch.ones_like(a))
+        q = (full * inv[:, None]).clamp_(-F8_MAX, F8_MAX)
+        # (converted on the host: one conversion routine for every device)
+        nd.wpk = q.cpu().to(torch.float8_e4m3fn).view(torch.uint8).to(full.device).contiguous()
+        self._q8_fields(nd, torch.where(pos, a / F8_MAX, torch.ones_like(a)), bn_scale)
+
+    def _q8_fields(self, nd: ConvNode, sw: torch.Tensor, bn_scale: torch.Tensor):
+        """What an 8-bit launch carries besides its weights, for either 8-bit code."""
+        q8 = self.qcode
+        sx = self.act_scale(nd.src)
         nd.scale = (sw * sx * bn_scale).float().contiguous()
         nd.scale_folded = False
         nd.unit_mask, nd.zero_unit_frac = None, 0.0
         nd.i8 = True
-        nd.x_val = nd.src if self.vcode.get(nd.src) == _lib.DRNMI_I8 else "q:" + nd.src
+        nd.x_val = nd.src if self.vcode.get(nd.src) == q8 else "q:" + nd.src
         if nd.res:
-            nd.r_val = nd.res if self.vcode.get(nd.res) == _lib.DRNMI_I8 else "q:" + nd.res
-            nd.res_scale = float(self.act_scales[nd.res])
-        if self.vcode.get(nd.dst) == _lib.DRNMI_I8:
-            nd.out_scale = 1.0 / float(self.act_scales[nd.dst])
+            nd.r_val = nd.res if self.vcode.get(nd.res) == q8 else "q:" + nd.res
+            nd.res_scale = self.act_scale(nd.res)
+        if self.vcode.get(nd.dst) == q8:
+            nd.out_scale = 1.0 / self.act_scale(nd.dst)
 
 
 def split3_bf16(w: torch.Tensor) -> torch.Tensor:
@@ -763,7 +794,7 @@ class Plan:
         if seg.conv.kernel_size[0] != 1 or not 1 <= classes <= 256:
             return
         wide = classes != 19
-        if wide and pk.precision not in ("bf16", "int8"):
+        if wide and pk.precision not in ("bf16", "int8", "fp8"):
             return                               # fp32 / fp32x plans keep the logits planes
         cs = (classes + 3) // 4 * 4 if wide else self.SEG_NHWC_CS
         lh, lw = self.shapes[seg.dst]
@@ -772,7 +803,7 @@ class Plan:
         a.y_sn, a.y_sp, a.y_sc = lh * lw * cs, cs, 1
         name = lib.drnmi_conv_kernel_name(ctypes.byref(a))   # (routing does not read a.y)
         if name is None or not name.decode().startswith(("conv_big_kernel", "conv_i8_kernel", "conv_i8_occ2_kernel",
-                                                        "conv_x6_kernel")):
+                                                        "conv_x6_kernel", "conv_f8_kernel", "conv_f8_occ2_kernel")):
             return
         if "logits_nhwc" not in self.bufs:      # only plans whose seg conv writes the NHWC rows
             self.bufs["logits_nhwc"] = torch.empty(self.n * lh * lw * cs, dtype=torch.float32, device=pk.device)
@@ -781,6 +812,8 @@ class Plan:
         self.seg_classes, self.seg_cs = classes, cs
         if wide or not SEG_FUSE or not self.fuse or seg.x_val != seg.src or seg.r_val:
             return
+        if pk.qcode == _lib.DRNMI_F8:
+            return                               # fp8: a separate seg conv feeds the NHWC head (no seg-fused fp8 tile)
         # the launch that writes the seg conv's input, on the labels-only list without this fusion:
         # one that already computes several nodes (front, block, folded downsample) is left alone
         prod = [l for l in self._build_launches("u8" if self.stem_u8 is not None else "nchw", True)
@@ -966,8 +999,12 @@ class Plan:
                 self._quantize(lib, v, stream)
 
     def _quantize(self, lib, v: str, stream: ctypes.c_void_p):
-        """bf16 value -> its int8 copy "q:<v>" (include/drnmi.h drnmi_quantize_i8)."""
+        """bf16 value -> its 8-bit copy "q:<v>" (include/drnmi.h drnmi_quantize_i8 / drnmi_quantize_f8)."""
         src, dst = self.bufs[v], self.bufs["q:" + v]
+        if self.packed.qcode == _lib.DRNMI_F8:
+            _lib.check(lib.drnmi_quantize_f8(src.data_ptr(), self.packed.value_code(v), dst.numel(),
+                                             1.0 / self.packed.act_scale(v), dst.data_ptr(), stream), f"quantize_f8 {v}")
+            return
         _lib.check(lib.drnmi_quantize_i8(src.data_ptr(), self.packed.value_code(v), dst.data_ptr(), dst.numel(),
                                          1.0 / float(self.packed.act_scales[v]), stream), f"quantize_i8 {v}")
 
@@ -1069,6 +1106,10 @@ class Plan:
             cs = self.packed.cstride[value]
             q = self.bufs[value].view(self.n, oh, ow, cs)[..., :c]
             return (q.float() * float(self.packed.act_scales[value])).permute(0, 3, 1, 2).contiguous()
+        if self.packed.value_code(value) == _lib.DRNMI_F8:
+            cs = self.packed.cstride[value]
+            q = self.bufs[value].view(torch.float8_e4m3fn).view(self.n, oh, ow, cs)[..., :c]
+            return (q.float() * self.packed.act_scale(value)).permute(0, 3, 1, 2).contiguous()
         out = torch.empty(self.n, c, oh, ow, dtype=torch.float32, device=self.packed.device)
         _lib.check(lib.drnmi_nhwc_to_nchw(self.bufs[value].data_ptr(), out.data_ptr(), self.n, c, oh, ow,
                                           self.packed.cstride[value], self.packed.value_code(value),

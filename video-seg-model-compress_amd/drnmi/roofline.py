@@ -11,7 +11,8 @@ f32-input MFMA 157.3 TFLOP/s.
 from __future__ import annotations
 
 HBM_PEAK_BPS = 8.0e12
-# int8: dense i8 MFMA = 2x bf16; fp32x: fp32-accurate split-bf16 arithmetic, 6 bf16 MFMAs per fp32
+# int8: dense i8 MFMA = 2x bf16 (fp8 launches, nd.i8 too, run e4m3 on the K-128 f8f6f4 MFMA at the same
+# peak and one byte per element); fp32x: fp32-accurate split-bf16 arithmetic, 6 bf16 MFMAs per fp32
 # product (csrc/conv_x6.hip) = 2.5 PF / 6
 MFMA_PEAK = {"bf16": 2.5e15, "fp32": 157.3e12, "int8": 5.0e15, "fp32x": 2.5e15 / 6}
 
@@ -19,6 +20,8 @@ MFMA_PEAK = {"bf16": 2.5e15, "fp32": 157.3e12, "int8": 5.0e15, "fp32x": 2.5e15 /
 def kernel_peak(kernel_name: str, base: str) -> float:
     """MFMA peak of the arithmetic a kernel (named as rocprofv3 names it) runs."""
     if kernel_name.startswith("conv_i8") or "_i8_" in kernel_name:   # conv_i8_*, conv_w1_i8_*, conv_w1h_i8_*
+        return MFMA_PEAK["int8"]
+    if kernel_name.startswith("conv_f8"):      # e4m3 on the K-128 f8f6f4 MFMA: the 8-bit peak
         return MFMA_PEAK["int8"]
     if kernel_name.startswith("conv_x6"):
         return MFMA_PEAK["fp32x"]
