@@ -56,7 +56,7 @@ def e4m3_bytes_np(v) -> np.ndarray:
 
 
 def pack_weights(full: torch.Tensor):
-    """PackedNet._pack_fp8's weight side: fp32 [rows][k] -> (e4m3 bytes, s_w)."""
+    """PackedNet._pack_q8's weight side for e4m3: fp32 [rows][k] -> (e4m3 bytes, s_w)."""
     a = full.abs().amax(dim=1)
     pos = a > 0
     inv = torch.where(pos, F8_MAX / torch.where(pos, a, torch.ones_like(a)), torch.ones_like(a))

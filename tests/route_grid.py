@@ -22,7 +22,7 @@ from drnmi import _lib
 ARGS = np.dtype(_lib.ConvArgs)
 PTR = 0x1000                 # placeholder for a present, 16-B aligned operand
 STEP = 2654435761            # prime: coprime with every product of small dimension sizes
-F32, BF16, I8, F32X3 = _lib.DRNMI_F32, _lib.DRNMI_BF16, _lib.DRNMI_I8, _lib.DRNMI_F32X3
+F32, BF16, I8, F32X3, F8 = _lib.DRNMI_F32, _lib.DRNMI_BF16, _lib.DRNMI_I8, _lib.DRNMI_F32X3, _lib.DRNMI_F8
 DATA_POINTERS = ("x", "wgt", "shift", "y")
 
 # (x2 channels, k_pad convention): k_pad == k, or k rounded up to whole 64-column weight steps
@@ -30,7 +30,7 @@ X2K = [(0, 0), (0, 1), (32, 0), (32, 1), (64, 0), (64, 1)]
 # (ws, ws_bytes): none, a workspace, a misaligned one, one too small for any split
 WS = [(0, 0), (PTR, 1 << 40), (PTR + 8, 1 << 40), (PTR, 16)]
 DEFAULTS = dict(dtype=BF16, algo=0, ks=3, cin=64, cout=64, stride=1, dil=1, wo=16, x2k=0, res=0, scale=0, mask=0,
-                ws=0, stats=0, ysr=0, out=0, cpad=128, tile=-1, src_u8=0, pad0=0, seg=0)
+                ws=0, stats=0, ysr=0, out=0, cpad=128, tile=-1, src_u8=0, pad0=0, seg=0, odt=-1)
 
 
 def product(**dims):
@@ -84,10 +84,11 @@ def build(d):
     a["ws_bytes"] = np.array([WS[i][1] for i in g["ws"]])
     a["stats"] = g["stats"]
     # output: 0 dense NHWC in the net's own type, 1 NCHW fp32, 2 NHWC rows padded to whole float4s
-    native = np.select([g["dtype"] == BF16, g["dtype"] == I8], [BF16, I8], F32)
+    # (odt >= 0: that out_dtype whatever the layout)
+    native = np.select([g["dtype"] == BF16, g["dtype"] == I8, g["dtype"] == F8], [BF16, I8, F8], F32)
     out = g["out"]
     row = np.where(out == 2, (cout + 4) // 4 * 4, cout)
-    a["out_dtype"] = np.where(out == 1, F32, native)
+    a["out_dtype"] = np.where(g["odt"] >= 0, g["odt"], np.where(out == 1, F32, native))
     a["y_sp"] = np.where(out == 1, 1, row)
     a["y_sc"] = np.where(out == 1, ho * wo, 1)
     a["y_sn"] = np.where(out == 1, cout * ho * wo, row * ho * wo)
@@ -147,13 +148,42 @@ def _parts():
                           res=[0, 1], out=[0, 1]))
 
 
-def grid():
-    parts = [build(d) for d in _parts()]
+def _parts_f8():
+    """DRNMI_F8 over the axes the int8 rows above use, plus every out_dtype (I8: refusals)."""
+    sd = np.array([(1, 1), (2, 1), (1, 2), (1, 4)])
+
+    def with_sd(d):
+        pairs = sd[d.pop("sd")]
+        d["stride"], d["dil"] = pairs[:, 0], pairs[:, 1]
+        return d
+    # auto route, every shape (cin: non-powers of two are refusals), clean operands
+    yield with_sd(product(dtype=[F8], ks=[1, 2, 3, 7], cin=[8, 16, 32, 64, 96, 128, 192, 256, 512],
+                          cout=[16, 19, 32, 64, 128, 130, 150, 256, 512], sd=[0, 1, 2, 3], wo=[16, 256],
+                          scale=[0, 1]))
+    # every tile id and auto over the shapes fp8 runs
+    yield with_sd(product(dtype=[F8], tile=[-1] + list(range(0, 26)), ks=[1, 3], cin=[64, 128, 256, 512],
+                          cout=[19, 128, 130, 256, 512], sd=[0, 2], wo=[16, 256], scale=[1], res=[0, 1]))
+    # every tile id against every optional operand, out_dtype, layout and padding convention
+    yield with_sd(lattice(12000, dtype=[F8], tile=[-1, -1, -1] + list(range(0, 26)), ks=[1, 3, 3, 7],
+                          cin=[32, 64, 128, 192, 256, 512], cout=[19, 64, 128, 130, 256, 512], sd=[0, 0, 1, 2, 3],
+                          wo=[16, 128, 256], x2k=[0, 0, 0, 1, 2, 4], res=[0, 1], scale=[0, 1, 1], mask=[0, 0, 1],
+                          odt=[F32, BF16, F8, F8, I8], out=[0, 0, 1, 2], cpad=[128, 256, 16]))
+    # the seg-fused entry (no fp8 form: refusals)
+    yield with_sd(product(seg=[1], dtype=[F8], tile=[-1, 19, 22], ks=[1, 3], cin=[256, 512], cout=[256, 512],
+                          sd=[0, 1, 2, 3], wo=[16, 256], scale=[0, 1], res=[0, 1], out=[0, 1]))
+
+
+def grid(parts=_parts):
+    parts = [build(d) for d in parts()]
     # into zeroed memory: np.concatenate copies field by field and leaves the record's four padding
     # bytes as it finds them, and digest() reads them
     args = np.zeros(sum(len(p[0]) for p in parts), dtype=ARGS)
     np.concatenate([p[0] for p in parts], out=args)
     return args, np.concatenate([p[1] for p in parts])
+
+
+def grid_f8():
+    return grid(_parts_f8)
 
 
 def digest(args, entry):

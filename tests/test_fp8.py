@@ -166,11 +166,18 @@ def test_fp8_pack_reuses_the_int8_scales():
         full[:cout, :n8.k] = wp.reshape(cout, n8.k)
         q, sw = R.pack_weights(full)
         assert n8.wpk.dtype == torch.uint8 and torch.equal(n8.wpk, q)
+        # the same pack in int8 (oracle/int8_oracle.py quantize_weight_rows in torch's fp32 arithmetic)
+        a = full.abs().amax(dim=1)
+        one = torch.ones_like(a)
+        qi = torch.round(full * torch.where(a > 0, 127.0 / torch.where(a > 0, a, one), one)[:, None]).clamp(-127, 127)
+        swi = torch.where(a > 0, a / 127.0, one)
+        assert ni.wpk.dtype == torch.int8 and torch.equal(ni.wpk, qi.to(torch.int8))
         bn = torch.ones(n8.cout_pad)
         if n8.bn is not None:
             bn[:cout] = _fold_bn(n8.bn)[0]
         s8 = s[n8.src] * 127.0 / 448.0
         assert torch.equal(n8.scale, (sw * s8 * bn).float())
+        assert torch.equal(ni.scale, (swi * s[n8.src] * bn).float())
         if n8.res:
             assert n8.res_scale == s[n8.res] * 127.0 / 448.0 and ni.res_scale == s[n8.res]
         if n8.out_scale:

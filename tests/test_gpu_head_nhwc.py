@@ -274,7 +274,7 @@ def test_seg_fused_int8_w1_matches_stag():
 
 
 def test_segment_labels_nhwc_identical_int8():
-    """int8 nets (C5): the int8 seg conv writes the same fp32 values as NHWC rows (store_tile_i8's
+    """int8 nets (C5): the int8 seg conv writes the same fp32 values as NHWC rows (store_tile_q8's
     16-B path) -- labels identical to the NCHW-planes head."""
     m = drnseg.build("drn_d_22", 19, seed=5, device=torch.device(DEV))
     g = torch.Generator(device=DEV).manual_seed(11)

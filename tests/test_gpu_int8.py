@@ -75,6 +75,10 @@ CONV_CASES = [
     # 9 K steps, an odd tap-group count), D-22 layer4.1 in int8 nets
     (2, 3, 256, 128, 128, 3, 1, 1, 1, True, "i8"),
     (1, 4, 512, 128, 128, 3, 1, 2, 2, False, "i8"),
+    # cout % 4 != 0 with a residual: every group's residual is loaded byte by byte, the last group
+    # (channels 128, 129) is partial; cout_pad 256
+    (1, 4, 7, 128, 130, 3, 1, 1, 1, True, "bf16"),
+    (1, 4, 7, 128, 130, 3, 1, 1, 1, True, "f32"),
 ]
 
 

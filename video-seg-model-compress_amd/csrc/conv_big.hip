@@ -92,7 +92,7 @@ __device__ __forceinline__ void conv_big_body(const drnmi_conv_args& p) {
   int a_par[2];
   // pixel row i: (ih0, iw0) of tap (0,0) packed as two int16 (ih0 = -16384: no pixel) and the
   // int32 element offset of that tap's chunk (only dereferenced when the tap is inside the
-  // image; big_conv_supported / i8_conv_supported bound n*h*w*cin < 2^31 and h, w < 16384)
+  // image; big_conv_supported / q8_conv_supported bound n*h*w*cin < 2^31 and h, w < 16384)
   uint32_t b_hw[C::B_INSTR];
   int b_off[C::B_INSTR];
   int b2_off[X2 ? C::B_INSTR : 1];   // x2 element offset of the row's chunk (x2 steps)
@@ -373,21 +373,18 @@ __device__ __forceinline__ void conv_big_body(const drnmi_conv_args& p) {
              cur_co0 + C::BCO <= p.cout;
       if (x4) store_tile_x4<C::FM, WCO, C::FN>(p, acc, cur_px0, cur_co0, wc, wp, fr, fq);
       else store_tile<C::FM, WCO, C::FN, DEFER>(p, acc, cur_px0, cur_co0, wc, wp, fr, fq);
-    } else if constexpr (F8) {
-      // whole tile of a dense, 16-B aligned e4m3 NHWC output: 16-B pieces
-      const bool x4 = C::FM % 4 == 0 && p.out_dtype == DRNMI_F8 && p.y_sc == 1 && p.y_sp == p.cout &&
-          p.y_sn == static_cast<int64_t>(p.ho) * p.wo * p.cout && ((reinterpret_cast<uintptr_t>(p.y) | reinterpret_cast<uintptr_t>(p.res)) & 15) == 0 &&
-          cur_px0 + kBPX <= p.n * p.ho * p.wo && cur_co0 + C::BCO <= p.cout;
-      if (x4) store_tile_f8_x4<C::FM, WCO, C::FN>(p, acc, cur_px0, cur_co0, wc, wp, fr, fq);
-      else store_tile_f8<C::FM, WCO, C::FN>(p, acc, cur_px0, cur_co0, wc, wp, fr, fq);
     } else {
-      bool x4 = false;
-      if constexpr (C::FM % 4 == 0)
-        x4 = p.out_dtype == DRNMI_I8 && p.y_sc == 1 && p.y_sp == p.cout &&
-             p.y_sn == static_cast<int64_t>(p.ho) * p.wo * p.cout && cur_px0 + kBPX <= p.n * p.ho * p.wo &&
-             cur_co0 + C::BCO <= p.cout && (p.res == nullptr || p.cout % 16 == 0);
-      if (x4) store_tile_i8_x4<C::FM, WCO, C::FN>(p, acc, cur_px0, cur_co0, wc, wp, fr, fq);
-      else store_tile_i8<C::FM, WCO, C::FN>(p, acc, cur_px0, cur_co0, wc, wp, fr, fq);
+      // whole tile inside a dense 8-bit NHWC output of the code's own type: 16-B pieces.  The terms
+      // of q8_dense_x4 with the whole-tile test between them, each code's guard (conv_tile.h Q8,
+      // CHECKS_ALIGNMENT) where that code has always evaluated it
+      using Q = Q8<T>;
+      const bool x4 = C::FM % 4 == 0 && p.out_dtype == Q::OUT && p.y_sc == 1 && p.y_sp == p.cout &&
+          p.y_sn == static_cast<int64_t>(p.ho) * p.wo * p.cout &&
+          (Q::CHECKS_ALIGNMENT ? ((reinterpret_cast<uintptr_t>(p.y) | reinterpret_cast<uintptr_t>(p.res)) & 15) == 0 : true) &&
+          cur_px0 + kBPX <= p.n * p.ho * p.wo && cur_co0 + C::BCO <= p.cout &&
+          (Q::CHECKS_ALIGNMENT ? true : (p.res == nullptr || p.cout % 16 == 0));
+      if (x4) store_tile_q8_x4<T, C::FM, WCO, C::FN>(p, acc, cur_px0, cur_co0, wc, wp, fr, fq);
+      else store_tile_q8<T, C::FM, WCO, C::FN>(p, acc, cur_px0, cur_co0, wc, wp, fr, fq);
     }
     if (!more) break;
     if constexpr (K::ESZ == 2) init_tile<C::FM, WCO, C::FN, DEFER>(p, acc, px0, co0, wc, wp, fr, fq);
@@ -416,7 +413,7 @@ conv_i8_strip_kernel(const drnmi_conv_args p) {
 
 // W8A8 (config C5): the same LDS-DMA pipeline over int8 elements, BK int8 channels per K step
 // (128-B LDS rows for cin >= 128, 64-B rows for cin == 64), v_mfma_i32_16x16x64_i8 into int32
-// accumulators, store_tile_i8 epilogue.
+// accumulators, store_tile_q8 epilogue.
 template <int KS, int WCO, int WC, int NST, int BK>
 __global__ void __launch_bounds__(64 * 4 * WC, 1)
 conv_i8_kernel(const drnmi_conv_args p) {
@@ -425,7 +422,7 @@ conv_i8_kernel(const drnmi_conv_args p) {
 
 // fp8 (DRNMI_F8, OCP e4m3): the same pipeline and LDS image over e4m3 bytes, BK channels per K
 // step as the int8 rows, v_mfma_f32_16x16x128_f8f6f4 into fp32 accumulators (one MFMA per fragment
-// pair and K step: KT<f8_t>), store_tile_f8 epilogue
+// pair and K step: KT<f8_t>), the same epilogue (conv_tile.h Q8<T>)
 template <int KS, int WCO, int WC, int NST, int BK>
 __global__ void __launch_bounds__(64 * 4 * WC, 1)
 conv_f8_kernel(const drnmi_conv_args p) {
@@ -701,35 +698,18 @@ hipError_t launch_strip(const drnmi_conv_args& p, hipStream_t s) {
   return hipGetLastError();
 }
 
-template <int KS, int WCO, int WC, int NST, int BK, bool OCC2 = false>
-hipError_t launch_i8(const drnmi_conv_args& p, hipStream_t s) {
-  using C = BigCfg<WCO, WC, NST, BK, 4, 1>;
-  const void* f;
-  if constexpr (OCC2) f = reinterpret_cast<const void*>(&conv_i8_occ2_kernel<KS, WCO, WC, NST, BK>);
-  else f = reinterpret_cast<const void*>(&conv_i8_kernel<KS, WCO, WC, NST, BK>);
-  static bool attr_set = false;
-  if (!attr_set) {
-    const hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, C::LDS);
-    if (e != hipSuccess) return e;
-    attr_set = true;
-  }
-  const int64_t M = static_cast<int64_t>(p.n) * p.ho * p.wo;
-  const int64_t blocks = ((M + kBPX - 1) / kBPX) * ((p.cout + C::BCO - 1) / C::BCO);
-  if constexpr (OCC2)
-    hipLaunchKernelGGL((conv_i8_occ2_kernel<KS, WCO, WC, NST, BK>), dim3(static_cast<unsigned>(blocks)), dim3(C::THREADS),
-                       C::LDS, s, p);
-  else
-    hipLaunchKernelGGL((conv_i8_kernel<KS, WCO, WC, NST, BK>), dim3(static_cast<unsigned>(blocks)), dim3(C::THREADS),
-                       C::LDS, s, p);
-  return hipGetLastError();
-}
-
-template <int KS, int WCO, int WC, int NST, int BK, bool OCC2 = false>
-hipError_t launch_f8(const drnmi_conv_args& p, hipStream_t s) {
+// conv_i8_kernel / conv_f8_kernel, or at OCC2 their two-workgroups-per-CU forms
+template <typename T, int KS, int WCO, int WC, int NST, int BK, bool OCC2>
+hipError_t launch_q8(const drnmi_conv_args& p, hipStream_t s) {
   using C = BigCfg<WCO, WC, NST, BK, 4, 1>;
   void (*kernel)(const drnmi_conv_args);
-  if constexpr (OCC2) kernel = &conv_f8_occ2_kernel<KS, WCO, WC, NST, BK>;
-  else kernel = &conv_f8_kernel<KS, WCO, WC, NST, BK>;
+  if constexpr (kIsF8<T>) {
+    if constexpr (OCC2) kernel = &conv_f8_occ2_kernel<KS, WCO, WC, NST, BK>;
+    else kernel = &conv_f8_kernel<KS, WCO, WC, NST, BK>;
+  } else {
+    if constexpr (OCC2) kernel = &conv_i8_occ2_kernel<KS, WCO, WC, NST, BK>;
+    else kernel = &conv_i8_kernel<KS, WCO, WC, NST, BK>;
+  }
   static bool attr_set = false;
   if (!attr_set) {
     const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, C::LDS);
@@ -740,16 +720,6 @@ hipError_t launch_f8(const drnmi_conv_args& p, hipStream_t s) {
   const int64_t blocks = ((M + kBPX - 1) / kBPX) * ((p.cout + C::BCO - 1) / C::BCO);
   hipLaunchKernelGGL(kernel, dim3(static_cast<unsigned>(blocks)), dim3(C::THREADS), C::LDS, s, p);
   return hipGetLastError();
-}
-
-template <int KS, int WCO, int WC, int NST, int BK>
-hipError_t launch_f8_occ2(const drnmi_conv_args& p, hipStream_t s) {
-  return launch_f8<KS, WCO, WC, NST, BK, true>(p, s);
-}
-
-template <int KS, int WCO, int WC, int NST, int BK>
-hipError_t launch_i8_occ2(const drnmi_conv_args& p, hipStream_t s) {
-  return launch_i8<KS, WCO, WC, NST, BK, true>(p, s);
 }
 
 // one lane per 16 x 32 unit; lanes 0-31 / 32-63 of a wave cover the 32 units of two mask words
@@ -818,28 +788,24 @@ const ConvKernel* strip_kernel(bool i8) {
   return &k[i8];
 }
 
-#define I8_ROWS(KERNEL, LAUNCH, ...) {DRNMI_KERNEL_ROW(KERNEL, LAUNCH, 1, __VA_ARGS__), DRNMI_KERNEL_ROW(KERNEL, LAUNCH, 3, __VA_ARGS__)}
-const I8Variant& i8_variant_row(int v) {
-  static const I8Variant k[5] = {
-    {256, I8_ROWS(conv_i8_kernel, launch_i8, 128, 2, 2, 128)},             // 2 x 64 KB
-    {128, I8_ROWS(conv_i8_kernel, launch_i8, 128, 1, 3, 128)},             // 3 x 48 KB
-    {256, I8_ROWS(conv_i8_kernel, launch_i8, 128, 2, 4, 64)},              // 4 x 32 KB
-    {128, I8_ROWS(conv_i8_kernel, launch_i8, 128, 1, 4, 64)},              // 4 x 24 KB
-    {128, I8_ROWS(conv_i8_occ2_kernel, launch_i8_occ2, 128, 1, 2, 64)},    // 2 x 24 KB, 2 WGs / CU
-  };
-  return k[v];
-}
-
-// the int8 rows' tiles
-const I8Variant& f8_variant_row(int v) {
-  static const I8Variant k[5] = {
-    {256, I8_ROWS(conv_f8_kernel, launch_f8, 128, 2, 2, 128)},             // 2 x 64 KB
-    {128, I8_ROWS(conv_f8_kernel, launch_f8, 128, 1, 3, 128)},             // 3 x 48 KB
-    {256, I8_ROWS(conv_f8_kernel, launch_f8, 128, 2, 4, 64)},              // 4 x 32 KB, K-64 steps
-    {128, I8_ROWS(conv_f8_kernel, launch_f8, 128, 1, 4, 64)},              // 4 x 24 KB, K-64 steps
-    {128, I8_ROWS(conv_f8_occ2_kernel, launch_f8_occ2, 128, 1, 2, 64)},    // 2 x 24 KB, K-64 steps, 2 WGs / CU
-  };
-  return k[v];
+// the 8-bit tiles, one table per code (conv_route.h Q8Variant): KERNEL<KS, ARGS> launched by
+// launch_q8<T, KS, ARGS, OCC2>, rows [ks == 3].  (q8_variant sends every 1x1 to the occ2 tile, so the
+// KS = 1 rows of tiles 0-3 and the KS = 3 row of the occ2 tile are never picked, for either code.)
+#define Q8_ROW(KERNEL, T, OCC2, KS, ...) \
+  ConvKernel { #KERNEL "<" #KS ", " #__VA_ARGS__ ">", &launch_unsplit<&launch_q8<T, KS, __VA_ARGS__, OCC2>> }
+#define Q8_ROWS(KERNEL, T, OCC2, ...) {Q8_ROW(KERNEL, T, OCC2, 1, __VA_ARGS__), Q8_ROW(KERNEL, T, OCC2, 3, __VA_ARGS__)}
+#define Q8_TABLE(KERNEL, OCC2_KERNEL, T)                                                                         \
+  {                                                                                                              \
+    {256, Q8_ROWS(KERNEL, T, false, 128, 2, 2, 128)},        /* 2 x 64 KB */                                     \
+    {128, Q8_ROWS(KERNEL, T, false, 128, 1, 3, 128)},        /* 3 x 48 KB */                                     \
+    {256, Q8_ROWS(KERNEL, T, false, 128, 2, 4, 64)},         /* 4 x 32 KB (fp8: K-64 steps on these 64-B rows) */ \
+    {128, Q8_ROWS(KERNEL, T, false, 128, 1, 4, 64)},         /* 4 x 24 KB */                                     \
+    {128, Q8_ROWS(OCC2_KERNEL, T, true, 128, 1, 2, 64)},     /* 2 x 24 KB, 2 WGs / CU */                         \
+  }
+const Q8Variant& q8_variant_row(int dtype, int v) {
+  static const Q8Variant i8[5] = Q8_TABLE(conv_i8_kernel, conv_i8_occ2_kernel, int8_t);
+  static const Q8Variant f8[5] = Q8_TABLE(conv_f8_kernel, conv_f8_occ2_kernel, f8_t);
+  return (dtype == DRNMI_F8 ? f8 : i8)[v];
 }
 
 // a 256-pixel tile is a run of one output row, the strip of 256 + 2 dil rows fits its buffer
@@ -868,41 +834,35 @@ bool w1h_ok(const drnmi_conv_args& p) {
          p.y_sc == 1 && p.y_sp == p.cout && p.y_sn == static_cast<int64_t>(p.ho) * p.wo * p.cout;
 }
 
-bool i8_conv_supported(const drnmi_conv_args& p) {
-  return p.dtype == DRNMI_I8 && p.scale != nullptr && p.cin >= 64 && (p.cin & (p.cin - 1)) == 0 &&
+// the 8-bit families' shapes (int8: config C5; fp8: e4m3 bytes): cin >= 64, a non-NULL scale, the
+// code's own 8-bit output or bf16 / fp32.  fp8 has no fused second input and no unit skipping and
+// refuses them; int8 does not look at those two pointers (its pinned behaviour with them set).
+bool q8_conv_supported(const drnmi_conv_args& p) {
+  if (p.dtype != DRNMI_I8 && p.dtype != DRNMI_F8) return false;
+  if (p.dtype == DRNMI_F8 && (p.x2 != nullptr || p.unit_mask != nullptr)) return false;
+  return p.scale != nullptr && p.cin >= 64 && (p.cin & (p.cin - 1)) == 0 &&
          p.cout_pad % 128 == 0 && (p.ks == 1 || p.ks == 3) && p.k == p.ks * p.ks * p.cin && p.k_pad == p.k &&
          static_cast<int64_t>(p.n) * p.h * p.w * p.cin < (int64_t(1) << 31) && p.h < 16384 && p.w < 16384 &&
-         (p.out_dtype == DRNMI_F32 || p.out_dtype == DRNMI_BF16 || p.out_dtype == DRNMI_I8);
+         (p.out_dtype == DRNMI_F32 || p.out_dtype == DRNMI_BF16 || p.out_dtype == p.dtype);
 }
 
-// fp8: the int8 family's shapes (e4m3 bytes, a non-NULL scale)
-bool f8_conv_supported(const drnmi_conv_args& p) {
-  return p.dtype == DRNMI_F8 && p.scale != nullptr && p.cin >= 64 && (p.cin & (p.cin - 1)) == 0 &&
-         p.cout_pad % 128 == 0 && (p.ks == 1 || p.ks == 3) && p.k == p.ks * p.ks * p.cin && p.k_pad == p.k &&
-         p.x2 == nullptr && p.unit_mask == nullptr &&
-         static_cast<int64_t>(p.n) * p.h * p.w * p.cin < (int64_t(1) << 31) && p.h < 16384 && p.w < 16384 &&
-         (p.out_dtype == DRNMI_F32 || p.out_dtype == DRNMI_BF16 || p.out_dtype == DRNMI_F8);
-}
-// fp8 staggered strip tile: the int8 one's geometry (128-channel K steps walked in pairs of tap groups)
-bool f8_stag_ok(const drnmi_conv_args& p) {
-  return p.cout % 256 == 0 && p.cin % 256 == 0 && p.cout <= p.cout_pad && strip_ok(p);
-}
-
-// int8 strip-staged B: the 256 x 256 tile with 128-B rows (i8_variant_row(0): cin >= 128, cout % 256 == 0)
+// int8 strip-staged B: the 256 x 256 tile with 128-B rows (q8_variant_row 0: cin >= 128, cout % 256 == 0)
 bool i8_strip_ok(const drnmi_conv_args& p) {
   return p.cout % 256 == 0 && p.cin % 128 == 0 && strip_ok(p);
 }
 
-// int8 staggered strip tile (conv_stag.hip): 128-channel K steps, so cin % 256 == 0 gives the
-// even number of 3-step tap groups the kernel walks in pairs
-bool i8_stag_ok(const drnmi_conv_args& p) {
+// 8-bit staggered strip tile (conv_stag.hip, both codes): 128-channel K steps, so cin % 256 == 0
+// gives the even number of 3-step tap groups the kernel walks in pairs.  (The fp8 predicate also
+// asked cout <= cout_pad: conv_route() refuses cout > cout_pad before any 8-bit route, and both
+// routes check rows_exist first, so the term never decided anything.)
+bool q8_stag_ok(const drnmi_conv_args& p) {
   return i8_strip_ok(p) && p.cin % 256 == 0 && p.x2 == nullptr;
 }
 
 // int8 conv_w1 (conv_w1_i8_kernel): the staggered int8 tile's shapes at 256-channel blocks with a
 // dense int8 NHWC output (its 16-B epilogue)
 bool i8_w1_ok(const drnmi_conv_args& p) {
-  return i8_stag_ok(p) && p.cout % 256 == 0 && p.out_dtype == DRNMI_I8 && p.y_sc == 1 && p.y_sp == p.cout &&
+  return q8_stag_ok(p) && p.cout % 256 == 0 && p.out_dtype == DRNMI_I8 && p.y_sc == 1 && p.y_sp == p.cout &&
          p.y_sn == static_cast<int64_t>(p.ho) * p.wo * p.cout;
 }
 // int8 conv_w1h (conv_w1h_i8_kernel: 128 x 128 tiles, two workgroups per CU, odd tap-group counts

@@ -126,7 +126,7 @@ ConvRoute big_route(const drnmi_conv_args& p) {
   }
   if (tile == DRNMI_TILE_W1) return take(w1_kernel(false, p.x2 != nullptr));
   if (tile == DRNMI_TILE_W1H) return take(w1h_kernel(false, p.x2 != nullptr));
-  if (tile == DRNMI_TILE_STAG) return stag_ok(p) ? take(stag_kernel(false, p.cout <= 128, p.x2 != nullptr)) : refuse(DRNMI_ENOTSUP);
+  if (tile == DRNMI_TILE_STAG) return stag_ok(p) ? take(stag_kernel(DRNMI_BF16, p.cout <= 128, p.x2 != nullptr)) : refuse(DRNMI_ENOTSUP);
   if (tile == DRNMI_TILE_STRIP) {
     if (!strip_ok(p) || p.cin < 64) return refuse(DRNMI_ENOTSUP);
     return rows_exist(p, 256) ? take(strip_kernel(false)) : refuse(DRNMI_EINVAL);
@@ -142,12 +142,13 @@ ConvRoute big_route(const drnmi_conv_args& p) {
   return take(&v.dense[ks3]);
 }
 
-// --- W8A8
-int i8_variant(const drnmi_conv_args& p) {
+// --- the 8-bit families (DRNMI_I8: W8A8; DRNMI_F8: e4m3), one route
+int q8_variant(const drnmi_conv_args& p) {
   const int wide = p.cout % 256 == 0 ? 0 : 1;
   // 1x1: the two-workgroups-per-CU tile (71.6-73.5 vs 86.7-86.9 us for layer5.0 / layer6.0's
-  // downsample, 65.6-67.0 for the seg conv: profiles/r6_int8_fusions/occ2_ab.txt)
-  return p.ks == 1 && p.cout_pad % i8_variant_row(kI8Occ2).bco == 0 ? kI8Occ2 : (p.cin >= 128 ? 0 : 2) + wide;
+  // downsample, 65.6-67.0 for the seg conv: profiles/r6_int8_fusions/occ2_ab.txt).  Its 128 rows
+  // always divide cout_pad (q8_conv_supported: cout_pad % 128 == 0), for either code
+  return p.ks == 1 && p.cout_pad % q8_variant_row(p.dtype, kQ8Occ2).bco == 0 ? kQ8Occ2 : (p.cin >= 128 ? 0 : 2) + wide;
 }
 // conv_w1h_i8_kernel is auto-routed at cin, cout <= 256 (D-22 layer4.1, layer5 in int8 nets:
 // profiles/r11_int8_layer4)
@@ -156,37 +157,30 @@ bool i8_w1h_pick(const drnmi_conv_args& p) {
          (p.tile < 0 && i8_w1h_ok(p) && (p.cout <= 128 || p.cin == 128 || (p.cin <= 256 && p.cout <= 256)));
 }
 
-ConvRoute i8_route(const drnmi_conv_args& p) {
-  if (!i8_conv_supported(p)) return refuse(DRNMI_ENOTSUP);
-  const I8Variant& v = i8_variant_row(i8_variant(p));
+// Both codes run conv_{i8,f8}_kernel on the same five tiles (128-B rows at cin >= 128, the 64-B rows
+// -- fp8: the K-64 step shape -- at cin == 64) and the strip-staged conv_{i8,f8}_stag_kernel on the
+// row-aligned 3x3 launches q8_stag_ok admits.  What fp8 lacks is stated where int8 takes it: the
+// one-wave-per-SIMD tiles (W1, W1H), the strip tile and the seg-fused form (seg_route).
+ConvRoute q8_route(const drnmi_conv_args& p) {
+  if (!q8_conv_supported(p)) return refuse(DRNMI_ENOTSUP);
+  const bool f8 = p.dtype == DRNMI_F8;
+  if (f8 && (p.tile == DRNMI_TILE_W1 || p.tile == DRNMI_TILE_W1H)) return refuse(DRNMI_ENOTSUP);   // no fp8 form
+  const Q8Variant& v = q8_variant_row(p.dtype, q8_variant(p));
   if (!rows_exist(p, v.bco)) return refuse(DRNMI_EINVAL);
   const int ks3 = p.ks == 3;
-  if (ks3 && i8_w1h_pick(p)) return i8_w1h_ok(p) ? take(w1h_kernel(true, false)) : refuse(DRNMI_ENOTSUP);
-  if (ks3 && i8_stag_ok(p)) {
+  if (!f8 && ks3 && i8_w1h_pick(p)) return i8_w1h_ok(p) ? take(w1h_kernel(true, false)) : refuse(DRNMI_ENOTSUP);
+  if (ks3 && q8_stag_ok(p)) {
     // DRNMI_TILE_W1 forces the one-wave-per-SIMD int8 tile (the bit-identity tests); else the
     // staggered one: on the long-K residual-free int8 launches conv_w1_i8_kernel measured no faster
     // inside the network (profiles/r11_w1i8: layer6.1 conv1 460 vs 450 us); the seg-fused layer8
     // launch (drnmi_conv_stag_seg) takes its SEGF form (431 vs 456 us)
-    if (p.tile != DRNMI_TILE_W1) return take(stag_kernel(true, false, false));
+    if (p.tile != DRNMI_TILE_W1) return take(stag_kernel(p.dtype, false, false));
     return i8_w1_ok(p) ? take(w1_kernel(true, false)) : refuse(DRNMI_ENOTSUP);
   }
-  if (ks3 && i8_strip_ok(p)) return take(strip_kernel(true));
-  return take(&v.k[ks3]);
-}
-
-// --- fp8 (DRNMI_F8): conv_f8_kernel on the int8 rows' tiles (128-B rows at cin >= 128, the K-64
-// step shape at cin == 64); the row-aligned 3x3 launches i8_stag_ok's geometry admits take the
-// strip-staged conv_f8_stag_kernel (DRNMI_TILE_STAG forces it and refuses other shapes).  The
-// one-wave-per-SIMD tiles have no fp8 form.
-ConvRoute f8_route(const drnmi_conv_args& p) {
-  if (!f8_conv_supported(p)) return refuse(DRNMI_ENOTSUP);
-  if (p.tile == DRNMI_TILE_W1 || p.tile == DRNMI_TILE_W1H) return refuse(DRNMI_ENOTSUP);
-  // 1x1: the two-workgroups-per-CU tile, as int8 (i8_variant)
-  const I8Variant& v = f8_variant_row(p.ks == 1 ? kI8Occ2 : (p.cin >= 128 ? 0 : 2) + (p.cout % 256 == 0 ? 0 : 1));
-  if (!rows_exist(p, v.bco)) return refuse(DRNMI_EINVAL);
-  const int ks3 = p.ks == 3;
-  if (ks3 && f8_stag_ok(p)) return take(stag_f8_kernel());
-  if (p.tile == DRNMI_TILE_STAG) return refuse(DRNMI_ENOTSUP);
+  // fp8: DRNMI_TILE_STAG forces the staggered tile and refuses the shapes it does not admit (int8
+  // ignores the id there); and no fp8 strip tile
+  if (f8 && p.tile == DRNMI_TILE_STAG) return refuse(DRNMI_ENOTSUP);
+  if (!f8 && ks3 && i8_strip_ok(p)) return take(strip_kernel(true));
   return take(&v.k[ks3]);
 }
 
@@ -318,10 +312,8 @@ ConvRoute conv_route(const drnmi_conv_args& p) {
   if (p.cout <= 0 || p.cout > p.cout_pad || p.k != p.ks * p.ks * p.cin + (p.x2 != nullptr ? p.cin2 : 0))
     return refuse(DRNMI_EINVAL);
   if (p.k_pad < p.k || p.k_pad % kBK != 0 || p.stride <= 0 || p.dil <= 0 || p.pad < 0) return refuse(DRNMI_EINVAL);
-  if (p.dtype == DRNMI_I8) {
-    if (p.out_dtype != DRNMI_I8 && p.out_dtype != DRNMI_BF16 && p.out_dtype != DRNMI_F32) return refuse(DRNMI_EINVAL);
-  } else if (p.dtype == DRNMI_F8) {
-    if (p.out_dtype != DRNMI_F8 && p.out_dtype != DRNMI_BF16 && p.out_dtype != DRNMI_F32) return refuse(DRNMI_EINVAL);
+  if (p.dtype == DRNMI_I8 || p.dtype == DRNMI_F8) {       // 8-bit: the code's own type, bf16 or fp32
+    if (p.out_dtype != p.dtype && p.out_dtype != DRNMI_BF16 && p.out_dtype != DRNMI_F32) return refuse(DRNMI_EINVAL);
   } else if (p.dtype == DRNMI_F32X3) {
     if (p.out_dtype != DRNMI_F32) return refuse(DRNMI_EINVAL);
   } else if ((p.dtype != DRNMI_BF16 && p.dtype != DRNMI_F32) ||
@@ -332,8 +324,7 @@ ConvRoute conv_route(const drnmi_conv_args& p) {
   // the row-strided (y_sr) class launches of a stride-2 data gradient, whose taps past the input's
   // bottom / right edge read zeros (an asymmetric pad; conv_x6 bounds-checks every tap)
   if (p.y_sr == 0 && !conv_geometry(p)) return refuse(DRNMI_EINVAL);
-  if (p.dtype == DRNMI_I8) return i8_route(p);       // int8: one kernel family
-  if (p.dtype == DRNMI_F8) return f8_route(p);       // fp8: its own family too
+  if (p.dtype == DRNMI_I8 || p.dtype == DRNMI_F8) return q8_route(p);       // 8-bit: one kernel family
   if (p.dtype == DRNMI_F32X3) return x6_route(p);
   if (p.tile >= DRNMI_TILE_DMA128 || (p.tile < 0 && (big_conv_supported(p) || halo_conv_supported(p)))) return big_route(p);
   if (p.x2 != nullptr) return refuse(DRNMI_ENOTSUP);          // fused second input: LDS-DMA kernels only
@@ -364,7 +355,7 @@ SegRoute seg_route(const drnmi_conv_args& p) {
   if (i8 ? (p.out_dtype != DRNMI_I8 || p.scale == nullptr) : (p.dtype != DRNMI_BF16 || p.out_dtype != DRNMI_BF16))
     return {DRNMI_EINVAL, nullptr};
   if (!conv_geometry(p)) return {DRNMI_EINVAL, nullptr};
-  const bool stag = i8 ? i8_conv_supported(p) && p.ks == 3 && i8_stag_ok(p)
+  const bool stag = i8 ? q8_conv_supported(p) && p.ks == 3 && q8_stag_ok(p)
                        : big_conv_supported(p) && stag_ok(p) && p.x2 == nullptr && p.scale == nullptr;
   if (!stag || p.res != nullptr || p.cout % 256 != 0 || p.cout_pad < p.cout) return {DRNMI_ENOTSUP, nullptr};
   return {0, p.tile == DRNMI_TILE_STAG ? stag_seg_kernel(i8) : w1_seg_kernel(i8)};

@@ -58,33 +58,28 @@ struct BigVariant {
 constexpr int kNumBigVariants = 13;
 const BigVariant& big_variant(int v);            // tile ids DRNMI_TILE_DMA128 + v .. DRNMI_TILE_PP256
 const ConvKernel* strip_kernel(bool i8);
-// W8A8 variants: 0 = 256 x 256 tile / 128-B rows, 1 = 128 x 256 / 128-B, 2 = 256 x 256 / 64-B,
-// 3 = 128 x 256 / 64-B (K steps of 128 or 64 int8 channels), 4 = 128 x 256 / 64-B rows, 2 stages,
-// two workgroups per CU
-struct I8Variant {
+// The 8-bit families (dtype DRNMI_I8: W8A8, config C5; DRNMI_F8: e4m3) share their tiles.  Variants:
+// 0 = 256 x 256 tile / 128-B rows, 1 = 128 x 256 / 128-B, 2 = 256 x 256 / 64-B, 3 = 128 x 256 / 64-B
+// (K steps of 128 or 64 channels), 4 = 128 x 256 / 64-B rows, 2 stages, two workgroups per CU
+struct Q8Variant {
   int bco;
   ConvKernel k[2];
 };
-const I8Variant& i8_variant_row(int v);
-constexpr int kI8Occ2 = 4;
-// fp8 (DRNMI_F8): the same five tiles
-const I8Variant& f8_variant_row(int v);
-bool f8_conv_supported(const drnmi_conv_args& p);      // dtype DRNMI_F8, cin >= 64, scale non-NULL
-bool f8_stag_ok(const drnmi_conv_args& p);
+const Q8Variant& q8_variant_row(int dtype, int v);
+constexpr int kQ8Occ2 = 4;
+bool q8_conv_supported(const drnmi_conv_args& p);      // dtype DRNMI_I8 / DRNMI_F8, cin >= 64, scale non-NULL
+bool q8_stag_ok(const drnmi_conv_args& p);
 bool big_conv_supported(const drnmi_conv_args& p);
-bool i8_conv_supported(const drnmi_conv_args& p);      // dtype DRNMI_I8, cin >= 64 (config C5)
 bool strip_ok(const drnmi_conv_args& p);
 bool stag_ok(const drnmi_conv_args& p);
 bool w1_ok(const drnmi_conv_args& p);
 bool w1h_ok(const drnmi_conv_args& p);
 bool i8_strip_ok(const drnmi_conv_args& p);
-bool i8_stag_ok(const drnmi_conv_args& p);
 bool i8_w1_ok(const drnmi_conv_args& p);
 bool i8_w1h_ok(const drnmi_conv_args& p);
 
 // conv_stag.hip: the strip tile with staggered SIMD partners: 3x3 stride-1, wo % 256 == 0, cin % 128 == 0
-const ConvKernel* stag_kernel(bool i8, bool tile128, bool x2);
-const ConvKernel* stag_f8_kernel();
+const ConvKernel* stag_kernel(int dtype, bool tile128, bool x2);     // DRNMI_I8 / DRNMI_F8: the 256-channel tile, no x2
 const SegKernel* stag_seg_kernel(bool i8);
 // conv_w1.hip: the same tile as 4 waves of 128 x 128 (one per SIMD), and as 128 x 128 tiles of 4
 // waves of 64 x 64 (two workgroups per CU); bit-identical to conv_stag_kernel

@@ -60,7 +60,7 @@ struct SegFuse {
 constexpr int kSegCS = 20;
 
 // int8 nets (C5): the seg classifier on the int8 copy of the last conv's output.  Each output
-// value is quantised exactly as store_tile_i8 stores it (fmul, fadd, ReLU, rint(v * out_scale)
+// value is quantised exactly as store_tile_q8<int8_t> stores it (fmul, fadd, ReLU, rint(v * out_scale)
 // clamped to +-127; no contraction) and becomes the B operand of v_mfma_i32_16x16x64_i8 whose A
 // fragments are the int8 seg weights.  Lane (fr, fq) holds channels 16 fm + 4 fq .. + 3 of
 // pixel fr; for the 64-channel group g its 16 bytes are channels 64 g + 16 m + 4 fq + e (m, e =
@@ -557,20 +557,14 @@ __device__ __forceinline__ void conv_stag_body(const drnmi_conv_args& p, const S
   if constexpr (K::ESZ == 2) {
     if (fast_epi) store_tile_x4<FM, WCO, 4>(p, acc, px0, co0, wc, wp, fr, fq);
     else store_tile<FM, WCO, 4, false>(p, acc, px0, co0, wc, wp, fr, fq);
-  } else if constexpr (F8) {
-    // whole tile of a dense, 16-B aligned e4m3 NHWC output (M % 256 == 0, cout % 256 == 0 here): 16-B pieces
-    if (p.out_dtype == DRNMI_F8 && p.y_sc == 1 && p.y_sp == p.cout &&
-          p.y_sn == static_cast<int64_t>(p.ho) * p.wo * p.cout && ((reinterpret_cast<uintptr_t>(p.y) | reinterpret_cast<uintptr_t>(p.res)) & 15) == 0)
-      store_tile_f8_x4<FM, WCO, 4>(p, acc, px0, co0, wc, wp, fr, fq);
-    else
-      store_tile_f8<FM, WCO, 4>(p, acc, px0, co0, wc, wp, fr, fq);
   } else {
-    // whole tile of a dense int8 NHWC output (M % 256 == 0 here): 16-B pieces
-    if (p.out_dtype == DRNMI_I8 && p.y_sc == 1 && p.y_sp == p.cout && p.y_sn == static_cast<int64_t>(hw_o) * p.cout &&
-        p.cout % BCO == 0 && (p.res == nullptr || p.cout % 16 == 0))
-      store_tile_i8_x4<FM, WCO, 4>(p, acc, px0, co0, wc, wp, fr, fq);
+    // whole tile of a dense 8-bit NHWC output of the code's own type (M % 256 == 0 here): 16-B pieces.
+    // int8 also asks cout % BCO == 0 here, as it always has; fp8 never did (the route's q8_stag_ok
+    // implies it for both)
+    if (q8_dense_x4<T>(p) && (Q8<T>::CHECKS_ALIGNMENT || p.cout % BCO == 0))
+      store_tile_q8_x4<T, FM, WCO, 4>(p, acc, px0, co0, wc, wp, fr, fq);
     else
-      store_tile_i8<FM, WCO, 4>(p, acc, px0, co0, wc, wp, fr, fq);
+      store_tile_q8<T, FM, WCO, 4>(p, acc, px0, co0, wc, wp, fr, fq);
   }
 }
 
@@ -580,14 +574,14 @@ conv_stag_kernel(const drnmi_conv_args p) {
 }
 
 // W8A8 (config C5): int8 rows of 128 channels are 128 B, the bf16 layout; v_mfma_i32_16x16x64_i8,
-// store_tile_i8 epilogue (bit-exact against oracle/int8_oracle.py like conv_i8_strip_kernel)
+// store_tile_q8 epilogue (bit-exact against oracle/int8_oracle.py like conv_i8_strip_kernel)
 __global__ void __launch_bounds__(512, 1)
 conv_i8_stag_kernel(const drnmi_conv_args p) {
   conv_stag_body<int8_t, false>(p);
 }
 
 // fp8 (DRNMI_F8): e4m3 rows of 128 channels, the int8 LDS image; v_mfma_f32_16x16x128_f8f6f4, one
-// MFMA per fragment pair and K step; store_tile_f8 / store_tile_f8_x4 epilogue (the arithmetic of
+// MFMA per fragment pair and K step; store_tile_q8 / store_tile_q8_x4 epilogue (the arithmetic of
 // conv_f8_kernel: the same K order, so the same sums)
 __global__ void __launch_bounds__(512, 1)
 conv_f8_stag_kernel(const drnmi_conv_args p) {
@@ -687,17 +681,14 @@ hipError_t launch_stag128(const drnmi_conv_args& p, hipStream_t s) {
   return hipGetLastError();
 }
 
-const ConvKernel* stag_kernel(bool i8, bool tile128, bool x2) {
+const ConvKernel* stag_kernel(int dtype, bool tile128, bool x2) {
   static const ConvKernel k[2][2] = {
       {DRNMI_KERNEL_ROW0(conv_stag_kernel, launch_stag), DRNMI_KERNEL_ROW0(conv_stag_x2_kernel, launch_stag)},
       {DRNMI_KERNEL_ROW0(conv_stag128_kernel, launch_stag128), DRNMI_KERNEL_ROW0(conv_stag128_x2_kernel, launch_stag128)}};
-  static const ConvKernel k8 = DRNMI_KERNEL_ROW0(conv_i8_stag_kernel, launch_stag);
-  return i8 ? &k8 : &k[tile128][x2];
-}
-
-const ConvKernel* stag_f8_kernel() {
-  static const ConvKernel k = DRNMI_KERNEL_ROW0(conv_f8_stag_kernel, launch_stag);
-  return &k;
+  static const ConvKernel k8[2] = {DRNMI_KERNEL_ROW0(conv_i8_stag_kernel, launch_stag),
+                                   DRNMI_KERNEL_ROW0(conv_f8_stag_kernel, launch_stag)};
+  if (dtype == DRNMI_I8 || dtype == DRNMI_F8) return &k8[dtype == DRNMI_F8];
+  return &k[tile128][x2];
 }
 
 const SegKernel* stag_seg_kernel(bool i8) {

@@ -74,6 +74,51 @@ template <> struct KT<f8_t> {
 template <typename T> constexpr bool kIsF8 = false;
 template <> constexpr bool kIsF8<f8_t> = true;
 
+// What differs between the two 8-bit codes in the epilogue (store_tile_q8 / store_tile_q8_x4): the
+// 8-bit out_dtype, the three conversions, the guards of the 4-B and 16-B accesses, and how
+// store_tile_q8 holds a group's residual bytes (RES_AS_WORD).
+// The guards are NOT the same rule twice (CHECKS_ALIGNMENT): int8 takes its 4-B accesses on y_sc and
+// cout % 4 alone and the 16-B form whenever a residual's rows are whole 16-B pieces (cout % 16 == 0),
+// trusting the buffers' alignment; fp8 checks the strides' and the pointers' alignment instead.
+// Making them one rule changes which store form a launch takes, so each code keeps its own here
+// until that is decided on its own.
+template <typename T> struct Q8;
+template <> struct Q8<int8_t> {
+  static constexpr int OUT = DRNMI_I8;
+  __device__ __forceinline__ static float acc_f32(int a) { return static_cast<float>(a); }
+  // byte J of a residual word
+  template <int J>
+  __device__ __forceinline__ static float res_f32(uint32_t w) {
+    return static_cast<float>(static_cast<int8_t>((w >> (8 * J)) & 0xff));
+  }
+  // four values times out_scale -> one packed word: rint, clamp to +-127
+  __device__ __forceinline__ static uint32_t pack(const float (&v)[4], float s) {
+#pragma clang fp contract(off)
+    uint32_t o = 0;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const float t = fminf(fmaxf(rintf(v[j] * s), -127.f), 127.f);
+      o |= static_cast<uint32_t>(static_cast<uint8_t>(static_cast<int8_t>(static_cast<int>(t)))) << (8 * j);
+    }
+    return o;
+  }
+  static constexpr bool CHECKS_ALIGNMENT = false;
+  static constexpr bool RES_AS_WORD = false;      // store_tile_q8 keeps a group's residual as four int8
+};
+template <> struct Q8<f8_t> {
+  static constexpr int OUT = DRNMI_F8;
+  __device__ __forceinline__ static float acc_f32(float a) { return a; }
+  template <int J>
+  __device__ __forceinline__ static float res_f32(uint32_t w) { return f8_to_f32<J>(w); }
+  // ... e4m3, saturating at +-448
+  __device__ __forceinline__ static uint32_t pack(const float (&v)[4], float s) {
+#pragma clang fp contract(off)
+    return pk_f8x4(v[0] * s, v[1] * s, v[2] * s, v[3] * s);
+  }
+  static constexpr bool CHECKS_ALIGNMENT = true;
+  static constexpr bool RES_AS_WORD = true;       // ... as the 4-B word res_f32<J> reads
+};
+
 __device__ __forceinline__ void glds16(const void* src, char* lds_wave_base) {
   __builtin_amdgcn_global_load_lds((g_void_t*)src, (lds_void_t*)lds_wave_base, 16, 0, 0);
 }
@@ -359,36 +404,31 @@ __device__ __forceinline__ void store_tile(const drnmi_conv_args& p, const f32x4
   }
 }
 
-template <int FM, int FN>
-__device__ __forceinline__ void zero_tile(i32x4 (&acc)[FM][FN]) {
+template <typename A, int FM, int FN>
+__device__ __forceinline__ void zero_tile(A (&acc)[FM][FN]) {
 #pragma unroll
   for (int i = 0; i < FM; ++i)
 #pragma unroll
-    for (int j = 0; j < FN; ++j) acc[i][j] = i32x4{0, 0, 0, 0};
+    for (int j = 0; j < FN; ++j) acc[i][j] = A{0, 0, 0, 0};
 }
 
-template <int FM, int FN>
-__device__ __forceinline__ void zero_tile(f32x4 (&acc)[FM][FN]) {
-#pragma unroll
-  for (int i = 0; i < FM; ++i)
-#pragma unroll
-    for (int j = 0; j < FN; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-}
-
-// fp8 epilogue (include/drnmi.h DRNMI_F8): store_tile_i8's steps on fp32 accumulators and e4m3
-// bytes -- fmul, fadd, residual fmul + fadd, ReLU, e4m3(v * out_scale); no contraction, so
-// tests/fp8_ref.py restates it step for step.
-template <int FM, int WCO, int FN>
-__device__ __forceinline__ void store_tile_f8(const drnmi_conv_args& p, const f32x4 (&acc)[FM][FN], int cur_px0,
-                                              int cur_co0, int wc, int wp, int fr, int fq) {
-#pragma clang fp contract(off)
+// 8-bit epilogue, both codes (Q8<T>; include/drnmi.h drnmi_conv_args, int8 fields and DRNMI_F8): fmul,
+// fadd, residual fmul + fadd, ReLU, convert(v * out_scale) -- one fp32 rounding per step, no
+// contraction (fp contract off), so oracle/int8_oracle.py reproduces the int8 bytes bit for bit and
+// tests/fp8_ref.py restates the fp8 ones step for step.
+template <typename T, int FM, int WCO, int FN>
+__device__ __forceinline__ void store_tile_q8(const drnmi_conv_args& p, const typename KT<T>::acc (&acc)[FM][FN],
+                                              int cur_px0, int cur_co0, int wc, int wp, int fr, int fq) {
+#pragma clang fp contract(off)   // hipcc contracts a*b+c into v_fma by default (also inside inlined
+                                 // __fmul_rn / __fadd_rn): the epilogue is fmul then fadd
+  using Q = Q8<T>;
   constexpr int PXW = 16 * FN;
   const int M = p.n * p.ho * p.wo;
   const int hw_o = p.ho * p.wo;
   const uint8_t* __restrict__ res = reinterpret_cast<const uint8_t*>(p.res);
-  const bool packed4 = p.out_dtype == DRNMI_F8 && p.y_sc == 1 && (p.y_sp & 3) == 0 && (p.y_sn & 3) == 0 &&
-                       (reinterpret_cast<uintptr_t>(p.y) & 3) == 0;
-  const bool res4 = (p.cout & 3) == 0 && (reinterpret_cast<uintptr_t>(p.res) & 3) == 0;
+  const bool packed4 = p.out_dtype == Q::OUT && p.y_sc == 1 &&
+                       (!Q::CHECKS_ALIGNMENT || ((p.y_sp & 3) == 0 && (p.y_sn & 3) == 0 && (reinterpret_cast<uintptr_t>(p.y) & 3) == 0));
+  const bool res4 = (p.cout & 3) == 0 && (!Q::CHECKS_ALIGNMENT || (reinterpret_cast<uintptr_t>(p.res) & 3) == 0);
 #pragma unroll
   for (int fn = 0; fn < FN; ++fn) {
     const int m = cur_px0 + wp * PXW + fn * 16 + fr;
@@ -404,31 +444,51 @@ __device__ __forceinline__ void store_tile_f8(const drnmi_conv_args& p, const f3
       const float4 sc = *reinterpret_cast<const float4*>(p.scale + co);   // padded to cout_pad
       const float4 sh = *reinterpret_cast<const float4*>(p.shift + co);
       float v[4];
-      v[0] = acc[fm][fn][0] * sc.x + sh.x;
-      v[1] = acc[fm][fn][1] * sc.y + sh.y;
-      v[2] = acc[fm][fn][2] * sc.z + sh.z;
-      v[3] = acc[fm][fn][3] * sc.w + sh.w;
+      v[0] = Q::acc_f32(acc[fm][fn][0]) * sc.x + sh.x;
+      v[1] = Q::acc_f32(acc[fm][fn][1]) * sc.y + sh.y;
+      v[2] = Q::acc_f32(acc[fm][fn][2]) * sc.z + sh.z;
+      v[3] = Q::acc_f32(acc[fm][fn][3]) * sc.w + sh.w;
       if (res != nullptr) {
-        uint32_t rw = 0;
+        // the group's four residual bytes: one 4-B load, or byte by byte inside cout.  fp8 gathers
+        // them into a word (its conversion selects the byte); int8 keeps four sign-extended bytes
+        // (signed byte loads).  One constexpr branch and not a Q8 method: behind a call, however it
+        // hands the bytes back, conv_i8_stag_kernel takes two more SGPRs and the fp8 kernels' text
+        // changes (profiles/q8_fold)
         const uint8_t* rp = res + static_cast<int64_t>(m) * p.cout + co;
-        if (full && res4) {
-          rw = *reinterpret_cast<const uint32_t*>(rp);
-        } else {
+        if constexpr (Q::RES_AS_WORD) {
+          uint32_t rw = 0;
+          if (full && res4) {
+            rw = *reinterpret_cast<const uint32_t*>(rp);
+          } else {
 #pragma unroll
-          for (int j = 0; j < 4; ++j)
-            if (co + j < p.cout) rw |= static_cast<uint32_t>(rp[j]) << (8 * j);
+            for (int j = 0; j < 4; ++j)
+              if (co + j < p.cout) rw |= static_cast<uint32_t>(rp[j]) << (8 * j);
+          }
+          v[0] = v[0] + Q::template res_f32<0>(rw) * p.res_scale;
+          v[1] = v[1] + Q::template res_f32<1>(rw) * p.res_scale;
+          v[2] = v[2] + Q::template res_f32<2>(rw) * p.res_scale;
+          v[3] = v[3] + Q::template res_f32<3>(rw) * p.res_scale;
+        } else {
+          int8_t r[4] = {0, 0, 0, 0};
+          if (full && res4) {
+            const uint32_t rw = *reinterpret_cast<const uint32_t*>(rp);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) r[j] = static_cast<int8_t>((rw >> (8 * j)) & 0xff);
+          } else {
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+              if (co + j < p.cout) r[j] = reinterpret_cast<const int8_t*>(rp)[j];
+          }
+#pragma unroll
+          for (int j = 0; j < 4; ++j) v[j] = v[j] + static_cast<float>(r[j]) * p.res_scale;
         }
-        v[0] = v[0] + f8_to_f32<0>(rw) * p.res_scale;
-        v[1] = v[1] + f8_to_f32<1>(rw) * p.res_scale;
-        v[2] = v[2] + f8_to_f32<2>(rw) * p.res_scale;
-        v[3] = v[3] + f8_to_f32<3>(rw) * p.res_scale;
       }
       if (p.relu) {
 #pragma unroll
         for (int j = 0; j < 4; ++j) v[j] = fmaxf(v[j], 0.f);
       }
-      if (p.out_dtype == DRNMI_F8) {
-        const uint32_t o = pk_f8x4(v[0] * p.out_scale, v[1] * p.out_scale, v[2] * p.out_scale, v[3] * p.out_scale);
+      if (p.out_dtype == Q::OUT) {
+        const uint32_t o = Q::pack(v, p.out_scale);
         uint8_t* y = reinterpret_cast<uint8_t*>(p.y);
         if (packed4 && full) {
           *reinterpret_cast<uint32_t*>(y + ybase + co) = o;
@@ -437,91 +497,6 @@ __device__ __forceinline__ void store_tile_f8(const drnmi_conv_args& p, const f3
           for (int j = 0; j < 4; ++j) {
             if (co + j >= p.cout) break;
             y[ybase + static_cast<int64_t>(co + j) * p.y_sc] = static_cast<uint8_t>((o >> (8 * j)) & 0xff);
-          }
-        }
-      } else if (p.out_dtype == DRNMI_F32 && p.y_sc == 1 && (p.y_sp & 3) == 0 && (p.y_sn & 3) == 0 &&
-                 (reinterpret_cast<uintptr_t>(p.y) & 15) == 0 && (full || p.y_sp == ((p.cout + 3) & ~3))) {
-        // fp32 NHWC rows, as store_tile_i8: a partial group only into the pixel's own padding
-        *reinterpret_cast<float4*>(reinterpret_cast<float*>(p.y) + ybase + co) = make_float4(v[0], v[1], v[2], v[3]);
-      } else {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          if (co + j >= p.cout) break;
-          const int64_t off = ybase + static_cast<int64_t>(co + j) * p.y_sc;
-          if (p.out_dtype == DRNMI_BF16) reinterpret_cast<uint16_t*>(p.y)[off] = f32_to_bf16(v[j]);
-          else reinterpret_cast<float*>(p.y)[off] = v[j];
-        }
-      }
-    }
-  }
-}
-
-// W8A8 epilogue (include/drnmi.h drnmi_conv_args, int8 fields): one fp32 rounding per step,
-// no contraction (fp contract off), so oracle/int8_oracle.py reproduces it bit for bit.
-template <int FM, int WCO, int FN>
-__device__ __forceinline__ void store_tile_i8(const drnmi_conv_args& p, const i32x4 (&acc)[FM][FN], int cur_px0,
-                                              int cur_co0, int wc, int wp, int fr, int fq) {
-#pragma clang fp contract(off)   // hipcc contracts a*b+c into v_fma by default (also inside inlined
-                                 // __fmul_rn / __fadd_rn): the epilogue is fmul then fadd
-  constexpr int PXW = 16 * FN;
-  const int M = p.n * p.ho * p.wo;
-  const int hw_o = p.ho * p.wo;
-  const int8_t* __restrict__ res = reinterpret_cast<const int8_t*>(p.res);
-  const bool packed4 = p.out_dtype == DRNMI_I8 && p.y_sc == 1;
-  const bool res4 = (p.cout & 3) == 0;
-#pragma unroll
-  for (int fn = 0; fn < FN; ++fn) {
-    const int m = cur_px0 + wp * PXW + fn * 16 + fr;
-    if (m >= M) continue;
-    const int n = m / hw_o;
-    const int q = m - n * hw_o;
-    const int64_t ybase = static_cast<int64_t>(n) * p.y_sn + static_cast<int64_t>(q) * p.y_sp;
-#pragma unroll
-    for (int fm = 0; fm < FM; ++fm) {
-      const int co = cur_co0 + wc * WCO + fm * 16 + fq * 4;
-      if (co >= p.cout) continue;
-      const bool full = co + 3 < p.cout;
-      const float4 sc = *reinterpret_cast<const float4*>(p.scale + co);   // padded to cout_pad
-      const float4 sh = *reinterpret_cast<const float4*>(p.shift + co);
-      float v[4];
-      v[0] = static_cast<float>(acc[fm][fn][0]) * sc.x + sh.x;
-      v[1] = static_cast<float>(acc[fm][fn][1]) * sc.y + sh.y;
-      v[2] = static_cast<float>(acc[fm][fn][2]) * sc.z + sh.z;
-      v[3] = static_cast<float>(acc[fm][fn][3]) * sc.w + sh.w;
-      if (res != nullptr) {
-        int8_t r[4] = {0, 0, 0, 0};
-        const int8_t* rp = res + static_cast<int64_t>(m) * p.cout + co;
-        if (full && res4) {
-          const uint32_t rw = *reinterpret_cast<const uint32_t*>(rp);
-#pragma unroll
-          for (int j = 0; j < 4; ++j) r[j] = static_cast<int8_t>((rw >> (8 * j)) & 0xff);
-        } else {
-#pragma unroll
-          for (int j = 0; j < 4; ++j)
-            if (co + j < p.cout) r[j] = rp[j];
-        }
-#pragma unroll
-        for (int j = 0; j < 4; ++j) v[j] = v[j] + static_cast<float>(r[j]) * p.res_scale;
-      }
-      if (p.relu) {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) v[j] = fmaxf(v[j], 0.f);
-      }
-      if (p.out_dtype == DRNMI_I8) {
-        uint32_t o = 0;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          const float t = fminf(fmaxf(rintf(v[j] * p.out_scale), -127.f), 127.f);
-          o |= static_cast<uint32_t>(static_cast<uint8_t>(static_cast<int8_t>(static_cast<int>(t)))) << (8 * j);
-        }
-        int8_t* y = reinterpret_cast<int8_t*>(p.y);
-        if (packed4 && full) {
-          *reinterpret_cast<uint32_t*>(y + ybase + co) = o;
-        } else {
-#pragma unroll
-          for (int j = 0; j < 4; ++j) {
-            if (co + j >= p.cout) break;
-            y[ybase + static_cast<int64_t>(co + j) * p.y_sc] = static_cast<int8_t>((o >> (8 * j)) & 0xff);
           }
         }
       } else if (p.out_dtype == DRNMI_F32 && p.y_sc == 1 && (p.y_sp & 3) == 0 && (p.y_sn & 3) == 0 &&
@@ -544,117 +519,27 @@ __device__ __forceinline__ void store_tile_i8(const drnmi_conv_args& p, const i3
   }
 }
 
-// store_tile_i8 for whole tiles of a dense int8 NHWC output (y_sc 1, y_sp cout): the same
-// per-element arithmetic, residual loads and output stores as 16-B pieces (common.h
-// transpose_rows4: row fq moves fragment 4 g + fq whole) instead of 4-B ones
-template <int FM, int WCO, int FN>
-__device__ __forceinline__ void store_tile_i8_x4(const drnmi_conv_args& p, const i32x4 (&acc)[FM][FN], int px0,
-                                                 int co0, int wc, int wp, int fr, int fq) {
-#pragma clang fp contract(off)
-  static_assert(FM % 4 == 0, "16-B int8 pieces");
-  constexpr int NG = FM / 4;                         // 64-B groups of the wave's channels per pixel
-  const int8_t* __restrict__ res = reinterpret_cast<const int8_t*>(p.res);
-  int8_t* __restrict__ y = reinterpret_cast<int8_t*>(p.y);
-  const int cbase = co0 + wc * WCO + fq * 16;
-  const bool lo = fr < 8;
-  // 128-B lines when the wave's channels span whole lines (NG even): groups (2 L, 2 L + 1) of
-  // pixels 0-7, then of pixels 8-15, lanes fr and fr ^ 8 trading the odd group (DPP row_ror:8)
-  constexpr bool LINES = NG % 2 == 0;
-  auto trade = [](uint4 v) {
-    uint4 r;
-    r.x = __builtin_amdgcn_update_dpp(0u, v.x, 0x128, 0xf, 0xf, false);
-    r.y = __builtin_amdgcn_update_dpp(0u, v.y, 0x128, 0xf, 0xf, false);
-    r.z = __builtin_amdgcn_update_dpp(0u, v.z, 0x128, 0xf, 0xf, false);
-    r.w = __builtin_amdgcn_update_dpp(0u, v.w, 0x128, 0xf, 0xf, false);
-    return r;
-  };
-  auto sel = [](bool c, uint4 a, uint4 b) {
-    return make_uint4(c ? a.x : b.x, c ? a.y : b.y, c ? a.z : b.z, c ? a.w : b.w);
-  };
-#pragma unroll
-  for (int fn = 0; fn < FN; ++fn) {
-    const int64_t m = px0 + wp * 16 * FN + fn * 16 + fr;
-    const int64_t m0 = m - (lo ? 0 : 8), m1 = m0 + 8;
-    uint4 rq[NG];
-    if (res != nullptr) {
-      if constexpr (LINES) {
-#pragma unroll
-        for (int L = 0; L < NG / 2; ++L) {
-          const uint4 d0 = *reinterpret_cast<const uint4*>(res + m0 * p.cout + cbase + (2 * L + (lo ? 0 : 1)) * 64);
-          const uint4 d1 = *reinterpret_cast<const uint4*>(res + m1 * p.cout + cbase + (2 * L + (lo ? 1 : 0)) * 64);
-          rq[2 * L] = sel(lo, d0, d1);
-          rq[2 * L + 1] = trade(sel(lo, d1, d0));
-        }
-      } else {
-#pragma unroll
-        for (int g = 0; g < NG; ++g) rq[g] = *reinterpret_cast<const uint4*>(res + m * p.cout + cbase + g * 64);
-      }
-    }
-    uint4 out[NG];
-#pragma unroll
-    for (int g = 0; g < NG; ++g) {
-      uint32_t rr[4] = {0, 0, 0, 0};
-      if (res != nullptr) {
-        rr[0] = rq[g].x;
-        rr[1] = rq[g].y;
-        rr[2] = rq[g].z;
-        rr[3] = rq[g].w;
-        transpose_rows4(rr);
-      }
-      uint32_t o[4];
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        const int fm = 4 * g + k;
-        const int co = co0 + wc * WCO + fm * 16 + fq * 4;
-        const float4 sc = *reinterpret_cast<const float4*>(p.scale + co);
-        const float4 sh = *reinterpret_cast<const float4*>(p.shift + co);
-        float v[4];
-        v[0] = static_cast<float>(acc[fm][fn][0]) * sc.x + sh.x;
-        v[1] = static_cast<float>(acc[fm][fn][1]) * sc.y + sh.y;
-        v[2] = static_cast<float>(acc[fm][fn][2]) * sc.z + sh.z;
-        v[3] = static_cast<float>(acc[fm][fn][3]) * sc.w + sh.w;
-        if (res != nullptr) {
-#pragma unroll
-          for (int j = 0; j < 4; ++j)
-            v[j] = v[j] + static_cast<float>(static_cast<int8_t>((rr[k] >> (8 * j)) & 0xff)) * p.res_scale;
-        }
-        if (p.relu) {
-#pragma unroll
-          for (int j = 0; j < 4; ++j) v[j] = fmaxf(v[j], 0.f);
-        }
-        uint32_t w = 0;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          const float t = fminf(fmaxf(rintf(v[j] * p.out_scale), -127.f), 127.f);
-          w |= static_cast<uint32_t>(static_cast<uint8_t>(static_cast<int8_t>(static_cast<int>(t)))) << (8 * j);
-        }
-        o[k] = w;
-      }
-      transpose_rows4(o);
-      out[g] = make_uint4(o[0], o[1], o[2], o[3]);
-    }
-    if constexpr (LINES) {
-#pragma unroll
-      for (int L = 0; L < NG / 2; ++L) {
-        const uint4 r = trade(out[2 * L + 1]);
-        *reinterpret_cast<uint4*>(y + m0 * p.cout + cbase + (2 * L + (lo ? 0 : 1)) * 64) = sel(lo, out[2 * L], r);
-        *reinterpret_cast<uint4*>(y + m1 * p.cout + cbase + (2 * L + (lo ? 1 : 0)) * 64) = sel(lo, r, out[2 * L]);
-      }
-    } else {
-#pragma unroll
-      for (int g = 0; g < NG; ++g) *reinterpret_cast<uint4*>(y + m * p.cout + cbase + g * 64) = out[g];
-    }
-  }
+// a dense 8-bit NHWC output in the code's own type (y_sc 1, y_sp cout) that passes the code's guard
+// for 16-B accesses: store_tile_q8_x4 for the tiles that lie whole inside it
+template <typename T>
+__device__ __forceinline__ bool q8_dense_x4(const drnmi_conv_args& p) {
+  const bool dense = p.out_dtype == Q8<T>::OUT && p.y_sc == 1 && p.y_sp == p.cout &&
+                     p.y_sn == static_cast<int64_t>(p.ho) * p.wo * p.cout;
+  if constexpr (Q8<T>::CHECKS_ALIGNMENT)
+    return dense && ((reinterpret_cast<uintptr_t>(p.y) | reinterpret_cast<uintptr_t>(p.res)) & 15) == 0;
+  else
+    return dense && (p.res == nullptr || p.cout % 16 == 0);
 }
 
-// store_tile_f8 for whole tiles of a dense e4m3 NHWC output (y_sc 1, y_sp cout, y and res 16-B
-// aligned): the same per-element arithmetic; residual loads and output stores as 16-B pieces, the
-// byte movement of store_tile_i8_x4
-template <int FM, int WCO, int FN>
-__device__ __forceinline__ void store_tile_f8_x4(const drnmi_conv_args& p, const f32x4 (&acc)[FM][FN], int px0,
-                                                 int co0, int wc, int wp, int fr, int fq) {
+// store_tile_q8 for whole tiles of such an output: the same per-element arithmetic, residual loads
+// and output stores as 16-B pieces (common.h transpose_rows4: row fq moves fragment 4 g + fq whole)
+// instead of 4-B ones
+template <typename T, int FM, int WCO, int FN>
+__device__ __forceinline__ void store_tile_q8_x4(const drnmi_conv_args& p, const typename KT<T>::acc (&acc)[FM][FN],
+                                                 int px0, int co0, int wc, int wp, int fr, int fq) {
 #pragma clang fp contract(off)
-  static_assert(FM % 4 == 0, "16-B e4m3 pieces");
+  using Q = Q8<T>;
+  static_assert(FM % 4 == 0, "16-B pieces of 8-bit channels");
   constexpr int NG = FM / 4;                         // 64-B groups of the wave's channels per pixel
   const uint8_t* __restrict__ res = reinterpret_cast<const uint8_t*>(p.res);
   uint8_t* __restrict__ y = reinterpret_cast<uint8_t*>(p.y);
@@ -712,21 +597,21 @@ __device__ __forceinline__ void store_tile_f8_x4(const drnmi_conv_args& p, const
         const float4 sc = *reinterpret_cast<const float4*>(p.scale + co);
         const float4 sh = *reinterpret_cast<const float4*>(p.shift + co);
         float v[4];
-        v[0] = acc[fm][fn][0] * sc.x + sh.x;
-        v[1] = acc[fm][fn][1] * sc.y + sh.y;
-        v[2] = acc[fm][fn][2] * sc.z + sh.z;
-        v[3] = acc[fm][fn][3] * sc.w + sh.w;
+        v[0] = Q::acc_f32(acc[fm][fn][0]) * sc.x + sh.x;
+        v[1] = Q::acc_f32(acc[fm][fn][1]) * sc.y + sh.y;
+        v[2] = Q::acc_f32(acc[fm][fn][2]) * sc.z + sh.z;
+        v[3] = Q::acc_f32(acc[fm][fn][3]) * sc.w + sh.w;
         if (res != nullptr) {
-          v[0] = v[0] + f8_to_f32<0>(rr[k]) * p.res_scale;
-          v[1] = v[1] + f8_to_f32<1>(rr[k]) * p.res_scale;
-          v[2] = v[2] + f8_to_f32<2>(rr[k]) * p.res_scale;
-          v[3] = v[3] + f8_to_f32<3>(rr[k]) * p.res_scale;
+          v[0] = v[0] + Q::template res_f32<0>(rr[k]) * p.res_scale;
+          v[1] = v[1] + Q::template res_f32<1>(rr[k]) * p.res_scale;
+          v[2] = v[2] + Q::template res_f32<2>(rr[k]) * p.res_scale;
+          v[3] = v[3] + Q::template res_f32<3>(rr[k]) * p.res_scale;
         }
         if (p.relu) {
 #pragma unroll
           for (int j = 0; j < 4; ++j) v[j] = fmaxf(v[j], 0.f);
         }
-        o[k] = pk_f8x4(v[0] * p.out_scale, v[1] * p.out_scale, v[2] * p.out_scale, v[3] * p.out_scale);
+        o[k] = Q::pack(v, p.out_scale);
       }
       transpose_rows4(o);
       out[g] = make_uint4(o[0], o[1], o[2], o[3]);

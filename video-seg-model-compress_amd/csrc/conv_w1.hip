@@ -207,7 +207,7 @@ __device__ __forceinline__ void conv_w1_body(const drnmi_conv_args& p, const W1S
   const int s_q = px0 - s_n * hw_o;
   const int s_oh = s_q / p.wo;
   const int s_ow0 = s_q - s_oh * p.wo;
-  const int xbytes = p.n * H * W * cin * ESZ;        // < 2^31 (big_conv_supported / i8_conv_supported)
+  const int xbytes = p.n * H * W * cin * ESZ;        // < 2^31 (big_conv_supported / q8_conv_supported)
   const __amdgpu_buffer_rsrc_t rs_x = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p.x), 0, xbytes, 0x00020000);
   const __amdgpu_buffer_rsrc_t rs_w = __builtin_amdgcn_make_buffer_rsrc(
       const_cast<void*>(p.wgt), 0, p.cout_pad * p.k_pad * ESZ, 0x00020000);
@@ -561,7 +561,7 @@ __device__ __forceinline__ void conv_w1_body(const drnmi_conv_args& p, const W1S
       w1_seg_i8<FM, FN>(p, acc, px0, co0, wc, wp, fr, fq, lane, sf, smem + AB);
     } else {
       // the dispatch (i8_w1_ok) admits only a dense int8 NHWC output: 16-B pieces
-      store_tile_i8_x4<FM, WCO, FN>(p, acc, px0, co0, wc, wp, fr, fq);
+      store_tile_q8_x4<int8_t, FM, WCO, FN>(p, acc, px0, co0, wc, wp, fr, fq);
     }
   } else if constexpr (!SEGF) {
     store_tile_x4<FM, WCO, FN>(p, acc, px0, co0, wc, wp, fr, fq);

@@ -403,7 +403,7 @@ __device__ __forceinline__ void store_labels4(void* labels, int64_t pix, const i
 }
 
 // int8 nets: the logits of the int8 seg conv from its two int32 partial planes: (float)(p0 + p1) *
-// scale + shift, fmul then fadd as store_tile_i8 (no contraction)
+// scale + shift, fmul then fadd as store_tile_q8 (no contraction)
 template <int NC, typename B>
 __device__ __forceinline__ void load_taps_seg2_i8(const int* src, int64_t half, int w, int cs, const B& scale,
                                                   const B& shift, int iy, int ix, float (&d)[NC]) {

@@ -325,7 +325,7 @@ class PackedNet:
                 nd.i8, nd.x_val, nd.r_val, nd.res_scale, nd.out_scale = False, nd.src, nd.res, 0.0, 0.0
                 nd.x6 = False
                 if ni in self.i8_nodes:
-                    (self._pack_fp8 if self.qcode == _lib.DRNMI_F8 else self._pack_int8)(nd, full, scale, cout)
+                    self._pack_q8(nd, full, scale, cout)
                     continue
                 if self.precision == "fp32x" and cs >= X6_MIN_CIN and kh in (1, 3):
                     nd.x6 = True
@@ -476,28 +476,25 @@ class PackedNet:
                         "x2_val": ds.src, "stride2": ds.conv.stride[0], "ds": j}
             ds.fused_into = i
 
-    def _pack_int8(self, nd: ConvNode, full: torch.Tensor, bn_scale: torch.Tensor, cout: int):
-        """Per-output-channel symmetric int8 weights (oracle/int8_oracle.py quantize_weight_rows):
-        s_w = absmax / 127, q = clamp(rint(w * 127 / absmax)); the epilogue scale is
-        s_w * s_x * bn_scale, so acc * scale is the dequantised, BN-scaled conv output."""
-        a = full.abs().amax(dim=1)
-        pos = a > 0
-        inv = torch.where(pos, 127.0 / torch.where(pos, a, torch.ones_like(a)), torch.ones_like(a))
-        nd.wpk = torch.round(full * inv[:, None]).clamp_(-127, 127).to(torch.int8).contiguous()
-        sw = torch.where(pos, a / 127.0, torch.ones_like(a))
-        self._q8_fields(nd, sw, bn_scale)
+    # per 8-bit code: the largest magnitude, and fp32 weights scaled to that range -> the stored bytes
+    # (int8: oracle/int8_oracle.py quantize_weight_rows; e4m3 is converted on the host: one conversion
+    # routine for every device)
+    _Q8_ENCODE = {
+        _lib.DRNMI_I8: (127.0, lambda q: torch.round(q).clamp_(-127, 127).to(torch.int8)),
+        _lib.DRNMI_F8: (F8_MAX, lambda q: q.clamp_(-F8_MAX, F8_MAX).cpu().to(torch.float8_e4m3fn).view(torch.uint8)),
+    }
 
-    def _pack_fp8(self, nd: ConvNode, full: torch.Tensor, bn_scale: torch.Tensor, cout: int):
-        """Per-output-channel e4m3 weights (include/drnmi.h DRNMI_F8): a = absmax(row), q = e4m3(w *
-        (448 / a)) stored as bytes, s_w = a / 448 (1 for an all-zero row); the epilogue scale is
-        s_w * s8_x * bn_scale with s8_x = s_x * 127 / 448."""
+    def _pack_q8(self, nd: ConvNode, full: torch.Tensor, bn_scale: torch.Tensor, cout: int):
+        """Per-output-channel symmetric 8-bit weights in the net's code (include/drnmi.h DRNMI_I8 /
+        DRNMI_F8), qmax = 127 / 448: a = absmax(row), q = encode(w * (qmax / a)), s_w = a / qmax (1
+        for an all-zero row); the epilogue scale is s_w * s_x * bn_scale (s_x: the code's activation
+        scale, act_scale()), so acc * scale is the dequantised, BN-scaled conv output."""
+        qmax, encode = self._Q8_ENCODE[self.qcode]
         a = full.abs().amax(dim=1)
         pos = a > 0
-        inv = torch.where(pos, F8_MAX / torch.where(pos, a, torch.ones_like(a)), torch.ones_like(a))
-        q = (full * inv[:, None]).clamp_(-F8_MAX, F8_MAX)
-        # (converted on the host: one conversion routine for every device)
-        nd.wpk = q.cpu().to(torch.float8_e4m3fn).view(torch.uint8).to(full.device).contiguous()
-        self._q8_fields(nd, torch.where(pos, a / F8_MAX, torch.ones_like(a)), bn_scale)
+        inv = torch.where(pos, qmax / torch.where(pos, a, torch.ones_like(a)), torch.ones_like(a))
+        nd.wpk = encode(full * inv[:, None]).to(full.device).contiguous()
+        self._q8_fields(nd, torch.where(pos, a / qmax, torch.ones_like(a)), bn_scale)
 
     def _q8_fields(self, nd: ConvNode, sw: torch.Tensor, bn_scale: torch.Tensor):
         """What an 8-bit launch carries besides its weights, for either 8-bit code."""
@@ -768,7 +765,7 @@ class Plan:
     # labels-only video path: the seg conv writes fp32 NHWC rows of SEG_NHWC_CS floats (16-B
     # stores instead of 19 strided planes) and drnmi_up8_labels_nhwc reads them; same values,
     # same labels.  Only where the seg conv runs on conv_big (bf16 input), on the int8 tile
-    # (int8 nets: store_tile_i8's 16-B fp32 rows) or on conv_x6 (fp32x) and the 19-class head.
+    # (int8 nets: store_tile_q8's 16-B fp32 rows) or on conv_x6 (fp32x) and the 19-class head.
     # Any other class count 1 .. 256 (bf16 and int8 plans): rows of round_up(classes, 4) floats
     # and drnmi_up8_labels_nhwc_wide; the seg classifier is not folded into the last conv there.
     SEG_NHWC_CS = 20
