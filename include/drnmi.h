@@ -642,9 +642,9 @@ int drnmi_conv_wgrad_f32x3(const drnmi_wgrad_args* args, void* stream);
  * kernel); pix_per_split: pixels per split, a multiple of 32 (the last split is ragged when
  * n*ho*wo % pix_per_split != 0; unused by the direct kernel); reduce: 0 = one thread per output,
  * 1 = the grouped reduce (>= 32 splits).  Out pointers may be NULL.  DRNMI_EINVAL on bad geometry. */
-#define DRNMI_WGRAD_F32 0     /* wgrad_kernel<false>: exact-f32 MFMA, 64 x 64 tile            */
-#define DRNMI_WGRAD_X6 1      /* wgrad_kernel<true>: split-bf16, 64 x 64 tile                 */
-#define DRNMI_WGRAD_BIG 2     /* wgrad_x6_big_kernel: split-bf16, 128 x 128 tile              */
+#define DRNMI_WGRAD_F32 0     /* wgrad_kernel<64, false>: exact-f32 MFMA, 64 x 64 tile        */
+#define DRNMI_WGRAD_X6 1      /* wgrad_kernel<64, true>: split-bf16, 64 x 64 tile             */
+#define DRNMI_WGRAD_BIG 2     /* wgrad_kernel<128, true>: split-bf16, 128 x 128 tile          */
 #define DRNMI_WGRAD_PRE 3     /* wgrad_dy_split_kernel + wgrad_x6_pre_kernel (K >= 1024)      */
 #define DRNMI_WGRAD_DIRECT 4  /* wgrad_x6_direct_kernel: cout <= 32, wo % 32 == 0             */
 int drnmi_conv_wgrad_plan(const drnmi_wgrad_args* args, int32_t x6, int32_t* kernel, int32_t* splits,

@@ -298,7 +298,7 @@ def test_wgrad_plan_query():
         a = A.wgrad_args(n, cin, cs, cout, dys, ks, s, p, d, h, w)
         kernel, splits, per, reduce = _lib.wgrad_plan(a, x6)
         M = n * a.ho * a.wo
-        assert (kernel == "wgrad_kernel<false>") == (not x6), case
+        assert (kernel == "wgrad_kernel<64, false>") == (not x6), case
         if kernel != "wgrad_x6_direct_kernel":
             assert per % 32 == 0 and (splits - 1) * per < M <= splits * per, (case, splits, per)
         else:
@@ -337,7 +337,7 @@ def test_gpu_cases_reach_every_workload_route_class():
     assert not cx - got_cx, sorted(cx - got_cx)
     # the ragged classes also with a pixel count that is no multiple of the 32-pixel chunk
     for c in wg:
-        if c[3] and c[0] in ("wgrad_kernel<false>", "wgrad_x6_pre_kernel") and c[1] == "2..31":
+        if c[3] and c[0] in ("wgrad_kernel<64, false>", "wgrad_x6_pre_kernel") and c[1] == "2..31":
             assert c[:4] + (True,) in got_wg, c
 
 

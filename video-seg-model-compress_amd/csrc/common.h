@@ -51,6 +51,29 @@ __device__ __forceinline__ void split3(const float4& lo4, const float4& hi4, bf1
   b3 = __builtin_bit_cast(bf16x8, make_uint4(u3[0], u3[1], u3[2], u3[3]));
 }
 
+// c += a * b on the split3 planes of both operands (a1 + a2 + a3, b1 + b2 + b3, largest first): the
+// six products above 2^-24 of the leading one, smallest first.  Every fp32x kernel accumulates in
+// this order, which is what makes their sums comparable bit for bit.
+__device__ __forceinline__ void mfma_x6(f32x4& c, const bf16x8 (&a)[3], const bf16x8 (&b)[3]) {
+  c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[2], b[0], c, 0, 0, 0);
+  c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[1], b[1], c, 0, 0, 0);
+  c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[0], b[2], c, 0, 0, 0);
+  c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[1], b[0], c, 0, 0, 0);
+  c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[0], b[1], c, 0, 0, 0);
+  c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[0], b[0], c, 0, 0, 0);
+}
+
+// 16-B chunk `chunk` of 64-B LDS row `row` (32 bf16): conflict-free for every ds_read_b128 lane
+// group (conv_big.hip swzb<64>)
+__device__ __forceinline__ int swz64(int row, int chunk) { return chunk ^ (((row >> 3) & 1) * 3); }
+
+// one ds_read_b128 at LDS byte address base + OFF.  Inline asm: the caller counts lgkmcnt itself
+template <int OFF, typename V>
+__device__ __forceinline__ void ds_rd(V& dst, uint32_t base) {
+  static_assert(sizeof(V) == 16 && OFF >= 0 && OFF < 65536, "ds_read_b128 offset");
+  asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(base), "i"(OFF));
+}
+
 // OCP e4m3fn bytes (include/drnmi.h DRNMI_F8).  f8_t tags the element type of the fp8 kernels.
 struct f8_t { uint8_t v; };
 constexpr float kF8Max = 448.f;
@@ -127,5 +150,11 @@ __device__ __forceinline__ void transpose_rows4(uint32_t (&r)[4]) {
 }
 
 inline int ceil_div(int64_t a, int64_t b) { return static_cast<int>((a + b - 1) / b); }
+
+// workgroups of `per` threads for the n elements of a grid-stride kernel (at least 1, at most 2^20 - 16)
+inline unsigned grid_of(int64_t n, int per = 256) {
+  const int64_t g = (n + per - 1) / per;
+  return static_cast<unsigned>(g < 1 ? 1 : (g > 65535 * 16 ? 65535 * 16 : g));
+}
 
 }  // namespace drnmi

@@ -50,8 +50,7 @@ __device__ __forceinline__ int xcd_remap(int bid, int nwg) {
   return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + bid / 8;
 }
 
-// bf16 A rows (64 B): conflict-free for every ds_read_b128 lane group (conv_big.hip swzb<64>)
-__device__ __forceinline__ int swz64(int row, int chunk) { return chunk ^ (((row >> 3) & 1) * 3); }
+// swz64 (bf16 A rows, 64 B) is common.h's
 __device__ __forceinline__ int swz128(int row, int chunk) { return chunk ^ ((row >> 1) & 7); }   // fp32 B rows
 
 
@@ -74,12 +73,7 @@ __device__ __forceinline__ double row16_sum(double x) {
   return x;
 }
 
-// one ds_read_b128 at LDS byte address base + OFF (smem is the kernel's only LDS object: byte 0)
-template <int OFF, typename V>
-__device__ __forceinline__ void ds_rd(V& dst, uint32_t base) {
-  static_assert(sizeof(V) == 16 && OFF >= 0 && OFF < 65536, "ds_read_b128 offset");
-  asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(base), "i"(OFF));
-}
+// ds_rd (common.h) reads at LDS byte address base + OFF: smem is the kernel's only LDS object, byte 0
 
 // Tile = BCO = WCO x WC output channels x BPX = 64 x PS pixels; one wave per (channel column,
 // 64-pixel slice).  PS = 4: one workgroup per CU (2- or 3-stage ring in up to 160 KB of LDS);

@@ -203,7 +203,7 @@ argmax_nchw_kernel(const float* __restrict__ x, int n, int c, int64_t hw, void* 
   }
 }
 
-unsigned grid_of(int64_t n) {
+unsigned resize_grid(int64_t n) {
   const int64_t b = (n + kThreads - 1) / kThreads;
   return static_cast<unsigned>(b < 65536 ? (b > 0 ? b : 1) : 65536);
 }
@@ -251,10 +251,10 @@ Plan make_plan(int n, int h, int w, int oh, int ow, int elem) {
 }
 
 void launch_coeffs(const Plan& q, char* ws, hipStream_t s) {
-  hipLaunchKernelGGL(coeffs_kernel, dim3(grid_of(q.ax.out)), dim3(kThreads), 0, s, q.ax.in, q.ax.out, q.ax.ksize,
+  hipLaunchKernelGGL(coeffs_kernel, dim3(resize_grid(q.ax.out)), dim3(kThreads), 0, s, q.ax.in, q.ax.out, q.ax.ksize,
                      q.ax.scale, q.ax.filterscale, q.ax.support, reinterpret_cast<int*>(ws + q.off_bh),
                      reinterpret_cast<double*>(ws + q.off_kh), reinterpret_cast<int*>(ws + q.off_k8h));
-  hipLaunchKernelGGL(coeffs_kernel, dim3(grid_of(q.ay.out)), dim3(kThreads), 0, s, q.ay.in, q.ay.out, q.ay.ksize,
+  hipLaunchKernelGGL(coeffs_kernel, dim3(resize_grid(q.ay.out)), dim3(kThreads), 0, s, q.ay.in, q.ay.out, q.ay.ksize,
                      q.ay.scale, q.ay.filterscale, q.ay.support, reinterpret_cast<int*>(ws + q.off_bv),
                      reinterpret_cast<double*>(ws + q.off_kv), reinterpret_cast<int*>(ws + q.off_k8v));
 }
@@ -290,13 +290,13 @@ extern "C" int drnmi_resize_bilinear_u8(const uint8_t* src, int32_t n, int32_t h
     return static_cast<int>(hipMemcpyAsync(dst, src, static_cast<size_t>(n) * h * w * 3, hipMemcpyDeviceToDevice, s));
   if (q.need_h) {
     uint8_t* out = q.need_v ? tmp : dst;
-    hipLaunchKernelGGL(resize_h_u8_kernel, dim3(grid_of(static_cast<int64_t>(n) * q.rows * ow)), dim3(kThreads), 0, s,
+    hipLaunchKernelGGL(resize_h_u8_kernel, dim3(resize_grid(static_cast<int64_t>(n) * q.rows * ow)), dim3(kThreads), 0, s,
                        src, n, h, w, q.row0, q.rows, ow, q.ax.ksize, bh, reinterpret_cast<const int*>(wsb + q.off_k8h),
                        out);
   }
   if (q.need_v) {
     const uint8_t* vin = q.need_h ? tmp : src;
-    hipLaunchKernelGGL(resize_v_u8_kernel, dim3(grid_of(static_cast<int64_t>(n) * oh * ow)), dim3(kThreads), 0, s,
+    hipLaunchKernelGGL(resize_v_u8_kernel, dim3(resize_grid(static_cast<int64_t>(n) * oh * ow)), dim3(kThreads), 0, s,
                        vin, n, q.need_h ? q.rows : h, ow, oh, q.ay.ksize, q.need_h ? q.row0 : 0, bv,
                        reinterpret_cast<const int*>(wsb + q.off_k8v), dst);
   }
@@ -316,23 +316,23 @@ extern "C" int drnmi_resize_bilinear_f32(const float* src, int32_t planes, int32
   const int* bv = reinterpret_cast<const int*>(wsb + q.off_bv);
   float* tmp = reinterpret_cast<float*>(wsb + q.off_tmp);
   if (!q.need_h && !q.need_v) {
-    hipLaunchKernelGGL(copy_f32_kernel, dim3(grid_of(static_cast<int64_t>(planes) * h * w)), dim3(kThreads), 0, s, src,
+    hipLaunchKernelGGL(copy_f32_kernel, dim3(resize_grid(static_cast<int64_t>(planes) * h * w)), dim3(kThreads), 0, s, src,
                        static_cast<int64_t>(planes) * h * w, dst, accumulate);
     return static_cast<int>(hipGetLastError());
   }
   if (q.need_h) {
     float* out = q.need_v ? tmp : dst;
     if (!q.need_v && accumulate) out = tmp;
-    hipLaunchKernelGGL(resize_h_f32_kernel, dim3(grid_of(static_cast<int64_t>(planes) * q.rows * ow)), dim3(kThreads), 0,
+    hipLaunchKernelGGL(resize_h_f32_kernel, dim3(resize_grid(static_cast<int64_t>(planes) * q.rows * ow)), dim3(kThreads), 0,
                        s, src, planes, h, w, q.row0, q.rows, ow, q.ax.ksize, bh,
                        reinterpret_cast<const double*>(wsb + q.off_kh), out);
     if (!q.need_v && accumulate)
-      hipLaunchKernelGGL(copy_f32_kernel, dim3(grid_of(static_cast<int64_t>(planes) * h * ow)), dim3(kThreads), 0, s, tmp,
+      hipLaunchKernelGGL(copy_f32_kernel, dim3(resize_grid(static_cast<int64_t>(planes) * h * ow)), dim3(kThreads), 0, s, tmp,
                          static_cast<int64_t>(planes) * h * ow, dst, 1);
   }
   if (q.need_v) {
     const float* vin = q.need_h ? tmp : src;
-    hipLaunchKernelGGL(resize_v_f32_kernel, dim3(grid_of(static_cast<int64_t>(planes) * oh * ow)), dim3(kThreads), 0, s,
+    hipLaunchKernelGGL(resize_v_f32_kernel, dim3(resize_grid(static_cast<int64_t>(planes) * oh * ow)), dim3(kThreads), 0, s,
                        vin, planes, q.need_h ? q.rows : h, ow, oh, q.ay.ksize, q.need_h ? q.row0 : 0, bv,
                        reinterpret_cast<const double*>(wsb + q.off_kv), dst, accumulate);
   }
@@ -346,10 +346,10 @@ extern "C" int drnmi_argmax_nchw_f32(const float* x, int32_t n, int32_t c, int64
   if (label_dtype == DRNMI_U8 && c > 256) return DRNMI_EINVAL;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   if (label_dtype == DRNMI_U8)
-    hipLaunchKernelGGL(argmax_nchw_kernel<DRNMI_U8>, dim3(grid_of(static_cast<int64_t>(n) * hw)), dim3(kThreads), 0, s,
+    hipLaunchKernelGGL(argmax_nchw_kernel<DRNMI_U8>, dim3(resize_grid(static_cast<int64_t>(n) * hw)), dim3(kThreads), 0, s,
                        x, n, c, hw, labels);
   else
-    hipLaunchKernelGGL(argmax_nchw_kernel<DRNMI_I64>, dim3(grid_of(static_cast<int64_t>(n) * hw)), dim3(kThreads), 0, s,
+    hipLaunchKernelGGL(argmax_nchw_kernel<DRNMI_I64>, dim3(resize_grid(static_cast<int64_t>(n) * hw)), dim3(kThreads), 0, s,
                        x, n, c, hw, labels);
   return static_cast<int>(hipGetLastError());
 }

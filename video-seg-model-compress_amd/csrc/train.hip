@@ -5,15 +5,14 @@
 // (semantic_seg.py:166-230, :817, :963-966; pruners/Pruner.py:17-20).  The convs' forward
 // and data-gradient (dgrad) passes reuse the implicit-GEMM conv of conv_igemm.hip (dgrad =
 // a stride-1 conv of dy with transposed/flipped weights, after a zero-insert for stride-s
-// layers); this file holds everything else:
+// layers) and the conv weight gradient is wgrad.hip; this file holds everything else:
 //
 //   pack_conv_weight   OIHW fp32 -> packed [rows_pad][k_pad] (forward or dgrad layout)
 //   bn stats / apply   train-mode BatchNorm2d: batch mean / biased var, running-stat update
 //                      (momentum, unbiased var), y -> relu(bn(y) [+ res])
 //   bn backward        relu mask, dgamma / dbeta, dy, residual-branch gradient
 //   channel_sum        per-channel column sums (conv bias gradient)
-//   conv_wgrad         weight gradient: GEMM over pixels, v_mfma_f32_16x16x4f32, split over
-//                      pixel ranges with a fixed-order (deterministic) reduction
+//   split3_bf16        fp32 -> three bf16 planes: the weight side of the fp32x forward pass
 //   zero_insert        dy of a stride-s conv spread onto the input grid (dgrad input)
 //   up8_lsm_bwd        LogSoftmax backward + transpose of the fixed bilinear up-conv
 //   ce_loss            CrossEntropyLoss(ignore_index) forward / backward on log-probs
@@ -31,11 +30,6 @@ constexpr int kThreads = 256;
 
 inline bool aligned16(const void* a, const void* b, const void* c) {
   return ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b) | reinterpret_cast<uintptr_t>(c)) & 15) == 0;
-}
-
-inline unsigned grid_of(int64_t n, int per = kThreads) {
-  const int64_t g = (n + per - 1) / per;
-  return static_cast<unsigned>(g < 1 ? 1 : (g > 65535 * 16 ? 65535 * 16 : g));
 }
 
 // ------------------------------------------------------------------ weight packing
@@ -548,884 +542,6 @@ colsum_final_kernel(const double* __restrict__ ws, int G, int C, int cvalid, flo
   double s = 0;
   for (int g = 0; g < G; ++g) s += ws[static_cast<int64_t>(g) * C + c];
   out[c] = acc ? out[c] + static_cast<float>(s) : static_cast<float>(s);
-}
-
-// ------------------------------------------------------------------ weight gradient
-// dW[co][tap][ci] = sum_m dy[m][co] * x[pix(m, tap)][ci]: C = A * B with A = dy^T (co x m),
-// B = im2col(x) (m x k).  Tile 64 co x 64 k per workgroup (4 waves, 32 x 32 each, 2 x 2
-// fragments of v_mfma_f32_16x16x4f32), K loop over 32-pixel chunks of the block's pixel
-// split.  Operand tiles go to LDS transposed ([row][m]) so one ds_read_b128 feeds 4 MFMAs:
-// lane l reads m = mm + 4*(l/16) + {0..3}; MFMA j consumes element j of both operands,
-// so the pairing of A and B over m is identical and the 4 MFMAs together cover 16 pixels.
-struct WgradP {
-  const float* dy;
-  const float* x;
-  float* ws;
-  int dys, cout;
-  int n, h, w, cs, ho, wo, ks, stride, pad, dil;
-  int K;                 // ks * ks * cs
-  int64_t M;
-  int64_t pix_per_split;
-};
-
-constexpr int kWT = 64;      // tile rows / cols
-constexpr int kWM = 32;      // pixels per chunk
-constexpr int kWLD = kWM + 4;
-
-// X6 (fp32x fine-tune): the same tiles and chunks, each 32-pixel chunk one K step of
-// v_mfma_f32_16x16x32_bf16 on the exact 3-way bf16 splits of both operands (common.h split3),
-// the six products above 2^-24 in conv_x6's order -- fp32-class accuracy at the bf16 MFMA rate
-// (2.5 PF / 6 = 417 TF against the 157 TF of the f32 MFMA).  Lane (fr, fq) takes pixels
-// 8 fq .. 8 fq + 7 of the chunk for its A row and its B column alike, so the pairing over m holds.
-template <bool X6>
-__global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(4))) wgrad_kernel(const WgradP p) {
-  __shared__ __attribute__((aligned(16))) float As[2][kWT][kWLD];
-  __shared__ __attribute__((aligned(16))) float Bs[2][kWT][kWLD];
-  const int t = threadIdx.x;
-  const int lane = t & 63;
-  const int wave = t >> 6;
-  const int wr = wave >> 1, wcn = wave & 1;
-  const int co0 = blockIdx.y * kWT;
-  const int kc0 = blockIdx.x * kWT;
-  const int64_t m_begin = static_cast<int64_t>(blockIdx.z) * p.pix_per_split;
-  int64_t m_end = m_begin + p.pix_per_split;
-  if (m_end > p.M) m_end = p.M;
-  // the transposed LDS writes As[8 lv + j][lm] hit bank (4 j + lm) % 32 whatever lv is (rows are
-  // 36 floats, 8 rows = 288 = 0 mod 32): with 8 pixels x 8 column groups per wave every write was
-  // 8-way conflicted; 32 pixels per 32-lane half (lm = t % 32) makes them conflict-free, at 64 B
-  // per pixel per load instruction pair instead of 256 B
-  const int lm = t & 31;      // pixel row of the chunk this thread loads
-  const int lv = t >> 5;      // 8-column group
-  const int hw = p.ho * p.wo;
-  // B column group: (tap, ci) fixed for the whole loop
-  const int kcol = kc0 + 8 * lv;
-  const int tap = kcol / p.cs;
-  const int ci = kcol - tap * p.cs;
-  const bool kval = kcol < p.K && tap < p.ks * p.ks;
-  const int kh = kval ? tap / p.ks : 0;
-  const int kw = kval ? tap - kh * p.ks : 0;
-  const int co = co0 + 8 * lv;
-
-  // The thread's pixel advances by kWM per chunk: (n, oh, ow) are stepped, not divided out of m
-  // every chunk (an int64 division per chunk and thread), and two register sets keep two chunks
-  // of global loads in flight (chunk c + 2 loads while chunk c computes and chunk c + 1 is staged).
-  int64_t m_cur = m_begin + lm;
-  int p_n = 0, p_oh = 0, p_ow = 0;
-  {
-    const int mi = static_cast<int>(m_cur < p.M ? m_cur : 0);   // M < 2^31 (wgrad_check rejects larger)
-    p_n = mi / hw;
-    const int q = mi - p_n * hw;
-    p_oh = q / p.wo;
-    p_ow = q - p_oh * p.wo;
-  }
-  auto load = [&](float (&ra)[8], float (&rb)[8]) {
-    const int64_t m = m_cur;
-    const int nn = p_n, oh = p_oh, ow = p_ow;
-    m_cur += kWM;
-    p_ow += kWM;
-    while (p_ow >= p.wo) {
-      p_ow -= p.wo;
-      if (++p_oh == p.ho) {
-        p_oh = 0;
-        ++p_n;
-      }
-    }
-#pragma unroll
-    for (int j = 0; j < 8; ++j) { ra[j] = 0.f; rb[j] = 0.f; }
-    if (m >= m_end) return;
-    const float* dr = p.dy + m * p.dys;
-    if (co + 8 <= p.dys && co + 8 <= p.cout) {
-      const float4 a0 = *reinterpret_cast<const float4*>(dr + co);
-      const float4 a1 = *reinterpret_cast<const float4*>(dr + co + 4);
-      ra[0] = a0.x; ra[1] = a0.y; ra[2] = a0.z; ra[3] = a0.w;
-      ra[4] = a1.x; ra[5] = a1.y; ra[6] = a1.z; ra[7] = a1.w;
-    } else {
-#pragma unroll
-      for (int j = 0; j < 8; ++j)
-        if (co + j < p.cout) ra[j] = dr[co + j];
-    }
-    if (kval) {
-      const int ih = oh * p.stride - p.pad + kh * p.dil;
-      const int iw = ow * p.stride - p.pad + kw * p.dil;
-      if (static_cast<unsigned>(ih) < static_cast<unsigned>(p.h) && static_cast<unsigned>(iw) < static_cast<unsigned>(p.w)) {
-        const float* xr = p.x + ((static_cast<int64_t>(nn) * p.h + ih) * p.w + iw) * p.cs + ci;
-        const float4 b0 = *reinterpret_cast<const float4*>(xr);
-        const float4 b1 = *reinterpret_cast<const float4*>(xr + 4);
-        rb[0] = b0.x; rb[1] = b0.y; rb[2] = b0.z; rb[3] = b0.w;
-        rb[4] = b1.x; rb[5] = b1.y; rb[6] = b1.z; rb[7] = b1.w;
-      }
-    }
-  };
-  auto store = [&](int buf, const float (&ra)[8], const float (&rb)[8]) {
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      As[buf][8 * lv + j][lm] = ra[j];
-      Bs[buf][8 * lv + j][lm] = rb[j];
-    }
-  };
-
-  f32x4 acc[2][2];
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-  const int fr = lane & 15;
-  const int fq = lane >> 4;
-  auto compute = [&](int buf) {
-    if constexpr (X6) {
-      // B splits first, then one A row block at a time (fewer live split registers: the kernel
-      // fits 128 VGPRs, four waves per SIMD, without spilling); same MFMA order per accumulator
-      bf16x8 b[2][3];
-#pragma unroll
-      for (int f = 0; f < 2; ++f) {
-        const float* br = &Bs[buf][wcn * 32 + f * 16 + fr][8 * fq];
-        split3(*reinterpret_cast<const float4*>(br), *reinterpret_cast<const float4*>(br + 4), b[f][0], b[f][1], b[f][2]);
-      }
-#pragma unroll
-      for (int fi = 0; fi < 2; ++fi) {
-        if (co0 + wr * 32 + fi * 16 >= p.cout) continue;   // rows past cout (16- and 32-channel layers)
-        bf16x8 a[3];
-        const float* ar = &As[buf][wr * 32 + fi * 16 + fr][8 * fq];
-        split3(*reinterpret_cast<const float4*>(ar), *reinterpret_cast<const float4*>(ar + 4), a[0], a[1], a[2]);
-#pragma unroll
-        for (int fj = 0; fj < 2; ++fj) {
-          f32x4& c = acc[fi][fj];
-          c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[2], b[fj][0], c, 0, 0, 0);
-          c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[1], b[fj][1], c, 0, 0, 0);
-          c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[0], b[fj][2], c, 0, 0, 0);
-          c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[1], b[fj][0], c, 0, 0, 0);
-          c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[0], b[fj][1], c, 0, 0, 0);
-          c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[0], b[fj][0], c, 0, 0, 0);
-        }
-      }
-    } else {
-#pragma unroll
-      for (int mm = 0; mm < kWM; mm += 16) {
-        float4 a4[2], b4[2];
-#pragma unroll
-        for (int f = 0; f < 2; ++f) {
-          a4[f] = *reinterpret_cast<const float4*>(&As[buf][wr * 32 + f * 16 + fr][mm + 4 * fq]);
-          b4[f] = *reinterpret_cast<const float4*>(&Bs[buf][wcn * 32 + f * 16 + fr][mm + 4 * fq]);
-        }
-#pragma unroll
-        for (int fi = 0; fi < 2; ++fi) {
-          if (co0 + wr * 32 + fi * 16 >= p.cout) continue;
-#pragma unroll
-          for (int fj = 0; fj < 2; ++fj) {
-            acc[fi][fj] = __builtin_amdgcn_mfma_f32_16x16x4f32(a4[fi].x, b4[fj].x, acc[fi][fj], 0, 0, 0);
-            acc[fi][fj] = __builtin_amdgcn_mfma_f32_16x16x4f32(a4[fi].y, b4[fj].y, acc[fi][fj], 0, 0, 0);
-            acc[fi][fj] = __builtin_amdgcn_mfma_f32_16x16x4f32(a4[fi].z, b4[fj].z, acc[fi][fj], 0, 0, 0);
-            acc[fi][fj] = __builtin_amdgcn_mfma_f32_16x16x4f32(a4[fi].w, b4[fj].w, acc[fi][fj], 0, 0, 0);
-          }
-        }
-      }
-    }
-  };
-
-  // chunk c computes from LDS buffer c & 1; set X holds chunk c + 1 (staged after the compute),
-  // set Y receives chunk c + 2 (its loads fly across the compute of c and the staging of c + 1)
-  float r0a[8], r0b[8], r1a[8], r1b[8];
-  load(r0a, r0b);
-  store(0, r0a, r0b);
-  load(r0a, r0b);                                   // chunk 1
-  __syncthreads();
-  for (int64_t mc = m_begin; mc < m_end; mc += 2 * kWM) {
-    load(r1a, r1b);                                 // chunk c + 2 (zeros past the end)
-    compute(0);
-    if (mc + kWM < m_end) store(1, r0a, r0b);
-    __syncthreads();
-    if (mc + kWM >= m_end) break;
-    load(r0a, r0b);                                 // chunk c + 3
-    compute(1);
-    if (mc + 2 * kWM < m_end) store(0, r1a, r1b);
-    __syncthreads();
-  }
-  // D[row = 4*(l/16) + r][col = l%16] of each 16x16 fragment; rows = co, cols = k
-  float* out = p.ws + static_cast<int64_t>(blockIdx.z) * p.cout * p.K;
-#pragma unroll
-  for (int fi = 0; fi < 2; ++fi)
-#pragma unroll
-    for (int fj = 0; fj < 2; ++fj) {
-      const int k = kc0 + wcn * 32 + fj * 16 + fr;
-      if (k >= p.K) continue;
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int c = co0 + wr * 32 + fi * 16 + 4 * fq + r;
-        if (c < p.cout) out[static_cast<int64_t>(c) * p.K + k] = acc[fi][fj][r];
-      }
-    }
-}
-
-// The fp32x weight gradient on a 128 co x 128 k tile (cout and K >= 128): four waves of 64 x 64
-// (4 x 4 fragments), so every staged byte feeds twice the MFMAs of the 64 x 64 tile.  Same chunks,
-// staging map (32 pixels per 32-lane half: conflict-free transposed writes), two register sets of
-// loads in flight, split order and MFMA order per accumulator as wgrad_kernel<true>; the split of a
-// B fragment is done once per chunk and reused by the wave's four row blocks.  Two workgroups per
-// CU (2 x 2 x 128 x 36 floats of LDS each).
-constexpr int kWT2 = 128;
-__global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(2))) wgrad_x6_big_kernel(const WgradP p) {
-  __shared__ __attribute__((aligned(16))) float As[2][kWT2][kWLD];
-  __shared__ __attribute__((aligned(16))) float Bs[2][kWT2][kWLD];
-  const int t = threadIdx.x;
-  const int lane = t & 63;
-  const int wave = t >> 6;
-  const int wr = wave >> 1, wcn = wave & 1;
-  const int co0 = blockIdx.y * kWT2;
-  const int kc0 = blockIdx.x * kWT2;
-  const int64_t m_begin = static_cast<int64_t>(blockIdx.z) * p.pix_per_split;
-  int64_t m_end = m_begin + p.pix_per_split;
-  if (m_end > p.M) m_end = p.M;
-  const int lm = t & 31;      // pixel row of the chunk this thread loads
-  const int lv = t >> 5;      // 16-column group
-  const int hw = p.ho * p.wo;
-  const int kcol = kc0 + 16 * lv;                  // 16 consecutive k stay in one tap (cs % 16 == 0)
-  const int tap = kcol / p.cs;
-  const int ci = kcol - tap * p.cs;
-  const bool kval = kcol < p.K && tap < p.ks * p.ks;
-  const int kh = kval ? tap / p.ks : 0;
-  const int kw = kval ? tap - kh * p.ks : 0;
-  const int co = co0 + 16 * lv;
-
-  int64_t m_cur = m_begin + lm;
-  int p_n = 0, p_oh = 0, p_ow = 0;
-  {
-    const int mi = static_cast<int>(m_cur < p.M ? m_cur : 0);
-    p_n = mi / hw;
-    const int q = mi - p_n * hw;
-    p_oh = q / p.wo;
-    p_ow = q - p_oh * p.wo;
-  }
-  auto load = [&](float4 (&ra)[4], float4 (&rb)[4]) {
-    const int64_t m = m_cur;
-    const int nn = p_n, oh = p_oh, ow = p_ow;
-    m_cur += kWM;
-    p_ow += kWM;
-    while (p_ow >= p.wo) {
-      p_ow -= p.wo;
-      if (++p_oh == p.ho) {
-        p_oh = 0;
-        ++p_n;
-      }
-    }
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      ra[j] = make_float4(0.f, 0.f, 0.f, 0.f);
-      rb[j] = make_float4(0.f, 0.f, 0.f, 0.f);
-    }
-    if (m >= m_end) return;
-    const float* dr = p.dy + m * p.dys;
-    if (co + 16 <= p.dys && co + 16 <= p.cout) {
-#pragma unroll
-      for (int j = 0; j < 4; ++j) ra[j] = *reinterpret_cast<const float4*>(dr + co + 4 * j);
-    } else {
-      float v[16];
-#pragma unroll
-      for (int j = 0; j < 16; ++j) v[j] = co + j < p.cout ? dr[co + j] : 0.f;
-#pragma unroll
-      for (int j = 0; j < 4; ++j) ra[j] = make_float4(v[4 * j], v[4 * j + 1], v[4 * j + 2], v[4 * j + 3]);
-    }
-    if (kval) {
-      const int ih = oh * p.stride - p.pad + kh * p.dil;
-      const int iw = ow * p.stride - p.pad + kw * p.dil;
-      if (static_cast<unsigned>(ih) < static_cast<unsigned>(p.h) && static_cast<unsigned>(iw) < static_cast<unsigned>(p.w)) {
-        const float* xr = p.x + ((static_cast<int64_t>(nn) * p.h + ih) * p.w + iw) * p.cs + ci;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) rb[j] = *reinterpret_cast<const float4*>(xr + 4 * j);
-      }
-    }
-  };
-  auto store = [&](int buf, const float4 (&ra)[4], const float4 (&rb)[4]) {
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const float av[4] = {ra[j].x, ra[j].y, ra[j].z, ra[j].w};
-      const float bv[4] = {rb[j].x, rb[j].y, rb[j].z, rb[j].w};
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        As[buf][16 * lv + 4 * j + e][lm] = av[e];
-        Bs[buf][16 * lv + 4 * j + e][lm] = bv[e];
-      }
-    }
-  };
-
-  f32x4 acc[4][4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-  const int fr = lane & 15;
-  const int fq = lane >> 4;
-  auto compute = [&](int buf) {
-    bf16x8 b[4][3];
-#pragma unroll
-    for (int f = 0; f < 4; ++f) {
-      const float* br = &Bs[buf][wcn * 64 + f * 16 + fr][8 * fq];
-      split3(*reinterpret_cast<const float4*>(br), *reinterpret_cast<const float4*>(br + 4), b[f][0], b[f][1], b[f][2]);
-    }
-#pragma unroll
-    for (int fi = 0; fi < 4; ++fi) {
-      bf16x8 a[3];
-      const float* ar = &As[buf][wr * 64 + fi * 16 + fr][8 * fq];
-      split3(*reinterpret_cast<const float4*>(ar), *reinterpret_cast<const float4*>(ar + 4), a[0], a[1], a[2]);
-#pragma unroll
-      for (int fj = 0; fj < 4; ++fj) {
-        f32x4& c = acc[fi][fj];
-        c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[2], b[fj][0], c, 0, 0, 0);
-        c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[1], b[fj][1], c, 0, 0, 0);
-        c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[0], b[fj][2], c, 0, 0, 0);
-        c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[1], b[fj][0], c, 0, 0, 0);
-        c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[0], b[fj][1], c, 0, 0, 0);
-        c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[0], b[fj][0], c, 0, 0, 0);
-      }
-    }
-  };
-
-  float4 r0a[4], r0b[4], r1a[4], r1b[4];
-  load(r0a, r0b);
-  store(0, r0a, r0b);
-  load(r0a, r0b);
-  __syncthreads();
-  for (int64_t mc = m_begin; mc < m_end; mc += 2 * kWM) {
-    load(r1a, r1b);
-    compute(0);
-    if (mc + kWM < m_end) store(1, r0a, r0b);
-    __syncthreads();
-    if (mc + kWM >= m_end) break;
-    load(r0a, r0b);
-    compute(1);
-    if (mc + 2 * kWM < m_end) store(0, r1a, r1b);
-    __syncthreads();
-  }
-  float* out = p.ws + static_cast<int64_t>(blockIdx.z) * p.cout * p.K;
-#pragma unroll
-  for (int fi = 0; fi < 4; ++fi)
-#pragma unroll
-    for (int fj = 0; fj < 4; ++fj) {
-      const int k = kc0 + wcn * 64 + fj * 16 + fr;
-      if (k >= p.K) continue;
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int c = co0 + wr * 64 + fi * 16 + 4 * fq + r;
-        if (c < p.cout) out[static_cast<int64_t>(c) * p.K + k] = acc[fi][fj][r];
-      }
-    }
-}
-
-// ---- fp32x weight gradient, dy pre-split -----------------------------------------------------
-// The 128 x 128 tile above splits every dy and x value in each of the two waves that read it
-// (~4.4 VALU instructions per MFMA: VALU-bound, MFMA busy 0.31, profiles/r5r_wgrad_pmc).  Here dy
-// is split once per launch into three transposed bf16 planes [plane][co][m] (one HBM pass,
-// wgrad_dy_split_kernel) that the tile stages with LDS-DMA like conv_x6's weight planes: the
-// kernel splits only x.  Same split3 (RNE) of the same values and the same MFMA order per
-// accumulator as wgrad_x6_big_kernel, so the partial sums are bit-identical to it.
-constexpr int kPreRows = kWT2;   // dyT rows padded to a multiple of the tile (zero rows)
-__device__ float4 g_wgrad_zero[4];   // zero-initialised: the B source outside the image
-
-// LDS byte address of a __shared__ object; one ds_read_b128 at LDS address base + OFF
-__device__ __forceinline__ uint32_t lds_addr(const void* p) {
-  return static_cast<uint32_t>(reinterpret_cast<uintptr_t>((const __attribute__((address_space(3))) void*)p));
-}
-template <int OFF, typename V>
-__device__ __forceinline__ void ds_rd(V& dst, uint32_t base) {
-  static_assert(sizeof(V) == 16 && OFF >= 0 && OFF < 65536, "ds_read_b128 offset");
-  asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(base), "i"(OFF));
-}
-// one 16-B-per-lane LDS-DMA (global_load_lds_dwordx4) to the wave-uniform LDS address `lds`
-// (M0 holds the LDS address; its previous value is restored, as M0 is reserved to the compiler)
-__device__ __forceinline__ void dma16(const void* src, uint32_t lds) {
-  uint32_t keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep) : "v"(src), "s"(lds) : "memory");
-}
-__device__ __forceinline__ int pre_swz_a(int row) { return ((row >> 3) & 1) * 3; }          // 64-B bf16 rows
-__device__ __forceinline__ int pre_swz_b(int row) { return ((row >> 1) & 1) | (row & 4); }  // 128-B fp32 rows
-// transposed B write of row RR (0..15) of a thread's 16-row group: w[k] holds the lane address for
-// swizzle value k -> (0, 1, 4, 5)
-template <int RR>
-__device__ __forceinline__ void pre_wr(const uint32_t (&w)[4], float v) {
-  constexpr int k = ((RR >> 1) & 1) | (((RR >> 2) & 1) << 1);
-  asm volatile("ds_write_b32 %0, %1 offset:%2" :: "v"(w[k]), "v"(v), "i"(RR * 128) : "memory");
-}
-
-__global__ void __launch_bounds__(kThreads)
-wgrad_dy_split_kernel(const float* __restrict__ dy, int dys, int cout, int64_t M, int64_t Mp, int Cp,
-                      bf16_t* __restrict__ out) {
-  // thread: channel co = 64-channel block + t / 4, pixels 8 (t % 4) .. +7 of a 32-pixel group:
-  // four lanes write one channel's 64-B row piece per plane; each read instruction is 16
-  // consecutive channels (64 B) of 4 pixels
-  const int t = threadIdx.x;
-  const int64_t ngroups = Mp / 32;
-  const int cblocks = Cp / 64;
-  const int64_t total = ngroups * cblocks;
-  const int64_t pstride = static_cast<int64_t>(Cp) * Mp;
-  for (int64_t b = blockIdx.x; b < total; b += gridDim.x) {
-    const int cb = static_cast<int>(b % cblocks);
-    const int64_t g = b / cblocks;
-    const int co = cb * 64 + (t >> 2);
-    const int64_t m0 = g * 32 + 8 * (t & 3);
-    float v[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j)
-      v[j] = (co < cout && m0 + j < M) ? dy[(m0 + j) * dys + co] : 0.f;
-    bf16x8 h1, h2, h3;
-    split3(make_float4(v[0], v[1], v[2], v[3]), make_float4(v[4], v[5], v[6], v[7]), h1, h2, h3);
-    bf16_t* o = out + static_cast<int64_t>(co) * Mp + m0;
-    *reinterpret_cast<bf16x8*>(o) = h1;
-    *reinterpret_cast<bf16x8*>(o + pstride) = h2;
-    *reinterpret_cast<bf16x8*>(o + 2 * pstride) = h3;
-  }
-}
-
-struct WgradPreP {
-  WgradP p;
-  const bf16_t* dyt;   // [3][Cp][Mp]
-  int64_t Mp;
-  int Cp;
-};
-
-__global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(2))) wgrad_x6_pre_kernel(const WgradPreP q) {
-  const WgradP& p = q.p;
-  // A: [buf][plane][128 rows][64 B] bf16 (16-B chunks swizzled), B: [buf][128 rows][32 floats]
-  // (16-B chunks swizzled): 2 x (24 + 16) KB, two workgroups per CU
-  __shared__ __attribute__((aligned(16))) char Ab[2][3 * kWT2 * 64];
-  __shared__ __attribute__((aligned(16))) float Bs[2][kWT2 * 32];
-  const int t = threadIdx.x;
-  const int lane = t & 63;
-  const int wave = t >> 6;
-  const int wr = wave >> 1, wcn = wave & 1;
-  const int co0 = blockIdx.y * kWT2;
-  const int kc0 = blockIdx.x * kWT2;
-  const int64_t m_begin = static_cast<int64_t>(blockIdx.z) * p.pix_per_split;
-  int64_t m_end = m_begin + p.pix_per_split;
-  if (m_end > p.M) m_end = p.M;
-  const int lm = t & 31;
-  const int lv = t >> 5;
-  const int hw = p.ho * p.wo;
-  const int kcol = kc0 + 16 * lv;
-  const int tap = kcol / p.cs;
-  const int ci = kcol - tap * p.cs;
-  const bool kval = kcol < p.K && tap < p.ks * p.ks;
-  const int kh = kval ? tap / p.ks : 0;
-  const int kw = kval ? tap - kh * p.ks : 0;
-
-  // A DMA: 24 pieces of 1 KB per chunk, 6 per wave; piece gi = plane * 8 + 16-row block.  Sources
-  // as element offsets from the block's first row (< 2^31: 3 x 128 rows x Mp), not 64-bit pointers
-  // (six of those spilled to scratch, and the reload waited on every load in flight)
-  const int64_t plane_stride = static_cast<int64_t>(q.Cp) * q.Mp;
-  const bf16_t* a_base = q.dyt + static_cast<int64_t>(co0) * q.Mp;
-  int32_t a_off[6];
-#pragma unroll
-  for (int i = 0; i < 6; ++i) {
-    const int gi = wave * 6 + i;
-    const int pl = gi >> 3;
-    const int r = (gi & 7) * 16 + (lane >> 2);
-    const int c = (lane & 3) ^ pre_swz_a(r);
-    a_off[i] = static_cast<int32_t>(pl * plane_stride + static_cast<int64_t>(r) * q.Mp + 8 * c);
-  }
-  // as inline asm: hipcc models the LDS-DMA builtin's address registers as pending until vmcnt(0)
-  // and drained the B loads in flight the first time it reused one
-  const uint32_t a_dst = static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(static_cast<int>(lds_addr(&Ab[0][wave * 6 * 1024]))));
-  auto dma_a = [&](int buf, int64_t m) {
-    const bf16_t* src = a_base + m;
-#pragma unroll
-    for (int i = 0; i < 6; ++i) dma16(src + a_off[i], a_dst + buf * static_cast<uint32_t>(sizeof(Ab[0])) + i * 1024);
-  };
-
-  int64_t m_cur = m_begin + lm;
-  int p_n = 0, p_oh = 0, p_ow = 0;
-  {
-    const int mi = static_cast<int>(m_cur < p.M ? m_cur : 0);
-    p_n = mi / hw;
-    const int qq = mi - p_n * hw;
-    p_oh = qq / p.wo;
-    p_ow = qq - p_oh * p.wo;
-  }
-  // exactly four 16-B loads per call (the zero page outside the image / past the split), so that
-  // the chunk-end wait below can leave them in flight with a fixed vmcnt
-  auto load = [&](float4 (&rb)[4]) {
-    const int64_t m = m_cur;
-    const int nn = p_n, oh = p_oh, ow = p_ow;
-    m_cur += kWM;
-    p_ow += kWM;
-    while (p_ow >= p.wo) {
-      p_ow -= p.wo;
-      if (++p_oh == p.ho) {
-        p_oh = 0;
-        ++p_n;
-      }
-    }
-    const float* xr = reinterpret_cast<const float*>(g_wgrad_zero);
-    const int ih = oh * p.stride - p.pad + kh * p.dil;
-    const int iw = ow * p.stride - p.pad + kw * p.dil;
-    if (m < m_end && kval && static_cast<unsigned>(ih) < static_cast<unsigned>(p.h) &&
-        static_cast<unsigned>(iw) < static_cast<unsigned>(p.w))
-      xr = p.x + ((static_cast<int64_t>(nn) * p.h + ih) * p.w + iw) * p.cs + ci;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) rb[j] = *reinterpret_cast<const float4*>(xr + 4 * j);
-  };
-  // transposed B writes as inline asm as well (a C++ LDS store made hipcc wait vmcnt(0) for the
-  // DMA in flight); row 16 lv + 4 j + e: its swizzle depends on 4 j + e only
-  const uint32_t bs_w = lds_addr(&Bs[0][0]) + static_cast<uint32_t>(16 * lv * 128 + 4 * (lm & 3));
-  auto store = [&](int buf, const float4 (&rb)[4]) {
-    const uint32_t base = bs_w + buf * static_cast<uint32_t>(sizeof(Bs[0]));
-    // one lane address per swizzle value (0, 1, 4, 5); the row is the instruction's offset
-    const uint32_t w[4] = {base + 16u * ((lm >> 2) ^ 0), base + 16u * ((lm >> 2) ^ 1), base + 16u * ((lm >> 2) ^ 4),
-                           base + 16u * ((lm >> 2) ^ 5)};
-    pre_wr<0>(w, rb[0].x); pre_wr<1>(w, rb[0].y); pre_wr<2>(w, rb[0].z); pre_wr<3>(w, rb[0].w);
-    pre_wr<4>(w, rb[1].x); pre_wr<5>(w, rb[1].y); pre_wr<6>(w, rb[1].z); pre_wr<7>(w, rb[1].w);
-    pre_wr<8>(w, rb[2].x); pre_wr<9>(w, rb[2].y); pre_wr<10>(w, rb[2].z); pre_wr<11>(w, rb[2].w);
-    pre_wr<12>(w, rb[3].x); pre_wr<13>(w, rb[3].y); pre_wr<14>(w, rb[3].z); pre_wr<15>(w, rb[3].w);
-  };
-
-  f32x4 acc[4][4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-  const int fr = lane & 15;
-  const int fq = lane >> 4;
-  // Fragment reads as inline-asm ds_read_b128 with hand-counted lgkmcnt waits: hipcc cannot tell
-  // that the LDS-DMA in flight targets the other buffer, and put a vmcnt(0) before the first C++
-  // read of the chunk (draining the B loads issued for two chunks ahead).  The swizzles depend on
-  // row bits the fragment offsets (16 rows apart) do not change, so one lane address per operand.
-  const uint32_t ab_lds = lds_addr(&Ab[0][0]), bs_lds = lds_addr(&Bs[0][0]);
-  uint32_t b_lane[2], a_lane;
-  {
-    const int rb = wcn * 64 + fr;
-    b_lane[0] = bs_lds + static_cast<uint32_t>(rb * 128 + 16 * ((2 * fq) ^ pre_swz_b(rb)));
-    b_lane[1] = bs_lds + static_cast<uint32_t>(rb * 128 + 16 * ((2 * fq + 1) ^ pre_swz_b(rb)));
-    const int ra = wr * 64 + fr;
-    a_lane = ab_lds + static_cast<uint32_t>(ra * 64 + 16 * (fq ^ pre_swz_a(ra)));
-  }
-  static_assert(sizeof(Bs[0]) == kWT2 * 128 && sizeof(Ab[0]) == 3 * kWT2 * 64, "LDS buffer strides");
-  auto compute = [&](int buf) {
-    const uint32_t vb0 = b_lane[0] + buf * static_cast<uint32_t>(sizeof(Bs[0]));
-    const uint32_t vb1 = b_lane[1] + buf * static_cast<uint32_t>(sizeof(Bs[0]));
-    const uint32_t va = a_lane + buf * static_cast<uint32_t>(sizeof(Ab[0]));
-    float4 blo[4], bhi[4];
-    ds_rd<0>(blo[0], vb0); ds_rd<0>(bhi[0], vb1);
-    ds_rd<2048>(blo[1], vb0); ds_rd<2048>(bhi[1], vb1);
-    ds_rd<4096>(blo[2], vb0); ds_rd<4096>(bhi[2], vb1);
-    ds_rd<6144>(blo[3], vb0); ds_rd<6144>(bhi[3], vb1);
-    bf16x8 a[3];
-    ds_rd<0>(a[0], va); ds_rd<kWT2 * 64>(a[1], va); ds_rd<2 * kWT2 * 64>(a[2], va);
-    // the reads are asm: their results are valid only after the counted wait, and a
-    // sched_barrier after each wait keeps the scheduler from hoisting their uses above it
-    asm volatile("s_waitcnt lgkmcnt(3)" ::: "memory");
-    __builtin_amdgcn_sched_barrier(0);
-    bf16x8 b[4][3];
-#pragma unroll
-    for (int f = 0; f < 4; ++f) split3(blo[f], bhi[f], b[f][0], b[f][1], b[f][2]);
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-    for (int fi = 0; fi < 4; ++fi) {
-      bf16x8 an[3];
-      // the next fragment's three planes (rows 16 apart: +1 KB), read under this one's MFMAs
-      switch (fi) {
-        case 0: ds_rd<1024>(an[0], va); ds_rd<1024 + kWT2 * 64>(an[1], va); ds_rd<1024 + 2 * kWT2 * 64>(an[2], va); break;
-        case 1: ds_rd<2048>(an[0], va); ds_rd<2048 + kWT2 * 64>(an[1], va); ds_rd<2048 + 2 * kWT2 * 64>(an[2], va); break;
-        case 2: ds_rd<3072>(an[0], va); ds_rd<3072 + kWT2 * 64>(an[1], va); ds_rd<3072 + 2 * kWT2 * 64>(an[2], va); break;
-        default: break;
-      }
-#pragma unroll
-      for (int fj = 0; fj < 4; ++fj) {
-        f32x4& c = acc[fi][fj];
-        c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[2], b[fj][0], c, 0, 0, 0);
-        c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[1], b[fj][1], c, 0, 0, 0);
-        c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[0], b[fj][2], c, 0, 0, 0);
-        c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[1], b[fj][0], c, 0, 0, 0);
-        c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[0], b[fj][1], c, 0, 0, 0);
-        c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[0], b[fj][0], c, 0, 0, 0);
-      }
-      if (fi < 3) {
-        __builtin_amdgcn_sched_barrier(0);
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_sched_barrier(0);
-        a[0] = an[0];
-        a[1] = an[1];
-        a[2] = an[2];
-      }
-    }
-  };
-
-  // Chunk c computes from buffers c & 1.  At the start of its phase the B registers of chunk c + 1
-  // (loaded during the previous phase) are written to the other buffer, chunk c + 1's A DMA goes to
-  // it as well, then chunk c + 2's B loads are issued into the same registers -- so hipcc's wait for
-  // those registers (it cannot count LDS-DMA and waits vmcnt(0)) drains nothing else.  The phase
-  // ends with vmcnt(4) (the DMA landed, the four B loads stay in flight across the barrier) +
-  // lgkmcnt(0) + s_barrier.  Compiler barriers keep the DMA ahead of the B loads in issue order.
-  float4 rb[4];
-  dma_a(0, m_begin);
-  load(rb);                                        // chunk 0
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  store(0, rb);
-  asm volatile("" ::: "memory");
-  __builtin_amdgcn_sched_barrier(0);
-  load(rb);                                        // chunk 1
-  __builtin_amdgcn_sched_barrier(0);
-  asm volatile("s_waitcnt vmcnt(4) lgkmcnt(0)\n\ts_barrier" ::: "memory");
-  int cur = 0;
-  for (int64_t mc = m_begin; mc < m_end; mc += kWM, cur ^= 1) {
-    store(cur ^ 1, rb);                            // chunk c + 1 (zeros past the split, never read)
-    if (mc + kWM < m_end) dma_a(cur ^ 1, mc + kWM);
-    asm volatile("" ::: "memory");
-    __builtin_amdgcn_sched_barrier(0);
-    load(rb);                                      // chunk c + 2 (the zero page past the split)
-    __builtin_amdgcn_sched_barrier(0);
-    compute(cur);
-    asm volatile("s_waitcnt vmcnt(4) lgkmcnt(0)\n\ts_barrier" ::: "memory");
-  }
-  float* out = p.ws + static_cast<int64_t>(blockIdx.z) * p.cout * p.K;
-#pragma unroll
-  for (int fi = 0; fi < 4; ++fi)
-#pragma unroll
-    for (int fj = 0; fj < 4; ++fj) {
-      const int k = kc0 + wcn * 64 + fj * 16 + fr;
-      if (k >= p.K) continue;
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int c = co0 + wr * 64 + fi * 16 + 4 * fq + r;
-        if (c < p.cout) out[static_cast<int64_t>(c) * p.K + k] = acc[fi][fj][r];
-      }
-    }
-}
-
-// ---- fp32x weight gradient of the small-cout convs (cout <= 32: stem, layer1, layer2) ----------
-// The 64 x 64 tile left 3/4 of its rows idle at cout 16, and the stem's 8-channel input stride left
-// 5/8 of its k columns zero (cin 3): 474 us for 20 GFLOP of the fine-tune step.  Here the MFMA
-// operands come straight from global memory into registers -- no LDS, no barriers: lane (fr, fq)
-// loads dy[m][16 fm + fr] and x[pix(m, tap)][ci] of its 8 pixels m = m0 + 8 fq + j, as the
-// 16x16x32 bf16 A / B layouts ask -- and the k columns are the dense (tap, ci < cin) pairs only
-// (147 at the stem instead of 392).  Each wave owns FN 16-column fragments and a contiguous range of
-// 32-pixel chunks (one output row segment each: wo % 32 == 0) and writes its own partial sums,
-// reduced in split order by wgrad_reduce*_kernel; same split3 and six-product order per
-// accumulator as wgrad_kernel<true>.
-constexpr int kDirFN = 4;
-static bool wgrad_direct_ok(const drnmi_wgrad_args& a) {
-  return a.cout <= 32 && a.wo % 32 == 0 && a.ks * a.ks * a.cin <= 4096;
-}
-static int wgrad_direct_tiles(const drnmi_wgrad_args& a) {
-  return (a.ks * a.ks * a.cin + 16 * kDirFN - 1) / (16 * kDirFN);
-}
-// wave splits: ~2048 waves in all (8 per CU), whole workgroups of 4, <= one chunk per wave
-static int wgrad_direct_splits(const drnmi_wgrad_args& a) {
-  const int64_t chunks = static_cast<int64_t>(a.n) * a.ho * a.wo / 32;
-  int64_t s = 2048 / wgrad_direct_tiles(a);
-  if (s > chunks) s = chunks;
-  s = (s + 3) / 4 * 4;
-  return static_cast<int>(s < 4 ? 4 : s);
-}
-
-template <int FM>
-__global__ void __launch_bounds__(kThreads) wgrad_x6_direct_kernel(const WgradP p, int cin) {
-  const int lane = threadIdx.x & 63;
-  const int z = blockIdx.y * 4 + (threadIdx.x >> 6);        // this wave's split
-  const int nz = gridDim.y * 4;
-  const int fr = lane & 15, fq = lane >> 4;
-  const int hw = p.ho * p.wo;
-  const int chunks = static_cast<int>(p.M / 32);
-  const int c_begin = static_cast<int>(static_cast<int64_t>(chunks) * z / nz);
-  const int c_end = static_cast<int>(static_cast<int64_t>(chunks) * (z + 1) / nz);
-  const int kdense = p.ks * p.ks * cin;
-  // the lane's B column of each fragment: dense column kv -> (tap, ci) -> tap offsets
-  int b_dh[kDirFN], b_dw[kDirFN], b_ci[kDirFN];
-  bool b_ok[kDirFN];
-#pragma unroll
-  for (int f = 0; f < kDirFN; ++f) {
-    const int kv = (blockIdx.x * kDirFN + f) * 16 + fr;
-    b_ok[f] = kv < kdense;
-    const int tap = b_ok[f] ? kv / cin : 0;
-    b_ci[f] = b_ok[f] ? kv - tap * cin : 0;
-    const int kh = tap / p.ks;
-    b_dh[f] = kh * p.dil - p.pad;
-    b_dw[f] = (tap - kh * p.ks) * p.dil - p.pad;
-  }
-  f32x4 acc[FM][kDirFN];
-#pragma unroll
-  for (int i = 0; i < FM; ++i)
-#pragma unroll
-    for (int j = 0; j < kDirFN; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-  for (int c = c_begin; c < c_end; ++c) {
-    const int m0 = c * 32;
-    const int n = m0 / hw;
-    const int q = m0 - n * hw;
-    const int oh = q / p.wo;
-    const int ow = q - oh * p.wo + 8 * fq;                 // the lane's first pixel (same row)
-    const int64_t mrow = static_cast<int64_t>(m0 + 8 * fq) * p.dys;
-    float av[FM][8], bv[kDirFN][8];
-#pragma unroll
-    for (int fm = 0; fm < FM; ++fm) {
-      const int co = 16 * fm + fr;
-#pragma unroll
-      for (int j = 0; j < 8; ++j) av[fm][j] = co < p.cout ? p.dy[mrow + static_cast<int64_t>(j) * p.dys + co] : 0.f;
-    }
-#pragma unroll
-    for (int f = 0; f < kDirFN; ++f) {
-      const int ih = oh * p.stride + b_dh[f];
-      const bool row_ok = b_ok[f] && static_cast<unsigned>(ih) < static_cast<unsigned>(p.h);
-      const float* xr = p.x + (static_cast<int64_t>(n) * p.h + (row_ok ? ih : 0)) * p.w * p.cs + b_ci[f];
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const int iw = (ow + j) * p.stride + b_dw[f];
-        bv[f][j] = row_ok && static_cast<unsigned>(iw) < static_cast<unsigned>(p.w) ? xr[static_cast<int64_t>(iw) * p.cs] : 0.f;
-      }
-    }
-    bf16x8 b[kDirFN][3];
-#pragma unroll
-    for (int f = 0; f < kDirFN; ++f)
-      split3(make_float4(bv[f][0], bv[f][1], bv[f][2], bv[f][3]), make_float4(bv[f][4], bv[f][5], bv[f][6], bv[f][7]),
-             b[f][0], b[f][1], b[f][2]);
-#pragma unroll
-    for (int fm = 0; fm < FM; ++fm) {
-      bf16x8 a[3];
-      split3(make_float4(av[fm][0], av[fm][1], av[fm][2], av[fm][3]),
-             make_float4(av[fm][4], av[fm][5], av[fm][6], av[fm][7]), a[0], a[1], a[2]);
-#pragma unroll
-      for (int f = 0; f < kDirFN; ++f) {
-        f32x4& cc = acc[fm][f];
-        cc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[2], b[f][0], cc, 0, 0, 0);
-        cc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[1], b[f][1], cc, 0, 0, 0);
-        cc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[0], b[f][2], cc, 0, 0, 0);
-        cc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[1], b[f][0], cc, 0, 0, 0);
-        cc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[0], b[f][1], cc, 0, 0, 0);
-        cc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[0], b[f][0], cc, 0, 0, 0);
-      }
-    }
-  }
-  // C[row = 16 fm + 4 fq + r][col = 16 f + fr] -> ws[z][co][tap * cs + ci] (the reduce skips ci >= cin)
-  float* out = p.ws + static_cast<int64_t>(z) * p.cout * p.K;
-#pragma unroll
-  for (int f = 0; f < kDirFN; ++f) {
-    if (!b_ok[f]) continue;
-    const int kv = (blockIdx.x * kDirFN + f) * 16 + fr;
-    const int tap = kv / cin;
-    const int k = tap * p.cs + (kv - tap * cin);
-#pragma unroll
-    for (int fm = 0; fm < FM; ++fm)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int co = 16 * fm + 4 * fq + r;
-        if (co < p.cout) out[static_cast<int64_t>(co) * p.K + k] = acc[fm][f][r];
-      }
-  }
-}
-
-// dw[co][ci][kh][kw] (+)= sum_z ws[z][co][(kh*ks + kw)*cs + ci]
-__global__ void __launch_bounds__(kThreads)
-wgrad_reduce_kernel(const float* __restrict__ ws, int splits, int cout, int cin, int cs, int ks, int K,
-                    float* __restrict__ dw, int acc) {
-  // threads walk the partials' own [co][k] order (k = tap * cs + ci), so each of the `splits`
-  // reads is coalesced (walking dw's OIHW order read them ks*ks*... apart); dw is written once
-  const int64_t total = static_cast<int64_t>(cout) * K;
-  for (int64_t i = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x; i < total;
-       i += static_cast<int64_t>(gridDim.x) * blockDim.x) {
-    const int co = static_cast<int>(i / K);
-    const int k = static_cast<int>(i - static_cast<int64_t>(co) * K);
-    const int tap = k / cs;
-    const int ci = k - tap * cs;
-    if (ci >= cin) continue;
-    // eight splits' loads in flight at a time, summed in split order (one load per add serialised
-    // the chain on its latency)
-    float s = 0.f;
-    const int64_t zs = static_cast<int64_t>(cout) * K;
-    int z = 0;
-    for (; z + 8 <= splits; z += 8) {
-      float a[8];
-#pragma unroll
-      for (int u = 0; u < 8; ++u) a[u] = ws[(z + u) * zs + i];
-#pragma unroll
-      for (int u = 0; u < 8; ++u) s += a[u];
-    }
-    for (; z < splits; ++z) s += ws[z * zs + i];
-    const int64_t o = (static_cast<int64_t>(co) * cin + ci) * ks * ks + tap;   // tap = kh * ks + kw
-    dw[o] = acc ? dw[o] + s : s;
-  }
-}
-
-// Few outputs over many splits (the stem's 16 x 392 partials over 432 splits): one thread per
-// output walked its splits as a chain of dependent loads on 18 workgroups (125 us).  Here 8
-// threads share an output, each sums a contiguous eighth of the splits (8 loads in flight), and
-// the eighths are added in order: a fixed order, so dw stays bit-reproducible.
-constexpr int kRedOut = 32;
-constexpr int kRedGrp = kThreads / kRedOut;
-
-__global__ void __launch_bounds__(kThreads)
-wgrad_reduce_grouped_kernel(const float* __restrict__ ws, int splits, int cout, int cin, int cs, int ks, int K,
-                            float* __restrict__ dw, int acc) {
-  __shared__ float part[kRedGrp][kRedOut];
-  const int t = threadIdx.x;
-  const int oi = t % kRedOut, g = t / kRedOut;
-  const int64_t total = static_cast<int64_t>(cout) * K;
-  const int64_t i = static_cast<int64_t>(blockIdx.x) * kRedOut + oi;
-  const int z0 = static_cast<int>(static_cast<int64_t>(splits) * g / kRedGrp);
-  const int z1 = static_cast<int>(static_cast<int64_t>(splits) * (g + 1) / kRedGrp);
-  float s = 0.f;
-  if (i < total) {
-    const float* p = ws + i;
-#pragma unroll 8
-    for (int z = z0; z < z1; ++z) s += p[static_cast<int64_t>(z) * total];
-  }
-  part[g][oi] = s;
-  __syncthreads();
-  if (g != 0 || i >= total) return;
-  const int co = static_cast<int>(i / K);
-  const int k = static_cast<int>(i - static_cast<int64_t>(co) * K);
-  const int tap = k / cs;
-  const int ci = k - tap * cs;
-  if (ci >= cin) return;
-  float v = part[0][oi];
-#pragma unroll
-  for (int j = 1; j < kRedGrp; ++j) v += part[j][oi];
-  const int64_t o = (static_cast<int64_t>(co) * cin + ci) * ks * ks + tap;
-  dw[o] = acc ? dw[o] + v : v;
-}
-
-// The pixel range is split so that the launch fills the chip: at least two rounds of the resident
-// workgroup slots, and among lo .. 4 lo splits the count whose last round is fullest (the first
-// rule alone put D-54 layer7.0's 576 big tiles on 512 slots at one split: 1.125 rounds, the
-// second round 1/8 full, 4.6 ms of a 52.8 ms fine-tune step).  Every split holds >= 512 pixels.
-static bool wgrad_big_ok(const drnmi_wgrad_args& a) {
-  const int K = a.ks * a.ks * a.cin_stride;
-  return a.cout >= kWT2 && K >= kWT2 && a.cin_stride % 16 == 0;
-}
-
-static void wgrad_plan(const drnmi_wgrad_args& a, bool big, int* splits, int64_t* per) {
-  const int K = a.ks * a.ks * a.cin_stride;
-  const int tile = big ? kWT2 : kWT;
-  static int cus = 0;
-  if (cus == 0) {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess ||
-        hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0)
-      cus = 256;
-  }
-  const int64_t slots = (big ? 2 : 4) * static_cast<int64_t>(cus);   // resident workgroups: LDS 73.7 / 36.9 KB
-  const int64_t M = static_cast<int64_t>(a.n) * a.ho * a.wo;
-  const int64_t tiles = static_cast<int64_t>((a.cout + tile - 1) / tile) * ((K + tile - 1) / tile);
-  int64_t smax = (M + 511) / 512;
-  if (smax > 512) smax = 512;
-  if (smax < 1) smax = 1;
-  int64_t lo = (2 * slots + tiles - 1) / tiles;
-  if (lo > smax) lo = smax;
-  int64_t hi = 4 * lo < smax ? 4 * lo : smax;
-  int64_t best_s = 0, best_pp = 0;
-  double best_eff = -1.0;
-  for (int64_t s = lo; s <= hi; ++s) {
-    int64_t pp = (M + s - 1) / s;
-    pp = (pp + kWM - 1) / kWM * kWM;
-    const int64_t sa = (M + pp - 1) / pp;
-    const int64_t wgs = tiles * sa;
-    const int64_t rounds = (wgs + slots - 1) / slots;
-    const double eff = static_cast<double>(wgs) / static_cast<double>(rounds * slots);
-    if (eff > best_eff + 0.02) {     // a larger split count only for a clearly fuller last round
-      best_eff = eff;
-      best_s = sa;
-      best_pp = pp;
-    }
-  }
-  *splits = static_cast<int>(best_s);
-  *per = best_pp;
 }
 
 // ------------------------------------------------------------------ stride-2 dgrad parity classes
@@ -2065,171 +1181,6 @@ extern "C" int drnmi_channel_sum_f32(const float* x, int64_t rows, int32_t C, in
   return static_cast<int>(hipGetLastError());
 }
 
-static int wgrad_check(const drnmi_wgrad_args* a) {
-  if (a == nullptr) return DRNMI_EINVAL;
-  if (a->n <= 0 || a->h <= 0 || a->w <= 0 || a->ho <= 0 || a->wo <= 0 || a->cout <= 0 || a->cin <= 0) return DRNMI_EINVAL;
-  if (a->cin_stride < 8 || (a->cin_stride & (a->cin_stride - 1)) != 0 || a->cin > a->cin_stride) return DRNMI_EINVAL;
-  if (a->dy_stride < a->cout || a->ks <= 0 || a->stride <= 0 || a->dil <= 0 || a->pad < 0) return DRNMI_EINVAL;
-  if (a->ho != (a->h + 2 * a->pad - a->dil * (a->ks - 1) - 1) / a->stride + 1 ||
-      a->wo != (a->w + 2 * a->pad - a->dil * (a->ks - 1) - 1) / a->stride + 1)
-    return DRNMI_EINVAL;
-  // pixel indices are int32 inside the tiles (wgrad_kernel / wgrad_x6_*: m_cur, m / hw)
-  if (static_cast<int64_t>(a->n) * a->ho * a->wo >= (int64_t(1) << 31)) return DRNMI_EINVAL;
-  return DRNMI_OK;
-}
-
-// the partials [splits][cout][K] fp32, then (fp32x, 128-tile geometries) the dy planes [3][Cp][Mp]
-static int64_t wgrad_partials_bytes(const drnmi_wgrad_args& a, int splits) {
-  return (static_cast<int64_t>(splits) * a.cout * a.ks * a.ks * a.cin_stride * 4 + 255) / 256 * 256;
-}
-// the dy split pass costs ~10 B of HBM per dy element against 2 K flops per element of the tile:
-// it pays where K >= 1024 (layer7.0: 3.78 -> 2.72 ms; a 1x1 256 -> 1024 wgrad: 128 -> 234 us)
-static bool wgrad_pre_ok(const drnmi_wgrad_args& a) {
-  return wgrad_big_ok(a) && a.ks * a.ks * a.cin_stride >= 1024;
-}
-static int64_t wgrad_pre_bytes(const drnmi_wgrad_args& a) {
-  if (!wgrad_pre_ok(a)) return 0;
-  const int64_t M = static_cast<int64_t>(a.n) * a.ho * a.wo;
-  const int64_t Mp = (M + kWM - 1) / kWM * kWM;
-  const int64_t Cp = (a.cout + kPreRows - 1) / kPreRows * kPreRows;
-  return 3 * Cp * Mp * 2;
-}
-
-// the exact-f32 kernel's own partials (the f32x3 query below also holds the split-bf16 plan and
-// its dy planes)
-extern "C" int64_t drnmi_conv_wgrad_f32_workspace_bytes(const drnmi_wgrad_args* a) {
-  if (wgrad_check(a) != DRNMI_OK) return -1;
-  int splits;
-  int64_t per;
-  wgrad_plan(*a, false, &splits, &per);
-  return wgrad_partials_bytes(*a, splits);
-}
-
-extern "C" int64_t drnmi_conv_wgrad_workspace_bytes(const drnmi_wgrad_args* a) {
-  if (wgrad_check(a) != DRNMI_OK) return -1;
-  // room for either kernel (f32 or f32x3): enough for both plans
-  int splits;
-  int64_t per;
-  wgrad_plan(*a, false, &splits, &per);
-  int64_t pre = 0;
-  if (wgrad_big_ok(*a)) {
-    int s2;
-    wgrad_plan(*a, true, &s2, &per);
-    if (s2 > splits) splits = s2;
-    pre = wgrad_pre_bytes(*a);
-  }
-  if (wgrad_direct_ok(*a) && wgrad_direct_splits(*a) > splits) splits = wgrad_direct_splits(*a);
-  return wgrad_partials_bytes(*a, splits) + pre;
-}
-
-// The one launch decision of a weight gradient: wgrad_launch runs it and drnmi_conv_wgrad_plan
-// reports it.  kernel: DRNMI_WGRAD_* (include/drnmi.h); full_splits: the split count whose
-// partials precede the dy planes of the pre kernel in the workspace.
-struct WgradRoute {
-  int kernel;
-  int splits;
-  int64_t per;
-  int reduce;        // 0 wgrad_reduce_kernel, 1 wgrad_reduce_grouped_kernel
-  int full_splits;
-};
-static WgradRoute wgrad_route(const drnmi_wgrad_args& a, bool x6) {
-  WgradRoute r{};
-  const bool big = x6 && wgrad_big_ok(a);
-  wgrad_plan(a, big, &r.splits, &r.per);
-  if (x6 && !big && wgrad_direct_ok(a)) {
-    r.kernel = DRNMI_WGRAD_DIRECT;
-    r.splits = wgrad_direct_splits(a);
-  } else if (big && wgrad_pre_ok(a)) {
-    r.kernel = DRNMI_WGRAD_PRE;
-    int64_t per;
-    wgrad_plan(a, false, &r.full_splits, &per);
-    int s2;
-    wgrad_plan(a, true, &s2, &per);
-    if (s2 > r.full_splits) r.full_splits = s2;
-  } else if (big) {
-    r.kernel = DRNMI_WGRAD_BIG;
-  } else {
-    r.kernel = x6 ? DRNMI_WGRAD_X6 : DRNMI_WGRAD_F32;
-  }
-  const int64_t total = static_cast<int64_t>(a.cout) * a.ks * a.ks * a.cin_stride;
-  // the grouped form where one thread per output would leave the chip mostly idle on a long chain
-  r.reduce = (r.splits >= 4 * kRedGrp && total <= 2048 * kThreads) ? 1 : 0;
-  return r;
-}
-
-extern "C" int drnmi_conv_wgrad_plan(const drnmi_wgrad_args* a, int32_t x6, int32_t* kernel, int32_t* splits,
-                                     int64_t* pix_per_split, int32_t* reduce) {
-  const int rc = wgrad_check(a);
-  if (rc != DRNMI_OK) return rc;
-  const WgradRoute r = wgrad_route(*a, x6 != 0);
-  if (kernel != nullptr) *kernel = r.kernel;
-  if (splits != nullptr) *splits = r.splits;
-  if (pix_per_split != nullptr) *pix_per_split = r.per;
-  if (reduce != nullptr) *reduce = r.reduce;
-  return DRNMI_OK;
-}
-
-static int wgrad_launch(const drnmi_wgrad_args* a, bool x6, void* stream) {
-  const int rc = wgrad_check(a);
-  if (rc != DRNMI_OK) return rc;
-  if (a->dy == nullptr || a->x == nullptr || a->dw == nullptr || a->ws == nullptr) return DRNMI_EINVAL;
-  if (a->ws_bytes < (x6 ? drnmi_conv_wgrad_workspace_bytes(a) : drnmi_conv_wgrad_f32_workspace_bytes(a)))
-    return DRNMI_EINVAL;
-  // 16-B loads of dy / x; the dy bf16 planes in ws are LDS-DMA'd and stored as 16-B pieces
-  if ((reinterpret_cast<uintptr_t>(a->dy) | reinterpret_cast<uintptr_t>(a->x) | reinterpret_cast<uintptr_t>(a->ws)) & 15)
-    return DRNMI_EINVAL;
-  if (a->dy_stride % 4 != 0) return DRNMI_EINVAL;
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  WgradP p{};
-  p.dy = a->dy;
-  p.x = a->x;
-  p.ws = reinterpret_cast<float*>(a->ws);
-  p.dys = a->dy_stride;
-  p.cout = a->cout;
-  p.n = a->n; p.h = a->h; p.w = a->w; p.cs = a->cin_stride;
-  p.ho = a->ho; p.wo = a->wo; p.ks = a->ks; p.stride = a->stride; p.pad = a->pad; p.dil = a->dil;
-  p.K = a->ks * a->ks * a->cin_stride;
-  p.M = static_cast<int64_t>(a->n) * a->ho * a->wo;
-  const WgradRoute r = wgrad_route(*a, x6);
-  const int splits = r.splits;
-  p.pix_per_split = r.per;
-  const dim3 grid((p.K + kWT - 1) / kWT, (a->cout + kWT - 1) / kWT, splits);
-  const dim3 g2((p.K + kWT2 - 1) / kWT2, (a->cout + kWT2 - 1) / kWT2, splits);
-  if (r.kernel == DRNMI_WGRAD_DIRECT) {
-    const dim3 gd(static_cast<unsigned>(wgrad_direct_tiles(*a)), static_cast<unsigned>(splits / 4));
-    if (a->cout <= 16) hipLaunchKernelGGL(wgrad_x6_direct_kernel<1>, gd, dim3(kThreads), 0, s, p, a->cin);
-    else hipLaunchKernelGGL(wgrad_x6_direct_kernel<2>, gd, dim3(kThreads), 0, s, p, a->cin);
-  } else if (r.kernel == DRNMI_WGRAD_PRE) {
-    WgradPreP q{};
-    q.p = p;
-    q.Mp = (p.M + kWM - 1) / kWM * kWM;
-    q.Cp = (a->cout + kPreRows - 1) / kPreRows * kPreRows;
-    bf16_t* dyt = reinterpret_cast<bf16_t*>(reinterpret_cast<char*>(a->ws) + wgrad_partials_bytes(*a, r.full_splits));
-    q.dyt = dyt;
-    const int64_t blocks = (q.Mp / 32) * (q.Cp / 64);
-    hipLaunchKernelGGL(wgrad_dy_split_kernel, dim3(static_cast<unsigned>(blocks < 8192 ? blocks : 8192)), dim3(kThreads),
-                       0, s, a->dy, a->dy_stride, a->cout, p.M, q.Mp, q.Cp, dyt);
-    hipLaunchKernelGGL(wgrad_x6_pre_kernel, g2, dim3(kThreads), 0, s, q);
-  } else if (r.kernel == DRNMI_WGRAD_BIG) {
-    hipLaunchKernelGGL(wgrad_x6_big_kernel, g2, dim3(kThreads), 0, s, p);
-  } else if (r.kernel == DRNMI_WGRAD_X6) {
-    hipLaunchKernelGGL(wgrad_kernel<true>, grid, dim3(kThreads), 0, s, p);
-  } else {
-    hipLaunchKernelGGL(wgrad_kernel<false>, grid, dim3(kThreads), 0, s, p);
-  }
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return static_cast<int>(e);
-  const int64_t total = static_cast<int64_t>(a->cout) * p.K;
-  if (r.reduce)
-    hipLaunchKernelGGL(wgrad_reduce_grouped_kernel, dim3(static_cast<unsigned>((total + kRedOut - 1) / kRedOut)),
-                       dim3(kThreads), 0, s, p.ws, splits, a->cout, a->cin, a->cin_stride, a->ks, p.K, a->dw,
-                       a->accumulate);
-  else
-    hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(grid_of(total)), dim3(kThreads), 0, s, p.ws, splits, a->cout, a->cin,
-                       a->cin_stride, a->ks, p.K, a->dw, a->accumulate);
-  return static_cast<int>(hipGetLastError());
-}
-
 // fp32 [n] -> bf16 [3][n] planes, w = w1 + w2 + w3 (round to nearest even at each step): the weight
 // side of the fp32x arithmetic in one pass (drnmi/engine.py split3_bf16 took six ATen launches per
 // weight and step in the fp32x fine-tune)
@@ -2253,9 +1204,6 @@ extern "C" int drnmi_split3_bf16(const float* w, int64_t n, void* out, void* str
                      reinterpret_cast<bf16_t*>(out));
   return static_cast<int>(hipGetLastError());
 }
-
-extern "C" int drnmi_conv_wgrad_f32(const drnmi_wgrad_args* a, void* stream) { return wgrad_launch(a, false, stream); }
-extern "C" int drnmi_conv_wgrad_f32x3(const drnmi_wgrad_args* a, void* stream) { return wgrad_launch(a, true, stream); }
 
 extern "C" int drnmi_zero_insert_f32(const float* dy, int32_t n, int32_t ho, int32_t wo, int32_t c, int32_t stride,
                                      int32_t hu, int32_t wu, float* out, void* stream) {

@@ -155,7 +155,7 @@ SIGNATURES = {
     "drnmi_pack_table_check": (ctypes.c_int, [_VP, _I32, ctypes.POINTER(ctypes.c_int64)]),
     "drnmi_pack_conv_weights_batched": (ctypes.c_int, [_VP, _I32, _I64, _VP]),
 }
-WGRAD_KERNELS = ("wgrad_kernel<false>", "wgrad_kernel<true>", "wgrad_x6_big_kernel", "wgrad_x6_pre_kernel",
+WGRAD_KERNELS = ("wgrad_kernel<64, false>", "wgrad_kernel<64, true>", "wgrad_kernel<128, true>", "wgrad_x6_pre_kernel",
                  "wgrad_x6_direct_kernel")      # DRNMI_WGRAD_* of drnmi_conv_wgrad_plan
 WGRAD_REDUCES = ("wgrad_reduce_kernel", "wgrad_reduce_grouped_kernel")
 
