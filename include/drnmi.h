@@ -30,12 +30,12 @@ extern "C" {
  * against another header must not pass them: check drnmi_abi_version() == DRNMI_ABI_VERSION and
  * drnmi_conv_args_size() == sizeof(drnmi_conv_args) once after loading the library (drnmi/_lib.py
  * does, and refuses a mismatched library). */
-#define DRNMI_ABI_VERSION 6
+#define DRNMI_ABI_VERSION 7
 int32_t drnmi_abi_version(void);
 int64_t drnmi_conv_args_size(void);
 
 enum drnmi_dtype { DRNMI_F32 = 0, DRNMI_BF16 = 1, DRNMI_U8 = 2, DRNMI_I64 = 3, DRNMI_I8 = 4, DRNMI_F32X3 = 5,
-                   DRNMI_F8 = 6 };
+                   DRNMI_F8 = 6, DRNMI_BF16_SP24 = 7 };
 /* DRNMI_F32X3 (conv dtype only, the "fp32x" precision mode): x, res and y are fp32 NHWC as in
  * DRNMI_F32, wgt is three bf16 planes [3][cout_pad][k_pad] with w = w1 + w2 + w3 (an exact split
  * of the fp32 weight), and the conv runs fp32-accurate arithmetic on the bf16 MFMA pipe: each
@@ -64,6 +64,35 @@ enum drnmi_dtype { DRNMI_F32 = 0, DRNMI_BF16 = 1, DRNMI_U8 = 2, DRNMI_I64 = 3, D
  *              with cin % 256 == 0 and cout % 256 == 0 take the strip-staged conv_f8_stag_kernel
  *              (DRNMI_TILE_STAG forces it).  DRNMI_TILE_W1 / DRNMI_TILE_W1H, drnmi_conv_stag_seg, a
  *              unit mask and a fused second input have no fp8 form: DRNMI_ENOTSUP. */
+
+/* DRNMI_BF16_SP24 (conv dtype only; version 7; inference, opt-in: DRNSeg.set_sparse24): a bf16 launch
+ * whose weights have at most two non-zeros in every group of four consecutive packed columns (a
+ * group is 4 consecutive input channels of one tap: k = (kh*ks + kw)*cin + ci, cin % 4 == 0), run on
+ * the 2:4 structured-sparse MFMA v_smfmac_f32_16x16x64_bf16 (csrc/conv_sp24.hip).  x, res and y are
+ * as in a DRNMI_BF16 launch; wgt is the blob drnmi_sp24_pack wrote (0.5625 x the dense bytes: the
+ * kept values and their 2-bit positions; its layout is private to the kernel); scale must be NULL
+ * (folded into the weights before packing).
+ *   shapes   cin a power of two >= 64, ks 1 or 3 at any stride / dilation, any M, cout_pad % 128 == 0
+ *            (256 x 256 tiles when cout_pad % 256 == 0, else 128 x 256), k_pad == k, out_dtype
+ *            DRNMI_BF16 (NHWC rows) or DRNMI_F32 (any strides), residual and ReLU.
+ *   refused  DRNMI_ENOTSUP: x2, unit_mask, a non-NULL scale, drnmi_conv_stag_seg; DRNMI_EINVAL: cin not
+ *            a power of two and whatever every launch is refused for.
+ *   tile     read as this dtype's own variant: DRNMI_SP24_GATHER (the per-tap gather, every shape above),
+ *            DRNMI_SP24_STRIP (strip-staged pixels: 3x3, stride 1, pad == dil <= 4, wo % 256 == 0, on
+ *            the 256-channel tile; DRNMI_ENOTSUP elsewhere; measured no faster than the gather, kept for
+ *            A/B runs) or DRNMI_TILE_AUTO (the gather).  The two forms add in the same order:
+ *            bit-identical.
+ * Operand map of the instruction, measured on gfx950 (tests/test_gpu_sp24.py::test_operand_map;
+ * lane = 16 fq + fr, D = A x B with A 16 x 64 sparse, B 64 x 16 dense):
+ *   A    8 bf16 per lane: row fr, the kept values of dense k 16 fq .. 16 fq + 15; elements 2 g and
+ *        2 g + 1 are the kept pair of group g (k 16 fq + 4 g .. + 3), lower position first;
+ *   idx  one 32-bit register per lane; ABID (0 / 1) selects its low / high 16 bits; bits
+ *        [2 s + 1 : 2 s] of that half are the position (0..3) of A element s inside its group.  A
+ *        group with fewer than two non-zeros still names two positions (zeros are kept there);
+ *   B    16 bf16 per lane: column fr, elements 0-7 = k 8 fq .. 8 fq + 7, elements 8-15 = k 32 + 8 fq ..
+ *        + 7 (two v_mfma_f32_16x16x32_bf16 B fragments side by side);
+ *   D    4 fp32 per lane: rows 4 fq .. 4 fq + 3 of column fr, as the dense 16x16 MFMAs. */
+enum drnmi_sp24_tile { DRNMI_SP24_GATHER = 0, DRNMI_SP24_STRIP = 1 };
 
 enum drnmi_status {
   DRNMI_OK = 0,
@@ -298,6 +327,25 @@ int drnmi_basic_block16(const void* x, const void* pack, void* y, int32_t n, int
  * units; narrower blocks skip where neighbouring blocks are both pruned). */
 int drnmi_weight_unit_mask(const void* wgt, int32_t dtype, int32_t rows_pad, int32_t k_pad, uint32_t* mask,
                            int32_t* nonzero_units, void* stream);
+
+/* 2:4 packing for DRNMI_BF16_SP24 (csrc/conv_sp24.hip).  dense_bf16: packed bf16 weights
+ * [rows_pad][k_pad] (rows_pad % 32 == 0, k_pad % 64 == 0, device memory); out: device buffer of
+ * drnmi_sp24_pack_bytes(rows_pad, k_pad) = rows_pad * k_pad * 9 / 8 bytes (-1 for other sizes), 16-B
+ * aligned.  For every group of four consecutive packed columns the kernel writes the kept values and
+ * their positions in its own layout (private: nothing else reads the blob).  *violations (device int32,
+ * NULL-able) receives the number of groups with more than two non-zeros (+-0 count as zero); a blob
+ * with violations drops weights (the first two non-zeros of such a group are kept) and must not be
+ * launched.
+ * drnmi_sp24_mma_probe: one v_smfmac_f32_16x16x64_bf16 on one wave with a zero accumulator, for the
+ * operand-map test: a [64][8] bf16, b [64][16] bf16, idx [64] words, d [64][4] fp32 per lane, abid 0 / 1. */
+int64_t drnmi_sp24_pack_bytes(int32_t rows_pad, int32_t k_pad);
+int drnmi_sp24_pack(const void* dense_bf16, int32_t rows_pad, int32_t k_pad, void* out, int32_t* violations,
+                    void* stream);
+int drnmi_sp24_mma_probe(const void* a, const void* b, const uint32_t* idx, float* d, int32_t abid, void* stream);
+/* Issue-rate loop for scripts/sp24_micro.py: `blocks` workgroups of four waves (one per SIMD), every wave
+ * iters x 8 back-to-back MFMAs on 8 accumulators, operands in registers: sparse != 0 runs
+ * v_smfmac_f32_16x16x64_bf16, else v_mfma_f32_16x16x32_bf16.  sink: blocks x 256 floats. */
+int drnmi_sp24_issue_probe(int32_t sparse, int32_t iters, int32_t blocks, float* sink, void* stream);
 
 /* W8A8 helpers (BASELINE config C5; csrc/quant.hip).  The reference has no quantisation code
  * (SURVEY.md C5 row): the scheme is ours.  Activations are per-tensor symmetric int8.

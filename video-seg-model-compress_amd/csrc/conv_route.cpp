@@ -184,6 +184,22 @@ ConvRoute q8_route(const drnmi_conv_args& p) {
   return take(&v.k[ks3]);
 }
 
+// --- the 2:4 weight-sparse bf16 tiles (DRNMI_BF16_SP24, conv_sp24.hip).  tile is this dtype's own
+// variant (enum drnmi_sp24_tile).  The strip-staged form takes conv_strip_kernel's geometry on the
+// 256 x 256 tile and is a forced variant only: with the MFMA time of a K step halved, its two-stage ring
+// that waits for all of a step's DMA measured slower than the gather's three counted stages at
+// cin 512 (758 vs 707 us) and equal at cin 256 (profiles/sp24), so auto is the gather everywhere
+ConvRoute sp24_route(const drnmi_conv_args& p) {
+  if (p.tile != DRNMI_TILE_AUTO && p.tile != DRNMI_SP24_GATHER && p.tile != DRNMI_SP24_STRIP) return refuse(DRNMI_EINVAL);
+  if (!sp24_conv_supported(p)) return refuse(DRNMI_ENOTSUP);
+  const bool tile128 = p.cout_pad % 256 != 0 || p.cout <= 128;
+  const bool strip = !tile128 && strip_ok(p);
+  if (p.tile == DRNMI_SP24_STRIP && !strip) return refuse(DRNMI_ENOTSUP);
+  if (p.tile == DRNMI_SP24_STRIP) return take(sp24_strip_kernel());
+  if (!rows_exist(p, tile128 ? 128 : 256)) return refuse(DRNMI_EINVAL);
+  return take(sp24_kernel(tile128, p.ks));
+}
+
 // --- conv_x6.  A drnmi_conv_args.tile >= 0 forces variant tile % 6 and, when tile >= 6, tile / 6
 // split-K partitions (tests, micro-benchmarks; split-K only with a caller workspace).
 // 128-channel layers take the two-per-CU 128 x 128 tile: D-22 layer4's five launches 1631-1649 ->
@@ -302,11 +318,14 @@ ConvRoute conv_route(const drnmi_conv_args& p) {
                       !x6_conv_supported(p)))
     return refuse(DRNMI_EINVAL);
   if (p.algo == DRNMI_ALGO_PATCH) {
+    if (p.dtype == DRNMI_BF16_SP24) return refuse(DRNMI_EINVAL);
     if (p.x2 != nullptr) return refuse(DRNMI_ENOTSUP);     // fused second input: LDS-DMA kernels only
     if (p.n <= 0 || p.h <= 0 || p.w <= 0 || p.cout > p.cout_pad || !conv_geometry(p)) return refuse(DRNMI_EINVAL);
     return take(patch_kernel(p));
   }
   if (p.algo != DRNMI_ALGO_IGEMM || p.src_u8) return refuse(DRNMI_EINVAL);
+  // 2:4 sparse: no fused second input, unit mask or unfolded scale
+  if (p.dtype == DRNMI_BF16_SP24 && (p.x2 != nullptr || p.unit_mask != nullptr || p.scale != nullptr)) return refuse(DRNMI_ENOTSUP);
   const bool pow2 = p.cin >= 8 && (p.cin & (p.cin - 1)) == 0;
   if (!pow2 || p.n <= 0 || p.h <= 0 || p.w <= 0 || p.ho <= 0 || p.wo <= 0) return refuse(DRNMI_EINVAL);
   if (p.cout <= 0 || p.cout > p.cout_pad || p.k != p.ks * p.ks * p.cin + (p.x2 != nullptr ? p.cin2 : 0))
@@ -316,7 +335,7 @@ ConvRoute conv_route(const drnmi_conv_args& p) {
     if (p.out_dtype != p.dtype && p.out_dtype != DRNMI_BF16 && p.out_dtype != DRNMI_F32) return refuse(DRNMI_EINVAL);
   } else if (p.dtype == DRNMI_F32X3) {
     if (p.out_dtype != DRNMI_F32) return refuse(DRNMI_EINVAL);
-  } else if ((p.dtype != DRNMI_BF16 && p.dtype != DRNMI_F32) ||
+  } else if ((p.dtype != DRNMI_BF16 && p.dtype != DRNMI_F32 && p.dtype != DRNMI_BF16_SP24) ||
              (p.out_dtype != DRNMI_BF16 && p.out_dtype != DRNMI_F32)) {
     return refuse(DRNMI_EINVAL);
   }
@@ -326,6 +345,7 @@ ConvRoute conv_route(const drnmi_conv_args& p) {
   if (p.y_sr == 0 && !conv_geometry(p)) return refuse(DRNMI_EINVAL);
   if (p.dtype == DRNMI_I8 || p.dtype == DRNMI_F8) return q8_route(p);       // 8-bit: one kernel family
   if (p.dtype == DRNMI_F32X3) return x6_route(p);
+  if (p.dtype == DRNMI_BF16_SP24) return sp24_route(p);
   if (p.tile >= DRNMI_TILE_DMA128 || (p.tile < 0 && (big_conv_supported(p) || halo_conv_supported(p)))) return big_route(p);
   if (p.x2 != nullptr) return refuse(DRNMI_ENOTSUP);          // fused second input: LDS-DMA kernels only
   const int tile = p.tile < 0 ? auto_tile(p.cout) : p.tile;
@@ -348,7 +368,7 @@ struct SegRoute {
 // staggered one (the same partial logits, bit for bit: the bit-identity test).
 SegRoute seg_route(const drnmi_conv_args& p) {
   if (p.algo != DRNMI_ALGO_IGEMM || p.src_u8) return {DRNMI_EINVAL, nullptr};
-  if (p.dtype == DRNMI_F8) return {DRNMI_ENOTSUP, nullptr};   // no seg-fused fp8 form
+  if (p.dtype == DRNMI_F8 || p.dtype == DRNMI_BF16_SP24) return {DRNMI_ENOTSUP, nullptr};   // no seg-fused fp8 / 2:4 form
   const bool i8 = p.dtype == DRNMI_I8;
   // int8 nets: the conv's int8 output (out_dtype I8, quantised with out_scale) feeds int8 seg
   // weights; int32 partials

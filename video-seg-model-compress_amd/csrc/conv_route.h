@@ -87,6 +87,11 @@ const ConvKernel* w1_kernel(bool i8, bool x2);          // i8: no x2 form
 const ConvKernel* w1h_kernel(bool i8, bool x2);
 const SegKernel* w1_seg_kernel(bool i8);
 
+// conv_sp24.hip: the 2:4 weight-sparse bf16 tiles (dtype DRNMI_BF16_SP24), 256 x 256 or 128 x 256
+bool sp24_conv_supported(const drnmi_conv_args& p);
+const ConvKernel* sp24_kernel(bool tile128, int ks);
+const ConvKernel* sp24_strip_kernel();           // 3x3 stride 1, wo % 256 == 0, the 256 x 256 tile (strip_ok)
+
 // conv_halo.hip: halo-patch 3x3 stride-1 conv, cin / cout 64 or 128
 bool halo_conv_supported(const drnmi_conv_args& p);
 const ConvKernel* halo_kernel(int cin, int cout);

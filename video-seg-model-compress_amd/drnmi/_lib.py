@@ -11,6 +11,8 @@ import os
 from .build import LIB_PATH
 
 DRNMI_F32, DRNMI_BF16, DRNMI_U8, DRNMI_I64, DRNMI_I8, DRNMI_F32X3, DRNMI_F8 = 0, 1, 2, 3, 4, 5, 6
+DRNMI_BF16_SP24 = 7
+SP24_GATHER, SP24_STRIP = 0, 1          # include/drnmi.h enum drnmi_sp24_tile
 ALGO_IGEMM, ALGO_PATCH = 0, 1
 # include/drnmi.h enum drnmi_tile: the ids tests and micro-benchmarks force
 TILE_AUTO, TILE_DMA128, TILE_PP256, TILE_HALO, TILE_STRIP, TILE_STAG = -1, 4, 16, 17, 18, 19
@@ -134,6 +136,10 @@ SIGNATURES = {
     "drnmi_ce_loss_bwd_f32": (ctypes.c_int, [_VP, _VP, _I32, _I32, _I64, _I64, _VP, _VP, _VP, _VP]),
     "drnmi_sgd_step_f32": (ctypes.c_int, [_I32, _VP, _VP, _VP, _VP, _VP, _VP, _F32, _F32, _F32, _F32, _I32, _VP]),
     "drnmi_weight_unit_mask": (ctypes.c_int, [_VP, _I32, _I32, _I32, _VP, _VP, _VP]),
+    "drnmi_sp24_pack_bytes": (ctypes.c_int64, [_I32, _I32]),
+    "drnmi_sp24_pack": (ctypes.c_int, [_VP, _I32, _I32, _VP, _VP, _VP]),
+    "drnmi_sp24_mma_probe": (ctypes.c_int, [_VP, _VP, _VP, _VP, _I32, _VP]),
+    "drnmi_sp24_issue_probe": (ctypes.c_int, [_I32, _I32, _I32, _VP, _VP]),
     "drnmi_quantize_i8": (ctypes.c_int, [_VP, _I32, _VP, _I64, _F32, _VP]),
     "drnmi_quantize_f8": (ctypes.c_int, [_VP, _I32, _I64, _F32, _VP, _VP]),
     "drnmi_absmax": (ctypes.c_int, [_VP, _I32, _I64, _VP, _VP]),
@@ -169,7 +175,7 @@ def wgrad_plan(args: "WgradArgs", x6: bool):
     return WGRAD_KERNELS[k.value], s.value, per.value, WGRAD_REDUCES[r.value]
 
 
-ABI_VERSION = 6          # include/drnmi.h DRNMI_ABI_VERSION
+ABI_VERSION = 7          # include/drnmi.h DRNMI_ABI_VERSION
 
 _lib = None
 

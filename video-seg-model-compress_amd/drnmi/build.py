@@ -28,7 +28,10 @@ CFLAGS = ["-O3", "-fPIC", "-std=c++17", f"--offload-arch={ARCH}", "-I", INCLUDE,
 # per-source extra flags.  front.hip: MFMA results in VGPRs (the weights are pinned to AGPRs in the
 # source), so the epilogues read the accumulators without v_accvgpr_read copies
 EXTRA = {"front.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"], "block64.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"],
-         "conv_s2row.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"]}
+         "conv_s2row.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"],
+         # conv_sp24.hip: its dense issue-rate loop next to the sparse one (v_smfmac writes VGPRs only) without
+         # accumulator copies between AGPRs and VGPRs in the loop
+         "conv_sp24.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"]}
 
 
 def sources():

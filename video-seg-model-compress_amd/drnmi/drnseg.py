@@ -88,6 +88,7 @@ class DRNSeg(nn.Module):
         self.classes = classes
         self.precision = "fp32"
         self.block_sparse = False    # opt-in: measured slower than dense below ~60 % zero units
+        self.sparse24 = False        # opt-in: 2:4-pruned bf16 layers on the sparse MFMA (set_sparse24)
         self._graph = lower_drnseg(self.layer, self.seg)
         self._act_scales = None      # int8: per-value activation scales (calibrate_int8)
         self._int8_hists = None      # value -> |x| histogram of the last histogram calibration
@@ -399,6 +400,26 @@ class DRNSeg(nn.Module):
         self._pack_key = None
         return self
 
+    def set_sparse24(self, enabled: bool) -> "DRNSeg":
+        """bf16 inference: run every conv whose weights are 2:4 sparse along the input channels (at most
+        two non-zeros in every four consecutive channels of a tap: NMPruner) and that has the sparse
+        kernel's shape (cin >= 64, ks 1 / 3, no folded downsample) on the structured-sparse MFMA
+        (include/drnmi.h DRNMI_BF16_SP24).  Layers with a violating group stay dense; other precisions
+        are untouched.  Opt-in, off by default; takes effect at the next pack."""
+        self.sparse24 = bool(enabled)
+        for pk in self._packed.values():
+            pk.sparse24 = self.sparse24
+        self._pack_key = None
+        return self
+
+    def sparse24_layers(self, device=None) -> list:
+        """Names of the conv nodes the current precision's pack launches on the 2:4 sparse kernel
+        (packs first if needed; [] with the switch off or outside bf16)."""
+        if not self.sparse24 or self.precision != "bf16":
+            return []
+        device = torch.device(device or next(self.parameters()).device)
+        return self._packed_net(device).sparse24_layers()
+
     def plan(self, n, h, w, device=None, keep_all=False) -> Plan:
         device = device or next(self.parameters()).device
         plan, _ = self._prepare(n, h, w, torch.device(device), keep_all=keep_all)
@@ -438,6 +459,16 @@ class DRNSeg(nn.Module):
         return (self.precision, tuple((t.data_ptr(), t._version) for t in ts))
 
     def _prepare(self, n, h, w, device, keep_all=False):
+        pk = self._packed_net(device)
+        pkey = (self.precision, n, h, w, keep_all)
+        plan = self._plans.get(pkey)
+        if plan is None:
+            plan = Plan(pk, n, h, w, keep_all=keep_all)
+            self._plans[pkey] = plan
+        return plan, _lib.stream_ptr(device)
+
+    def _packed_net(self, device) -> PackedNet:
+        """The current precision's PackedNet, (re)packed if the weights or a packing switch changed."""
         if device.type != "cuda":
             raise RuntimeError("drnmi.DRNSeg runs on the HIP engine only: move the model and input "
                                "to a ROCm device (no CPU fallback by design)")
@@ -462,14 +493,9 @@ class DRNSeg(nn.Module):
         pk = self._packed.get(self.precision)
         if pk is None:
             pk = PackedNet(self._graph, self.precision, device, block_sparse=self.block_sparse,
-                           act_scales=self._act_scales)
+                           act_scales=self._act_scales, sparse24=getattr(self, "sparse24", False))
             self._packed[self.precision] = pk
-        pkey = (self.precision, n, h, w, keep_all)
-        plan = self._plans.get(pkey)
-        if plan is None:
-            plan = Plan(pk, n, h, w, keep_all=keep_all)
-            self._plans[pkey] = plan
-        return plan, _lib.stream_ptr(device)
+        return pk
 
 
 def load_info(path: str):

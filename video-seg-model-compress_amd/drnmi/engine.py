@@ -113,6 +113,9 @@ class ConvNode:
     # (include/drnmi.h drnmi_conv_args.x2); ds_of names the folded-away downsample node
     fused: dict | None = None    # {"wpk", "shift", "k", "x2_val", "stride2", "ds": node index}
     fused_into: int = -1         # downsample node: index of the conv that computes it
+    # 2:4 weight sparsity (bf16, PackedNet.sparse24): the drnmi_sp24_pack blob of wpk; the launch is
+    # DRNMI_BF16_SP24 with wgt = wsp (wpk stays: the seg-fused form and keep_all plans read it)
+    wsp: torch.Tensor | None = None
 
 
 @dataclass
@@ -223,10 +226,11 @@ class PackedNet:
     any PackedNet stays valid while other precisions are packed."""
 
     def __init__(self, graph: Graph, precision: str, device, block_sparse: bool = True,
-                 act_scales: dict | None = None):
+                 act_scales: dict | None = None, sparse24: bool = False):
         self.graph = Graph(nodes=[dataclasses.replace(nd) for nd in graph.nodes],
                            stage_outputs=dict(graph.stage_outputs), channels=dict(graph.channels))
         self.block_sparse = block_sparse
+        self.sparse24 = sparse24
         self.precision = precision
         # int8 / fp8 nets run their small-channel layers in bf16: "base" is that precision
         self.qcode = Q8_CODES.get(precision)       # the net's 8-bit value code (None: no 8-bit launches)
@@ -357,6 +361,40 @@ class PackedNet:
             self._packs = {}                  # front_pack / block_pack blobs on the device, by key
             self.front_eligible = self._front_shapes_ok()
             self.block_pairs = {c: self._block_pairs(c) for c in (16, 64)}
+            self._pack_sp24()
+
+    def _pack_sp24(self):
+        """bf16 with sparse24 on: every conv that has the sparse kernel's shape (asked of the library's
+        own route), a folded BN scale, no folded downsample on either side, no part in a fused block
+        and not one group of four input channels with more than two non-zeros is packed 2:4
+        (include/drnmi.h drnmi_sp24_pack) and launched as DRNMI_BF16_SP24.  Everything else stays dense."""
+        for nd in self.graph.nodes:
+            nd.wsp = None
+        if not self.sparse24 or self.precision != "bf16":
+            return
+        lib = _lib.load()
+        in_block = {j for pairs in self.block_pairs.values() for i in pairs for j in (i, i + 1)}
+        cnt = torch.zeros(1, dtype=torch.int32, device=self.device)
+        for i, nd in enumerate(self.graph.nodes):
+            if not nd.scale_folded or nd.i8 or nd.x6 or nd.fused or nd.fused_into >= 0 or i in in_block or \
+                    nd.unit_mask is not None or nd.cin_stride < 64:
+                continue
+            a = _probe_args(nd, nd.cin_stride, nd.k, nd.k_pad)
+            a.dtype = _lib.DRNMI_BF16_SP24
+            if nd.out_fp32_nchw:
+                a.out_dtype, a.y_sp, a.y_sc = _lib.DRNMI_F32, 1, a.ho * a.wo
+            if lib.drnmi_conv_kernel_name(ctypes.byref(a)) is None:
+                continue
+            rows, kp = nd.wpk.shape
+            blob = torch.empty(int(lib.drnmi_sp24_pack_bytes(rows, kp)), dtype=torch.uint8, device=self.device)
+            _lib.check(lib.drnmi_sp24_pack(nd.wpk.data_ptr(), rows, kp, blob.data_ptr(), cnt.data_ptr(),
+                                           ctypes.c_void_p(_lib.stream_ptr(self.device))), f"sp24_pack {nd.name}")
+            if int(cnt.item()) == 0:            # read back once per (re)pack, never in the launch loop
+                nd.wsp = blob
+
+    def sparse24_layers(self) -> list:
+        """Names of the nodes launched on the 2:4 sparse kernel."""
+        return [nd.name for nd in self.graph.nodes if nd.wsp is not None]
 
     def _front_shapes_ok(self) -> bool:
         """The fused video front (drnmi_video_front_u8: layer0 + layer1 + layer2 of every DRN-D,
@@ -800,7 +838,8 @@ class Plan:
         a.y_sn, a.y_sp, a.y_sc = lh * lw * cs, cs, 1
         name = lib.drnmi_conv_kernel_name(ctypes.byref(a))   # (routing does not read a.y)
         if name is None or not name.decode().startswith(("conv_big_kernel", "conv_i8_kernel", "conv_i8_occ2_kernel",
-                                                        "conv_x6_kernel", "conv_f8_kernel", "conv_f8_occ2_kernel")):
+                                                        "conv_x6_kernel", "conv_f8_kernel", "conv_f8_occ2_kernel",
+                                                        "conv_sp24_kernel")):
             return
         if "logits_nhwc" not in self.bufs:      # only plans whose seg conv writes the NHWC rows
             self.bufs["logits_nhwc"] = torch.empty(self.n * lh * lw * cs, dtype=torch.float32, device=pk.device)
@@ -936,6 +975,8 @@ class Plan:
         a.algo = _lib.ALGO_PATCH if _uses_patch(nd, nd.cin_stride, pk.base) else _lib.ALGO_IGEMM
         a.res_scale, a.out_scale = nd.res_scale, nd.out_scale
         a.unit_mask = nd.unit_mask.data_ptr() if nd.unit_mask is not None else None
+        if nd.wsp is not None:                    # 2:4 sparse launch (never a node with a folded downsample)
+            a.wgt, a.dtype = nd.wsp.data_ptr(), _lib.DRNMI_BF16_SP24
         if fused:
             f = fused
             a.wgt, a.shift, a.res = f["wpk"].data_ptr(), f["shift"].data_ptr(), None

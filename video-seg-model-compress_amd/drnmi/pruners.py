@@ -281,7 +281,7 @@ def _load_configs(config_fp):
 def make_pruner(config_fp, on_gpu=True):
     """JSON pruner_type dispatch (semantic_seg.py:822-847)."""
     kind = _load_configs(config_fp)["pruner_type"]
-    table = {"block": BlockPruner, "rmb": RmbPruner, "srmbrep": SRMBRepMasker}
+    table = {"block": BlockPruner, "rmb": RmbPruner, "srmbrep": SRMBRepMasker, "nm": NMPruner}
     if kind not in table:
         raise NotImplementedError(f"pruner_type {kind!r}: hb/rmcdb/grouping mask generators are out of "
                                   "scope (their masks still apply through Pruner.apply_masks)")
@@ -831,5 +831,56 @@ class SRMBRepMasker(Pruner):
         return np.kron(fac["ocp"].astype(dt), ib).reshape(fac["shape"])
 
 
+# ============================================================================ NMPruner
+class NMPrunerConfig:
+    def __init__(self, n, m, seed=0):
+        if isinstance(n, bool) or isinstance(m, bool) or m != 4 or n not in (1, 2):
+            raise ValueError(f"NMPruner: n:m = {n!r}:{m!r}; only m == 4 with n in (1, 2) is supported")
+        self.n, self.m, self.seed = int(n), int(m), int(seed)
+
+    def __str__(self):
+        return "{}:{}".format(self.n, self.m)
+
+
+class NMPruner(Pruner):
+    """n:m structured sparsity along the input channels: of every m = 4 consecutive input channels at a
+    fixed (out, kh, kw) exactly n weights are kept.  n <= 2 is the pattern the 2:4 sparse MFMA takes
+    (include/drnmi.h DRNMI_BF16_SP24, DRNSeg.set_sparse24).  Not in the reference; the masks are 0/1
+    fp32 like every other pruner's, so apply_masks, save_masks / load_masks and the masked SGD take
+    them unchanged.  Config: {"pruner_type": "nm", "configs": [{"layer_set": [...], "n": 2, "m": 4,
+    "seed": 0 (optional, static masks)}]}."""
+
+    def parse_config_file(self, config_fp):
+        cfg = collections.OrderedDict()
+        for ls in _load_configs(config_fp)["configs"]:
+            c = NMPrunerConfig(ls["n"], ls["m"], ls.get("seed", 0))
+            for layer in ls["layer_set"]:
+                cfg[layer] = c
+        return cfg
+
+    def generate_masks(self, model, is_static=False, verbose=False):
+        """is_static=False: keep the n largest |w| of every group (ties: the lower channel);
+        True: n positions per group drawn from RandomState(seed + the layer's index in the config)."""
+        sd = model.state_dict()
+        for li, (layer, pc) in enumerate(self.layer_configs.items()):
+            w = sd[layer].detach().cpu().numpy()
+            if verbose:
+                print(f"Generating {pc} mask for layer {layer} ({'static' if is_static else 'magnitude'})")
+            rng = np.random.RandomState(pc.seed + li) if is_static else None
+            self._store(layer, NMPruner.nm_mask(w, pc.n, pc.m, rng))
+
+    @staticmethod
+    def nm_mask(tensor: np.ndarray, n: int, m: int = 4, rng=None) -> np.ndarray:
+        if tensor.ndim != 4 or tensor.shape[1] % m != 0:
+            raise ValueError(f"NMPruner: weight of shape {tuple(tensor.shape)}: OIHW with in_channels % {m} == 0 expected")
+        cout, cin, kh, kw = tensor.shape
+        score = np.abs(tensor.astype(np.float32)) if rng is None else rng.rand(cout, cin, kh, kw).astype(np.float32)
+        grp = score.transpose(0, 2, 3, 1).reshape(cout, kh, kw, cin // m, m)
+        order = np.argsort(-grp, axis=-1, kind="stable")          # descending; equal scores: lower channel first
+        keep = np.zeros(grp.shape, dtype=np.float32)
+        np.put_along_axis(keep, order[..., :n], 1.0, axis=-1)
+        return np.ascontiguousarray(keep.reshape(cout, kh, kw, cin).transpose(0, 3, 1, 2))
+
+
 __all__ = ["Pruner", "BlockPruner", "BlockPrunerConfig", "BlockMatrix", "RmbPruner", "RmbPrunerConfig",
-           "BlockletType", "SRMBRepMasker", "SRMBRepMaskerConfig", "make_pruner"]
+           "BlockletType", "SRMBRepMasker", "SRMBRepMaskerConfig", "NMPruner", "NMPrunerConfig", "make_pruner"]

@@ -24,6 +24,8 @@ def kernel_peak(kernel_name: str, base: str) -> float:
         return MFMA_PEAK["int8"]
     if kernel_name.startswith("conv_x6"):
         return MFMA_PEAK["fp32x"]
+    if kernel_name.startswith("conv_sp24"):       # 2:4 sparse bf16: dense-equivalent FLOPs against AMD's 2x sparse peak
+        return 2 * MFMA_PEAK["bf16"]
     return MFMA_PEAK["fp32" if base == "fp32x" else base]
 
 
