@@ -68,7 +68,8 @@ enum drnmi_dtype { DRNMI_F32 = 0, DRNMI_BF16 = 1, DRNMI_U8 = 2, DRNMI_I64 = 3, D
 /* DRNMI_BF16_SP24 (conv dtype only; version 7; inference, opt-in: DRNSeg.set_sparse24): a bf16 launch
  * whose weights have at most two non-zeros in every group of four consecutive packed columns (a
  * group is 4 consecutive input channels of one tap: k = (kh*ks + kw)*cin + ci, cin % 4 == 0), run on
- * the 2:4 structured-sparse MFMA v_smfmac_f32_16x16x64_bf16 (csrc/conv_sp24.hip).  x, res and y are
+ * the 2:4 structured-sparse MFMA v_smfmac_f32_16x16x64_bf16 (csrc/conv_sp24.hip: its own main loop on
+ * the gather pieces and epilogues of csrc/conv_tile.h, as the dense tiles of csrc/conv_big_body.h).  x, res and y are
  * as in a DRNMI_BF16 launch; wgt is the blob drnmi_sp24_pack wrote (0.5625 x the dense bytes: the
  * kept values and their 2-bit positions; its layout is private to the kernel); scale must be NULL
  * (folded into the weights before packing).

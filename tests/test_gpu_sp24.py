@@ -38,6 +38,7 @@ CASES = [
     (1, 6, 256, 64, 160, 3, 1, 4, False, True),
     (1, 6, 256, 256, 512, 3, 1, 2, True, False),
     (2, 2, 256, 128, 128, 3, 1, 1, False, True),       # whole rows on the 128-channel tile: the gather
+    (1, 3, 5, 64, 512, 1, 1, 1, True, False),          # one K step (fewer than the ring's prologue) on the 256-channel tile
 ]
 
 

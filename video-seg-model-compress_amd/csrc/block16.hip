@@ -314,11 +314,7 @@ extern "C" int drnmi_basic_block16(const void* x, const void* pack, void* y, int
     if (hipGetDevice(&dev) != hipSuccess ||
         hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0)
       cus = 256;
-    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&block16_kernel),
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, kLds);
-    if (e != hipSuccess) return static_cast<int>(e);
-    g_block16_wgs = 2 * cus;                           // two workgroups per CU; set only once the LDS
-                                                       // attribute is in place
+    g_block16_wgs = 2 * cus;                           // two workgroups per CU
   }
   Block16Params p;
   p.x = static_cast<const uint16_t*>(x);
@@ -331,6 +327,5 @@ extern "C" int drnmi_basic_block16(const void* x, const void* pack, void* y, int
   p.total = n * p.strips * h;
   p.per_wg = (p.total + g_block16_wgs - 1) / g_block16_wgs;
   const int grid = (p.total + p.per_wg - 1) / p.per_wg;
-  hipLaunchKernelGGL(block16_kernel, dim3(grid), dim3(256), kLds, static_cast<hipStream_t>(stream), p);
-  return static_cast<int>(hipGetLastError());
+  return static_cast<int>(launch_lds<&block16_kernel>(dim3(grid), dim3(256), kLds, static_cast<hipStream_t>(stream), p));
 }

@@ -149,6 +149,29 @@ __device__ __forceinline__ void transpose_rows4(uint32_t (&r)[4]) {
   r[3] = d[1];
 }
 
+// More than 64 KB of dynamic LDS is an opt-in per kernel (hipFuncAttributeMaxDynamicSharedMemorySize).
+// allow_lds makes it once per kernel, at the first size asked for; a kernel whose size varies asks for its
+// largest first (the wide confusion matrix) or is raised when a later launch needs more (conv_halo's patch
+// grows with the dilation).  One flag per kernel, whatever the argument types of the launch.
+template <auto KERNEL>
+hipError_t allow_lds(int lds) {
+  static int attr_lds = 0;
+  if (attr_lds < lds) {
+    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(KERNEL), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+    if (e != hipSuccess) return e;
+    attr_lds = lds;
+  }
+  return hipSuccess;
+}
+// allow_lds, then the launch with `lds` bytes of dynamic LDS: the first error of the two
+template <auto KERNEL, typename... Args>
+hipError_t launch_lds(dim3 grid, dim3 block, int lds, hipStream_t s, const Args&... args) {
+  const hipError_t e = allow_lds<KERNEL>(lds);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(KERNEL, grid, block, lds, s, args...);
+  return hipGetLastError();
+}
+
 inline int ceil_div(int64_t a, int64_t b) { return static_cast<int>((a + b - 1) / b); }
 
 // workgroups of `per` threads for the n elements of a grid-stride kernel (at least 1, at most 2^20 - 16)

@@ -375,16 +375,8 @@ template <int CIN, int WC, int TC>
 hipError_t launch_halo(const drnmi_conv_args& p, hipStream_t s) {
   static_assert(TC == halo_tc(CIN, 64 * WC), "the block width halo_conv_supported sizes the patch for");
   const int lds = kNST * 64 * WC * 128 + patch_bytes(CIN, p.dil, TC);
-  static int attr_lds = 0;
-  if (attr_lds < lds) {
-    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_halo_kernel<CIN, WC, TC>),
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    if (e != hipSuccess) return e;
-    attr_lds = lds;
-  }
   const int64_t tiles = static_cast<int64_t>(p.n) * ((p.ho + kTR - 1) / kTR) * ((p.wo + TC - 1) / TC);
-  hipLaunchKernelGGL((conv_halo_kernel<CIN, WC, TC>), dim3(static_cast<unsigned>(tiles)), dim3(256 * WC), lds, s, p);
-  return hipGetLastError();
+  return launch_lds<&conv_halo_kernel<CIN, WC, TC>>(dim3(static_cast<unsigned>(tiles)), dim3(256 * WC), lds, s, p);
 }
 
 }  // namespace

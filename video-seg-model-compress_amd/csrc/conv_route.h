@@ -89,6 +89,8 @@ const SegKernel* w1_seg_kernel(bool i8);
 
 // conv_sp24.hip: the 2:4 weight-sparse bf16 tiles (dtype DRNMI_BF16_SP24), 256 x 256 or 128 x 256
 bool sp24_conv_supported(const drnmi_conv_args& p);
+// conv_big.hip: the size and shape terms common to big_conv_supported, q8_conv_supported and sp24_conv_supported
+bool big_body_shape_ok(const drnmi_conv_args& p, int min_cin);
 const ConvKernel* sp24_kernel(bool tile128, int ks);
 const ConvKernel* sp24_strip_kernel();           // 3x3 stride 1, wo % 256 == 0, the 256 x 256 tile (strip_ok)
 

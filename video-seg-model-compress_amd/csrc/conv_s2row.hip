@@ -484,8 +484,6 @@ conv_s1x2row_kernel(const S1Params a) {
 }
 
 int g_cus = 0;
-constexpr auto kern32 = &conv_s2row_kernel<32, kRing32, kWgs32>;
-constexpr auto kern64 = &conv_s2row_kernel<64, kRing64, kWgs64>;
 
 template <auto KERNEL>
 hipError_t launch_s1x2row(const drnmi_conv_args& p, hipStream_t st) {
@@ -495,9 +493,6 @@ hipError_t launch_s1x2row(const drnmi_conv_args& p, hipStream_t st) {
     if (hipGetDevice(&dev) != hipSuccess ||
         hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0)
       cus = 256;
-    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(KERNEL),
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, kS1Lds);
-    if (e != hipSuccess) return e;
     wgs = 2 * cus;                                      // two workgroups per CU (58 KB LDS each)
   }
   S1Params a;
@@ -519,25 +514,16 @@ hipError_t launch_s1x2row(const drnmi_conv_args& p, hipStream_t st) {
   a.total = static_cast<int>(total);
   a.per_wg = (a.total + wgs - 1) / wgs;
   const int grid = (a.total + a.per_wg - 1) / a.per_wg;
-  hipLaunchKernelGGL(KERNEL, dim3(grid), dim3(256), kS1Lds, st, a);
-  return hipGetLastError();
+  return launch_lds<KERNEL>(dim3(grid), dim3(256), kS1Lds, st, a);
 }
 
 template <int CIN, int RING, int WGS>
 hipError_t launch_s2row(const drnmi_conv_args& p, hipStream_t st) {
-  static_assert(CIN == 32 ? (RING == kRing32 && WGS == kWgs32) : (CIN == 64 && RING == kRing64 && WGS == kWgs64),
-                "the instantiations whose attributes are set below");
   if (g_cus == 0) {
     int dev = 0, cus = 0;
     if (hipGetDevice(&dev) != hipSuccess ||
         hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0)
       cus = 256;
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern32), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       s2_lds_bytes<kRing32>());
-    if (e == hipSuccess)
-      e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern64), hipFuncAttributeMaxDynamicSharedMemorySize,
-                              s2_lds_bytes<kRing64>());
-    if (e != hipSuccess) return e;
     g_cus = cus;
   }
   const int wgs = g_cus * WGS;   // persistent: WGS workgroups per CU
@@ -560,8 +546,7 @@ hipError_t launch_s2row(const drnmi_conv_args& p, hipStream_t st) {
   a.total = static_cast<int>(total);
   a.per_wg = (a.total + wgs - 1) / wgs;
   const int grid = (a.total + a.per_wg - 1) / a.per_wg;
-  hipLaunchKernelGGL((conv_s2row_kernel<CIN, RING, WGS>), dim3(grid), dim3(256), s2_lds_bytes<RING>(), st, a);
-  return hipGetLastError();
+  return launch_lds<&conv_s2row_kernel<CIN, RING, WGS>>(dim3(grid), dim3(256), s2_lds_bytes<RING>(), st, a);
 }
 
 }  // namespace

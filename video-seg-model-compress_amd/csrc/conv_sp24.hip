@@ -3,10 +3,11 @@
 //
 // conv_big.hip's per-tap gather with the sparse MFMA in place of two dense ones: A = weights with at
 // most two non-zeros in every four consecutive input channels of a tap, stored compressed (the kept
-// values + 2-bit positions, drnmi_sp24_pack), B = pixels, dense.  What is shared with conv_big
-// (conv_tile.h): the LDS-DMA gather with the zero page, the swizzles, the counted vmcnt + one barrier
-// per K step, fragment reads one MFMA group ahead, the XCD-major tile deal, init_tile / store_tile /
-// store_tile_x4.
+// values + 2-bit positions, drnmi_sp24_pack), B = pixels, dense.  conv_sp24_body is a main loop of its
+// own, written out next to conv_big_body (conv_big_body.h): as one template over a fourth element type the
+// sparse kernels lost their schedule (profiles/sp24_fold/README.txt).  From conv_tile.h, one copy for both:
+// the swizzles, glds16 / glds4, the XCD-major tile deal, the strip source (strip_src), the strip geometry,
+// init_tile / store_tile / store_tile_x4.  Built with VGPR-form MFMAs (build.py).
 //
 // Operand map of the instruction (measured, tests/test_gpu_sp24.py::test_operand_map), lane = 16 fq + fr:
 //   A  lane holds row fr's 8 kept values of dense k 16 fq .. 16 fq + 15: slots (2 g, 2 g + 1) are the
@@ -38,10 +39,6 @@ namespace drnmi {
 namespace {
 
 typedef __bf16 bf16x16 __attribute__((ext_vector_type(16)));
-
-__device__ __forceinline__ void glds4(const void* src, char* lds_wave_base) {
-  __builtin_amdgcn_global_load_lds((g_void_t*)src, (lds_void_t*)lds_wave_base, 4, 0, 0);
-}
 
 template <int WCO, int WC>
 struct Sp24Cfg {
@@ -177,14 +174,7 @@ __device__ __forceinline__ void conv_sp24_body(const drnmi_conv_args& p) {
     const int j = wave + 8 * sh;
     if (j >= kStripPieces) return;                 // wave-uniform
     const int R = j * 8 + (lane >> 3);
-    const int cb = g / 3, kh = g - cb * 3;
-    const int ih = s_oh - p.pad + kh * dil;
-    const int iw = s_ow0 - p.pad + R;
-    const bool ok = R < kBPX + 2 * dil && static_cast<unsigned>(ih) < static_cast<unsigned>(H) &&
-                    static_cast<unsigned>(iw) < static_cast<unsigned>(W);
-    const void* src = ok ? static_cast<const void*>(x + ((static_cast<int64_t>(s_n) * H + ih) * W + iw) * cin + cb * BK +
-                                                    ((lane & 7) ^ (R & 7)) * 8)
-                         : static_cast<const void*>(zero_src);
+    const void* src = strip_src<BK, 8>(p, x, g, R, lane & 7, s_n, s_oh, s_ow0, H, W, cin, dil, zero_src);
     glds16(src, strips + (g & 1) * kStripBytes + j * 1024);
   };
   constexpr int GL = STRIP ? C::A_INSTR + 1 + 2 : C::GLDS;   // pieces a wave issues per step (strip: + two strip shares)
@@ -287,37 +277,27 @@ conv_sp24_strip_kernel(const drnmi_conv_args p) {
   conv_sp24_body<3, 128, 2, true>(p);
 }
 
+// the three dynamic LDS sizes and the DMA pieces per wave and step (the counted vmcnt), pinned
+constexpr int kSp24StripLds = 2 * (Sp24Cfg<128, 2>::A_BYTES + Sp24Cfg<128, 2>::I_BYTES) + 2 * kStripBytes;
+static_assert(Sp24Cfg<128, 2>::LDS == 3 * 50 * 1024 && Sp24Cfg<128, 2>::GLDS == 2 + 1 + 4, "256 x 256 gather");
+static_assert(Sp24Cfg<128, 1>::LDS == 3 * 41 * 1024 && Sp24Cfg<128, 1>::GLDS == 2 + 1 + 8, "128 x 256 gather");
+static_assert(kSp24StripLds == (2 * 18 + 2 * 33) * 1024, "strip form");
+
 template <auto KERNEL>
 hipError_t launch_sp24_strip(const drnmi_conv_args& p, hipStream_t s) {
-  using C = Sp24Cfg<128, 2>;
-  constexpr int LDS = 2 * (C::A_BYTES + C::I_BYTES) + 2 * kStripBytes;
-  static bool attr_set = false;
-  if (!attr_set) {
-    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(KERNEL), hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-    if (e != hipSuccess) return e;
-    attr_set = true;
-  }
   const int64_t M = static_cast<int64_t>(p.n) * p.ho * p.wo;
   const int64_t blocks = (M / kBPX) * ((p.cout + 255) / 256);
-  hipLaunchKernelGGL(KERNEL, dim3(static_cast<unsigned>(blocks)), dim3(512), LDS, s, p);
-  return hipGetLastError();
+  return launch_lds<KERNEL>(dim3(static_cast<unsigned>(blocks)), dim3(512), kSp24StripLds, s, p);
 }
 
 template <int KS, int WCO, int WC>
 hipError_t launch_sp24(const drnmi_conv_args& p, hipStream_t s) {
   using C = Sp24Cfg<WCO, WC>;
-  static bool attr_set = false;
-  if (!attr_set) {
-    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_sp24_kernel<KS, WCO, WC>),
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, C::LDS);
-    if (e != hipSuccess) return e;
-    attr_set = true;
-  }
   const int64_t M = static_cast<int64_t>(p.n) * p.ho * p.wo;
   const int64_t blocks = ((M + kBPX - 1) / kBPX) * ((p.cout + C::BCO - 1) / C::BCO);
-  hipLaunchKernelGGL((conv_sp24_kernel<KS, WCO, WC>), dim3(static_cast<unsigned>(blocks)), dim3(C::THREADS), C::LDS, s, p);
-  return hipGetLastError();
+  return launch_lds<&conv_sp24_kernel<KS, WCO, WC>>(dim3(static_cast<unsigned>(blocks)), dim3(C::THREADS), C::LDS, s, p);
 }
+
 
 // One lane per (32-row block, K step, index word): rows rb * 32 + fr and + 16 + fr, dense columns
 // kt * 64 + 16 fq .. + 15 -> 2 x 8 kept values (one 16-B store each) and one index word.  A group keeps
@@ -434,9 +414,7 @@ const ConvKernel* sp24_strip_kernel() {
 // the sparse kernel's shapes: conv_big's with cin >= 64 and a folded scale; no second input, no unit mask
 bool sp24_conv_supported(const drnmi_conv_args& p) {
   return p.dtype == DRNMI_BF16_SP24 && p.x2 == nullptr && p.unit_mask == nullptr && p.scale == nullptr &&
-         p.cin >= 64 && (p.cin & (p.cin - 1)) == 0 && p.cout_pad % 128 == 0 && (p.ks == 1 || p.ks == 3) &&
-         p.k == p.ks * p.ks * p.cin && p.k_pad == p.k &&
-         static_cast<int64_t>(p.n) * p.h * p.w * p.cin < (int64_t(1) << 31) && p.h < 16384 && p.w < 16384 &&
+         big_body_shape_ok(p, 64) && p.k == p.ks * p.ks * p.cin &&
          static_cast<int64_t>(p.cout_pad) * p.k_pad < (int64_t(1) << 31) &&
          (p.out_dtype == DRNMI_F32 || (p.out_dtype == DRNMI_BF16 && p.y_sc == 1 && p.y_sp == p.cout));
 }

@@ -625,60 +625,28 @@ constexpr int kStag128Lds = 2 * 128 * 128 + 2 * kStripBytes;  // 128-channel til
 
 template <auto KERNEL>
 hipError_t launch_stag_seg(const drnmi_conv_args& p, const void* seg_w, int seg_k_pad, void* part, hipStream_t s) {
-  static bool attr_set = false;
-  if (!attr_set) {
-    for (const void* f : {reinterpret_cast<const void*>(&conv_stag_seg_kernel), reinterpret_cast<const void*>(&conv_i8_stag_seg_kernel)}) {
-      const hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, kStagLds);
-      if (e != hipSuccess) return e;
-    }
-    attr_set = true;
-  }
   StagSegArgs a;
   a.p = p;
   a.sf = SegFuse{seg_w, seg_k_pad, part};
   const int64_t M = static_cast<int64_t>(p.n) * p.ho * p.wo;
   const dim3 grid(static_cast<unsigned>((M / kBPX) * ((p.cout + 255) / 256)));
-  hipLaunchKernelGGL(KERNEL, grid, dim3(512), kStagLds, s, a);
-  return hipGetLastError();
-}
-
-static hipError_t stag_attrs() {
-  static bool attr_set = false;
-  if (!attr_set) {
-    for (const void* f : {reinterpret_cast<const void*>(&conv_stag_kernel), reinterpret_cast<const void*>(&conv_stag_x2_kernel),
-                          reinterpret_cast<const void*>(&conv_i8_stag_kernel), reinterpret_cast<const void*>(&conv_f8_stag_kernel)}) {
-      const hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, kStagLds);
-      if (e != hipSuccess) return e;
-    }
-    for (const void* f : {reinterpret_cast<const void*>(&conv_stag128_kernel), reinterpret_cast<const void*>(&conv_stag128_x2_kernel)}) {
-      const hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, kStag128Lds);
-      if (e != hipSuccess) return e;
-    }
-    attr_set = true;
-  }
-  return hipSuccess;
+  return launch_lds<KERNEL>(grid, dim3(512), kStagLds, s, a);
 }
 
 // the 256-channel tile
 template <auto KERNEL>
 hipError_t launch_stag(const drnmi_conv_args& p, hipStream_t s) {
-  const hipError_t e = stag_attrs();
-  if (e != hipSuccess) return e;
   const int64_t M = static_cast<int64_t>(p.n) * p.ho * p.wo;
   const dim3 grid(static_cast<unsigned>((M / kBPX) * ((p.cout + 255) / 256)));
-  hipLaunchKernelGGL(KERNEL, grid, dim3(512), kStagLds, s, p);
-  return hipGetLastError();
+  return launch_lds<KERNEL>(grid, dim3(512), kStagLds, s, p);
 }
 
 // the 128-channel tile (bf16, cout <= 128)
 template <auto KERNEL>
 hipError_t launch_stag128(const drnmi_conv_args& p, hipStream_t s) {
-  const hipError_t e = stag_attrs();
-  if (e != hipSuccess) return e;
   const int64_t M = static_cast<int64_t>(p.n) * p.ho * p.wo;
   const dim3 g128(static_cast<unsigned>((M / kBPX) * ((p.cout + 127) / 128)));
-  hipLaunchKernelGGL(KERNEL, g128, dim3(512), kStag128Lds, s, p);
-  return hipGetLastError();
+  return launch_lds<KERNEL>(g128, dim3(512), kStag128Lds, s, p);
 }
 
 const ConvKernel* stag_kernel(int dtype, bool tile128, bool x2) {

@@ -1,5 +1,6 @@
-// Tile machinery shared by the bf16 / int8 LDS-DMA implicit-GEMM conv kernels (conv_big.hip,
-// conv_stag.hip): swizzles, element traits, the XCD remap, epilogues and the strip geometry.
+// Tile machinery shared by the LDS-DMA implicit-GEMM conv kernels (conv_big_body.h for conv_big.hip,
+// conv_sp24.hip, conv_stag.hip, conv_w1.hip): swizzles, element traits, the XCD remap, epilogues, the strip
+// geometry and the strip rows' DMA source.
 // Internal header (anonymous namespace: each translation unit gets its own copies).
 #pragma once
 #include "common.h"
@@ -121,6 +122,28 @@ template <> struct Q8<f8_t> {
 
 __device__ __forceinline__ void glds16(const void* src, char* lds_wave_base) {
   __builtin_amdgcn_global_load_lds((g_void_t*)src, (lds_void_t*)lds_wave_base, 16, 0, 0);
+}
+__device__ __forceinline__ void glds4(const void* src, char* lds_wave_base) {
+  __builtin_amdgcn_global_load_lds((g_void_t*)src, (lds_void_t*)lds_wave_base, 4, 0, 0);
+}
+
+// --- One copy for conv_big_body (conv_big_body.h) and conv_sp24_body (conv_sp24.hip), whose main
+// loops are written out separately
+// STRIP: DMA source of row R, slot lslot, of the strip of group g = K steps 3g..3g+2 (channel block
+// g / 3, tap row kh = g % 3) of the tile at image s_n, output row s_oh, first column s_ow0: strip row
+// R = input pixel (oh - pad + kh dil, ow0 - pad + R), 16-B chunk c at slot c ^ (R & 7) (conflict-free
+// for the 16 consecutive rows of a fragment read at any kw*dil offset)
+template <int BK, int CE, typename T>
+__device__ __forceinline__ const void* strip_src(const drnmi_conv_args& p, const T* x, int g, int R, int lslot, int s_n,
+                                                 int s_oh, int s_ow0, int H, int W, int cin, int dil, const char* zero_src) {
+  const int cb = g / 3, kh = g - cb * 3;
+  const int ih = s_oh - p.pad + kh * dil;
+  const int iw = s_ow0 - p.pad + R;
+  const bool ok = R < kBPX + 2 * dil && static_cast<unsigned>(ih) < static_cast<unsigned>(H) &&
+                  static_cast<unsigned>(iw) < static_cast<unsigned>(W);
+  return ok ? static_cast<const void*>(x + ((static_cast<int64_t>(s_n) * H + ih) * W + iw) * cin + cb * BK +
+                                       (lslot ^ (R & 7)) * CE)
+            : static_cast<const void*>(zero_src);
 }
 
 // index of the n-th set bit of m (n < popcount(m)): binary search on popcounts

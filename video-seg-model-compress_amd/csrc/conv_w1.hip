@@ -686,58 +686,28 @@ conv_w1h_i8_kernel(const drnmi_conv_args p) {
 
 }  // namespace
 
-static hipError_t w1_attrs() {
-  static bool attr_set = false;
-  if (!attr_set) {
-    for (const void* f : {reinterpret_cast<const void*>(&conv_w1_kernel), reinterpret_cast<const void*>(&conv_w1_seg_kernel),
-                          reinterpret_cast<const void*>(&conv_w1_i8_kernel), reinterpret_cast<const void*>(&conv_w1_i8_seg_kernel)}) {
-      const hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, W1::LDS);
-      if (e != hipSuccess) return e;
-    }
-    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_w1_x2_kernel),
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, W1::LDS);
-    if (e != hipSuccess) return e;
-    for (const void* f : {reinterpret_cast<const void*>(&conv_w1h_kernel), reinterpret_cast<const void*>(&conv_w1h_x2_kernel),
-                          reinterpret_cast<const void*>(&conv_w1h_i8_kernel)}) {
-      const hipError_t e2 = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, W1H::LDS);
-      if (e2 != hipSuccess) return e2;
-    }
-    attr_set = true;
-  }
-  return hipSuccess;
-}
-
 template <auto KERNEL>
 hipError_t launch_w1_seg(const drnmi_conv_args& p, const void* seg_w, int seg_k_pad, void* part, hipStream_t s) {
-  const hipError_t e = w1_attrs();
-  if (e != hipSuccess) return e;
   W1SegArgs a;
   a.p = p;
   a.sf = W1Seg{seg_w, seg_k_pad, part};
   const int64_t M = static_cast<int64_t>(p.n) * p.ho * p.wo;
   const dim3 grid(static_cast<unsigned>((M / W1::TPX) * ((p.cout + 255) / 256)));
-  hipLaunchKernelGGL(KERNEL, grid, dim3(256), W1::LDS, s, a);
-  return hipGetLastError();
+  return launch_lds<KERNEL>(grid, dim3(256), W1::LDS, s, a);
 }
 
 template <auto KERNEL>
 hipError_t launch_w1(const drnmi_conv_args& p, hipStream_t s) {
-  const hipError_t e0 = w1_attrs();
-  if (e0 != hipSuccess) return e0;
   const int64_t M = static_cast<int64_t>(p.n) * p.ho * p.wo;
   const dim3 grid(static_cast<unsigned>((M / W1::TPX) * ((p.cout + 255) / 256)));
-  hipLaunchKernelGGL(KERNEL, grid, dim3(256), W1::LDS, s, p);
-  return hipGetLastError();
+  return launch_lds<KERNEL>(grid, dim3(256), W1::LDS, s, p);
 }
 
 template <auto KERNEL>
 hipError_t launch_w1h(const drnmi_conv_args& p, hipStream_t s) {
-  const hipError_t e0 = w1_attrs();
-  if (e0 != hipSuccess) return e0;
   const int64_t M = static_cast<int64_t>(p.n) * p.ho * p.wo;
   const dim3 grid(static_cast<unsigned>((M / W1H::TPX) * ((p.cout + 127) / 128)));
-  hipLaunchKernelGGL(KERNEL, grid, dim3(256), W1H::LDS, s, p);
-  return hipGetLastError();
+  return launch_lds<KERNEL>(grid, dim3(256), W1H::LDS, s, p);
 }
 
 const ConvKernel* w1_kernel(bool i8, bool x2) {

@@ -569,18 +569,10 @@ __global__ void __launch_bounds__(256) x6_splitk_epilogue_kernel(const drnmi_con
 template <int KS, int WCO, int WC, int PS>
 hipError_t launch_x6(const drnmi_conv_args& p, int splits, hipStream_t s) {
   using C = X6Cfg<WCO, WC, PS>;
-  static bool attr_set = false;
-  if (!attr_set) {
-    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_x6_kernel<KS, WCO, WC, PS>),
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, C::LDS);
-    if (e != hipSuccess) return e;
-    attr_set = true;
-  }
   const int64_t M = static_cast<int64_t>(p.n) * p.ho * p.wo;
   const int64_t blocks = ((M + C::BPX - 1) / C::BPX) * ((p.cout + C::BCO - 1) / C::BCO);
-  hipLaunchKernelGGL((conv_x6_kernel<KS, WCO, WC, PS>), dim3(static_cast<unsigned>(blocks), splits), dim3(C::THREADS),
-                     C::LDS, s, p);
-  hipError_t e = hipGetLastError();
+  const hipError_t e = launch_lds<&conv_x6_kernel<KS, WCO, WC, PS>>(dim3(static_cast<unsigned>(blocks), splits),
+                                                                    dim3(C::THREADS), C::LDS, s, p);
   if (e != hipSuccess || splits == 1) return e;
   const int64_t total = M * ((p.cout + 3) / 4);
   int64_t g = (total + 255) / 256;

@@ -582,19 +582,13 @@ int launch_confusion_wide(const void* pred, const void* label, int64_t npix, int
   const int slabs = ceil_div(static_cast<int64_t>(n) * n * 4, kHistWideBytes);
   const int rows = ceil_div(n, slabs);
   const int lds = rows * n * 4;
-  static bool attr_set = false;                      // per instantiation: above 64 KiB is opt-in
-  if (!attr_set) {
-    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&confusion_wide_kernel<TP, TL>),
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, kHistWideBytes);
-    if (e != hipSuccess) return static_cast<int>(e);
-    attr_set = true;
-  }
   int64_t g = (npix + 8 * kHistWideThreads - 1) / (8 * kHistWideThreads);
   g = g > kHistWideGrid ? kHistWideGrid : g;
-  hipLaunchKernelGGL((confusion_wide_kernel<TP, TL>), dim3(static_cast<unsigned>(g), static_cast<unsigned>(slabs)),
-                     dim3(kHistWideThreads), lds, s, static_cast<const TP*>(pred), static_cast<const TL*>(label), npix,
-                     n, rows, hist);
-  return static_cast<int>(hipGetLastError());
+  const hipError_t e = allow_lds<&confusion_wide_kernel<TP, TL>>(kHistWideBytes);   // the largest a launch asks for
+  if (e != hipSuccess) return static_cast<int>(e);
+  return static_cast<int>(launch_lds<&confusion_wide_kernel<TP, TL>>(
+      dim3(static_cast<unsigned>(g), static_cast<unsigned>(slabs)), dim3(kHistWideThreads), lds, s,
+      static_cast<const TP*>(pred), static_cast<const TL*>(label), npix, n, rows, hist));
 }
 
 }  // namespace

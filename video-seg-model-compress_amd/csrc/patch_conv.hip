@@ -876,8 +876,7 @@ hipError_t launch_patch(const drnmi_conv_args& p, hipStream_t s) {
 hipError_t launch_stem_dma(const drnmi_conv_args& p, hipStream_t s) {
   static int per_cu = 0;
   if (per_cu == 0) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(stem_dma_kernel),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, kStemLDS);
+    const hipError_t e = allow_lds<&stem_dma_kernel>(kStemLDS);   // before the occupancy query that sizes the grid
     if (e != hipSuccess) return e;
     int dev = 0, cus = 0, blocks = 0;
     if (hipGetDevice(&dev) != hipSuccess ||
@@ -891,16 +890,13 @@ hipError_t launch_stem_dma(const drnmi_conv_args& p, hipStream_t s) {
   }
   const int64_t tiles = static_cast<int64_t>(p.n) * ((p.ho + kStemTR - 1) / kStemTR) * ((p.wo + kStemTC - 1) / kStemTC);
   const int64_t cap = static_cast<int64_t>(g_num_cus) * per_cu;
-  hipLaunchKernelGGL(stem_dma_kernel, dim3(static_cast<unsigned>(tiles < cap ? tiles : cap)), dim3(kThreads),
-                     kStemLDS, s, p);
-  return hipGetLastError();
+  return launch_lds<&stem_dma_kernel>(dim3(static_cast<unsigned>(tiles < cap ? tiles : cap)), dim3(kThreads), kStemLDS, s, p);
 }
 
 hipError_t launch_stem_l1(const drnmi_conv_args& p, const drnmi_conv_args& q, hipStream_t s) {
   static int per_cu = 0;
   if (per_cu == 0) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(stem_l1_kernel),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, kSLLDS);
+    const hipError_t e = allow_lds<&stem_l1_kernel>(kSLLDS);
     if (e != hipSuccess) return e;
     int dev = 0, cus = 0, blocks = 0;
     if (hipGetDevice(&dev) != hipSuccess ||
@@ -914,19 +910,16 @@ hipError_t launch_stem_l1(const drnmi_conv_args& p, const drnmi_conv_args& q, hi
   }
   const int64_t tiles = static_cast<int64_t>(p.n) * ((p.h + kSLTR - 1) / kSLTR) * ((p.w + kSLTC - 1) / kSLTC);
   const int64_t cap = static_cast<int64_t>(g_num_cus) * per_cu;
-  hipLaunchKernelGGL(stem_l1_kernel, dim3(static_cast<unsigned>(tiles < cap ? tiles : cap)), dim3(kThreads),
-                     kSLLDS, s, p, q);
-  return hipGetLastError();
+  return launch_lds<&stem_l1_kernel>(dim3(static_cast<unsigned>(tiles < cap ? tiles : cap)), dim3(kThreads), kSLLDS, s, p, q);
 }
 
 template <int CIN, int COUT, int S, int TR, int TC>
 hipError_t launch_patch_dma(const drnmi_conv_args& p, hipStream_t s) {
   using C = DmaCfg<CIN, COUT, S, TR, TC>;
   static int per_cu = 0;
-  auto kern = patch_dma_kernel<CIN, COUT, S, TR, TC>;
+  constexpr auto kern = &patch_dma_kernel<CIN, COUT, S, TR, TC>;
   if (per_cu == 0) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, C::LDS);
+    const hipError_t e = allow_lds<kern>(C::LDS);
     if (e != hipSuccess) return e;
     int dev = 0, cus = 0, blocks = 0;
     if (hipGetDevice(&dev) != hipSuccess ||
@@ -940,8 +933,7 @@ hipError_t launch_patch_dma(const drnmi_conv_args& p, hipStream_t s) {
   }
   const int64_t tiles = static_cast<int64_t>(p.n) * ((p.ho + TR - 1) / TR) * ((p.wo + TC - 1) / TC);
   const int64_t cap = static_cast<int64_t>(g_num_cus) * per_cu;
-  hipLaunchKernelGGL(kern, dim3(static_cast<unsigned>(tiles < cap ? tiles : cap)), dim3(kThreads), C::LDS, s, p);
-  return hipGetLastError();
+  return launch_lds<kern>(dim3(static_cast<unsigned>(tiles < cap ? tiles : cap)), dim3(kThreads), C::LDS, s, p);
 }
 
 }  // namespace

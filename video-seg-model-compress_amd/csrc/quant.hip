@@ -168,13 +168,6 @@ __global__ void __launch_bounds__(kHistThreads) abs_histogram_kernel(const T* __
 
 template <typename T>
 hipError_t launch_abs_histogram(const T* x, int64_t n8, int64_t* hist, hipStream_t s) {
-  static bool attr_set = false;          // > 64 KiB of dynamic LDS is an opt-in per kernel
-  if (!attr_set) {
-    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&abs_histogram_kernel<T>),
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(kHistLds));
-    if (e != hipSuccess) return e;
-    attr_set = true;
-  }
   if (g_hist_wgs == 0) {
     int dev = 0, cus = 0;
     if (hipGetDevice(&dev) != hipSuccess ||
@@ -183,9 +176,8 @@ hipError_t launch_abs_histogram(const T* x, int64_t n8, int64_t* hist, hipStream
     g_hist_wgs = cus;
   }
   const int64_t b = (n8 + kHistThreads - 1) / kHistThreads;
-  hipLaunchKernelGGL(abs_histogram_kernel<T>, dim3(static_cast<unsigned>(b < g_hist_wgs ? b : g_hist_wgs)),
-                     dim3(kHistThreads), kHistLds, s, x, n8, reinterpret_cast<unsigned long long*>(hist));
-  return hipGetLastError();
+  return launch_lds<&abs_histogram_kernel<T>>(dim3(static_cast<unsigned>(b < g_hist_wgs ? b : g_hist_wgs)), dim3(kHistThreads),
+                                              static_cast<int>(kHistLds), s, x, n8, reinterpret_cast<unsigned long long*>(hist));
 }
 
 }  // namespace
