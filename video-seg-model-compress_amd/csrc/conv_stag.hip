@@ -169,10 +169,6 @@ __device__ __forceinline__ void conv_stag_body(const drnmi_conv_args& p, const S
   const int H = p.h, W = p.w, dil = p.dil;
   const T* __restrict__ x = reinterpret_cast<const T*>(p.x);
   const T* __restrict__ wt = reinterpret_cast<const T*>(p.wgt);
-  const int nk = 9 * cin / BK;                       // tap steps: whole groups of 3
-  const int ngroups = nk / 3;
-  const int nx2 = X2 ? p.cin2 / BK : 0;              // x2 steps after the taps
-  const int nk_tot = nk + nx2;
   const int fr = lane & 15;
   const int fq = lane >> 4;
   const int lrow = lane >> 3;
@@ -185,6 +181,21 @@ __device__ __forceinline__ void conv_stag_body(const drnmi_conv_args& p, const S
   const int s_q = px0 - s_n * hw_o;
   const int s_oh = s_q / p.wo;
   const int s_ow0 = s_q - s_oh * p.wo;
+  // the tile's live tap rows (conv_tile.h TapWin): the K loop walks only those.  A tap row outside
+  // the image contributed +-0 (so a non-finite weight there no longer makes 0 x inf = NaN)
+  // (the X2 forms keep the full window and the full walk's code: conv_stag_x2 sits at the register
+  // limit, and with the window's scalars it spilled and measured 14-21 % slower)
+  const TapWin tw = X2 ? TapWin{0, 3} : live_tap_rows(s_oh, H, p.pad, dil);
+  const int gpc = __builtin_amdgcn_readfirstlane(tw.gpc);
+  const uint32_t rcp = __builtin_amdgcn_readfirstlane(tap_rcp(tw.gpc));
+  const int ngroups = (cin / BK) * gpc;              // live tap groups: even as the full walk's (cin / BK even: dispatch)
+  const int nk = 3 * ngroups;                        // live tap steps: whole groups of 3
+  const int nx2 = X2 ? p.cin2 / BK : 0;              // x2 steps after the taps
+  const int nk_tot = nk + nx2;
+  const int w_col0 = 3 * tw.kh0 * cin;               // weight column of the window's first tap (in a_off)
+  // byte offsets of the window's first input row (image s_n, row s_oh - pad + kh0 dil) and of one tap row
+  const int x_row0 = __builtin_amdgcn_readfirstlane(((s_n * H + s_oh - p.pad + tw.kh0 * dil) * W * cin) * K::ESZ);
+  const int x_rowd = __builtin_amdgcn_readfirstlane(dil * W * cin * K::ESZ);
   // DMA through buffer resources: per-lane 32-bit byte offsets, out-of-image pixels as an
   // out-of-range offset (the load returns zeros: the conv's zero padding), wave-uniform parts
   // in SGPRs -- one VGPR per stream instead of a 64-bit address and a validity mask
@@ -204,29 +215,43 @@ __device__ __forceinline__ void conv_stag_body(const drnmi_conv_args& p, const S
 #pragma unroll
   for (int i = 0; i < 2; ++i) {
     const int r = (wave * AI + i) * 8 + lrow;
-    a_off[i] = ((co0 + r) * p.k_pad + swzb<128>(r, lslot) * CE) * K::ESZ;
+    a_off[i] = ((co0 + r) * p.k_pad + w_col0 + swzb<128>(r, lslot) * CE) * K::ESZ;
   }
   constexpr uint32_t kOOB = 0x80000000u;             // beyond every buffer (sizes < 2^31)
 
-  // weight piece i (rows (wave*4 + i)*8 .. +8) of K step kt into A stage `stage`
+  // weight piece i (rows (wave*4 + i)*8 .. +8) of live K step kt into A stage `stage`
   auto issue_a = [&](int kt, int stage, int i) {
-    const int cb = kt / 9;
-    const int tap = kt - cb * 9;
-    const int k0 = (X2 && kt >= nk) ? 9 * cin + (kt - nk) * BK : (tap << lc) + cb * BK;
+    int k0;
+    if constexpr (X2) {
+      const int cb = kt / 9;
+      k0 = kt >= nk ? 9 * cin + (kt - nk) * BK : ((kt - cb * 9) << lc) + cb * BK;
+    } else {
+      const int cb = tap_div(rcp, kt);
+      k0 = (step_tap(gpc, kt, cb) << lc) + cb * BK;
+    }
     dma(rs_w, a_off[i & 1], ((i & ~1) * 8 * p.k_pad + k0) * K::ESZ, stage * AB + (wave * AI + i) * 1024);
   };
-  // strip share sh of group g (channel block g / 3, tap row g % 3) into strip buffer `buf`
+  // strip share sh of live group g (channel block g / gpc, tap row kh0 + g % gpc: inside the
+  // image) into strip buffer `buf`
   auto issue_strip = [&](int g, int buf, int sh) {
     const int j = wave + 8 * sh;
     if (j >= kStripPieces) return;                   // wave-uniform
     const int R = j * 8 + lrow;
-    const int cb = g / 3, kh = g - cb * 3;
-    const int ih = s_oh - p.pad + kh * dil;
     const int iw = s_ow0 - p.pad + R;
     const bool ok = R < kBPX + 2 * dil && static_cast<unsigned>(iw) < static_cast<unsigned>(W);
-    const bool row_ok = static_cast<unsigned>(ih) < static_cast<unsigned>(H);   // wave-uniform
-    const uint32_t voff = ok && row_ok ? static_cast<uint32_t>((iw * cin + (lslot ^ (R & 7)) * CE) * K::ESZ) : kOOB;
-    const int soff = row_ok ? ((s_n * H + ih) * W * cin + cb * BK) * K::ESZ : 0;
+    uint32_t voff;
+    int soff;
+    if constexpr (X2) {                              // the full walk: rows outside the image read zeros
+      const int cb = g / 3, kh = g - cb * 3;
+      const int ih = s_oh - p.pad + kh * dil;
+      const bool row_ok = static_cast<unsigned>(ih) < static_cast<unsigned>(H);   // wave-uniform
+      voff = ok && row_ok ? static_cast<uint32_t>((iw * cin + (lslot ^ (R & 7)) * CE) * K::ESZ) : kOOB;
+      soff = row_ok ? ((s_n * H + ih) * W * cin + cb * BK) * K::ESZ : 0;
+    } else {
+      const int cb = tap_div(rcp, 3 * g);
+      voff = ok ? static_cast<uint32_t>((iw * cin + (lslot ^ (R & 7)) * CE) * K::ESZ) : kOOB;
+      soff = x_row0 + group_row(gpc, g, cb) * x_rowd + cb * BK * K::ESZ;
+    }
     dma_x(rs_x, voff, soff, 2 * AB + buf * kStripBytes + j * 1024);
   };
   // X2: share sh of x2 step e's B -- pixel R of the tile sampled at stride2 in x2, channels
@@ -434,7 +459,7 @@ __device__ __forceinline__ void conv_stag_body(const drnmi_conv_args& p, const S
     phase(I2{}, I0{}, gp_c, g);
     phase(I2{}, I1{}, gp_c, g);
   };
-  for (int g = 0; g < ngroups; g += 2) {             // ngroups even (cin % 128 == 0, dispatch)
+  for (int g = 0; g < ngroups; g += 2) {             // ngroups even (cin / BK even: dispatch)
     group(I0{}, g);
     group(I1{}, g + 1);
   }

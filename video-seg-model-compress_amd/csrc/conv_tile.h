@@ -171,6 +171,86 @@ __device__ __forceinline__ int xcd_remap2(int bid, int nwg) {
   return base + bid / 8;
 }
 
+// --- The live tap-row window of a strip tile (conv_stag.hip, conv_w1.hip: 3x3, stride 1, pad = dil).
+// A tile is a run of one output row oh; tap row kh reads input row ih = oh - pad + kh dil.  A tap row
+// outside the image is all padding: its strip is zeros, and its three K steps (weight DMA, MFMAs,
+// barriers) add +-0 to every accumulator.  The tiles walk only the live rows kh0 .. kh0 + gpc - 1
+// (gpc = 1..3: the centre row is always inside), i.e. ncb * gpc groups and 3 ncb gpc K steps for ncb
+// channel blocks, in the full walk's order (cb, kh, kw) with the dead rows left out: the surviving
+// steps keep their order per accumulator, so for finite weights the output is the full walk's bit
+// for bit (up to the sign of an exactly-zero sum; integer sums are equal unconditionally).  A
+// non-finite weight in a skipped tap row no longer turns 0 x inf into NaN.
+// Scalar cost: kh0 is folded into the tile's weight column and input row bases, so the decodes below
+// are relative to the window; their divisor 3 gpc is wave-uniform, and kt / (3 gpc) is one scalar
+// mul-hi by rcp = ceil(2^32 / (3 gpc)) (exact for kt < 2^29), the cost of the compile-time / 9 it
+// replaces; with every walked row inside the image the loops' row checks are gone.
+// The group count ncb * gpc has the parity the full walk's 3 ncb needs for any gpc wherever that
+// one is even (the forms that pair their groups: ncb is even), so no tile needs the full window.
+// (One copy of the K loop per gpc, with compile-time divisors, spilled vector registers in every
+// form; a decode that kept kh0 and the row checks in the loop measured 13 % slower.)
+struct TapWin {
+  int kh0, gpc;     // first live tap row, live tap rows per channel block
+};
+__host__ __device__ constexpr TapWin live_tap_rows(int oh, int H, int pad, int dil) {
+  int kh0 = 0, gpc = 0;
+  for (int kh = 2; kh >= 0; --kh) {
+    const int ih = oh - pad + kh * dil;
+    if (ih >= 0 && ih < H) {
+      kh0 = kh;
+      ++gpc;
+    }
+  }
+  return {kh0, gpc};
+}
+__host__ __device__ constexpr uint32_t tap_rcp(int gpc) { return gpc == 1 ? 0x55555556u : gpc == 2 ? 0x2AAAAAABu : 0x1C71C71Du; }
+__host__ __device__ constexpr int tap_div(uint32_t rcp, int kt) {               // kt / (3 gpc)
+  return static_cast<int>((static_cast<uint64_t>(static_cast<uint32_t>(kt)) * rcp) >> 32);
+}
+// live K step kt -> channel block cb; tap inside the window, 3 (kh - kh0) + kw
+__host__ __device__ constexpr int step_tap(int gpc, int kt, int cb) { return kt - cb * 3 * gpc; }
+// live group g -> channel block cb = tap_div(3 g); tap row inside the window, kh - kh0
+__host__ __device__ constexpr int group_row(int gpc, int g, int cb) { return g - cb * gpc; }
+
+// the live step sequence == the full sequence (cb, kh, kw) with the out-of-image kh removed, in
+// the same order; the groups likewise; and the mul-hi is the division, also far past any real K
+constexpr bool tap_win_ok(int H, int dil) {
+  constexpr int ncb = 4;
+  for (int oh = 0; oh < H; ++oh) {
+    const TapWin w = live_tap_rows(oh, H, dil, dil);
+    if (w.gpc < 1 || w.gpc > 3) return false;
+    const uint32_t rcp = tap_rcp(w.gpc);
+    int kt = 0, g = 0;
+    for (int cb = 0; cb < ncb; ++cb)
+      for (int kh = 0; kh < 3; ++kh) {
+        const int ih = oh - dil + kh * dil;
+        if (ih < 0 || ih >= H) continue;
+        if (tap_div(rcp, 3 * g) != cb || w.kh0 + group_row(w.gpc, g, cb) != kh) return false;
+        ++g;
+        for (int kw = 0; kw < 3; ++kw, ++kt)
+          if (tap_div(rcp, kt) != cb || 3 * w.kh0 + step_tap(w.gpc, kt, cb) != 3 * kh + kw) return false;
+      }
+    if (g != ncb * w.gpc || kt != 3 * g) return false;
+  }
+  return true;
+}
+constexpr bool tap_win_all_ok() {
+  for (int H = 1; H <= 12; ++H)
+    for (int dil = 1; dil <= 4; dil *= 2)
+      if (!tap_win_ok(H, dil)) return false;
+  return true;
+}
+constexpr bool tap_div_ok() {
+  for (int gpc = 1; gpc <= 3; ++gpc) {
+    for (int kt = 0; kt < 4096; ++kt)
+      if (tap_div(tap_rcp(gpc), kt) != kt / (3 * gpc)) return false;
+    for (int kt = (1 << 29) - 64; kt < (1 << 29); ++kt)
+      if (tap_div(tap_rcp(gpc), kt) != kt / (3 * gpc)) return false;
+  }
+  return true;
+}
+static_assert(tap_win_all_ok(), "live tap steps: the full (cb, kh, kw) walk without the out-of-image rows");
+static_assert(tap_div_ok(), "tap_div: kt / (3 gpc)");
+
 // Epilogue shared by the conv kernels: lane owns channels co..co+3 of pixel m for FM x 4
 // accumulator fragments (folded BN scale/shift, optional residual, ReLU); bf16 NHWC rows get
 // one 8-byte store per fragment, other layouts (fp32 / strided seg logits) element stores.

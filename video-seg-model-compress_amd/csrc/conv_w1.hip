@@ -193,8 +193,6 @@ __device__ __forceinline__ void conv_w1_body(const drnmi_conv_args& p, const W1S
   const int cin = p.cin;
   const int lc = 31 - __builtin_clz(cin);
   const int H = p.h, W = p.w, dil = p.dil;
-  const int nk = 9 * cin / BK;
-  const int ngroups = nk / 3;                        // even (bf16: cin % 128 == 0), or ODDOK
   const int fr = lane & 15;
   const int fq = lane >> 4;
   const int lrow = lane >> 3;
@@ -207,6 +205,17 @@ __device__ __forceinline__ void conv_w1_body(const drnmi_conv_args& p, const W1S
   const int s_q = px0 - s_n * hw_o;
   const int s_oh = s_q / p.wo;
   const int s_ow0 = s_q - s_oh * p.wo;
+  // the tile's live tap rows (conv_tile.h TapWin): the K loop walks only those.  A tap row outside
+  // the image contributed +-0 (so a non-finite weight there no longer makes 0 x inf = NaN)
+  const TapWin tw = live_tap_rows(s_oh, H, p.pad, dil);
+  const int gpc = __builtin_amdgcn_readfirstlane(tw.gpc);
+  const uint32_t rcp = __builtin_amdgcn_readfirstlane(tap_rcp(tw.gpc));
+  const int ngroups = (cin / BK) * gpc;              // even as the full walk's (cin / BK even), or ODDOK
+  const int nk = 3 * ngroups;
+  const int w_col0 = 3 * tw.kh0 * cin;               // weight column of the window's first tap (in a_off)
+  // byte offsets of the window's first input row (image s_n, row s_oh - pad + kh0 dil) and of one tap row
+  const int x_row0 = __builtin_amdgcn_readfirstlane(((s_n * H + s_oh - p.pad + tw.kh0 * dil) * W * cin) * ESZ);
+  const int x_rowd = __builtin_amdgcn_readfirstlane(dil * W * cin * ESZ);
   const int xbytes = p.n * H * W * cin * ESZ;        // < 2^31 (big_conv_supported / q8_conv_supported)
   const __amdgpu_buffer_rsrc_t rs_x = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p.x), 0, xbytes, 0x00020000);
   const __amdgpu_buffer_rsrc_t rs_w = __builtin_amdgcn_make_buffer_rsrc(
@@ -221,28 +230,26 @@ __device__ __forceinline__ void conv_w1_body(const drnmi_conv_args& p, const W1S
 #pragma unroll
   for (int i = 0; i < 2; ++i) {
     const int r = (wave * AI + i) * 8 + lrow;
-    a_off[i] = ((co0 + r) * p.k_pad + swzb<128>(r, lslot) * CE) * ESZ;
+    a_off[i] = ((co0 + r) * p.k_pad + w_col0 + swzb<128>(r, lslot) * CE) * ESZ;
   }
   constexpr uint32_t kOOB = 0x80000000u;             // beyond every buffer (sizes < 2^31)
+  // (the prologue's steps 0 and 1: channel block 0, tap kt of the window)
   auto issue_a = [&](int kt, int stage, int i) __attribute__((always_inline)) {
-    const int cb = kt / 9;
-    const int tap = kt - cb * 9;
-    const int k0 = (tap << lc) + cb * BK;
+    const int k0 = kt << lc;
     dma(rs_w, a_off[i & 1], ((i & ~1) * 8 * p.k_pad + k0) * ESZ, stage * AB + (wave * AI + i) * 1024);
   };
-  // strip share sh of group g (channel block g / 3, tap row g % 3): piece j = wave + 4 sh; past the
-  // strip (j >= NSP) it reads nothing into the sink, so every wave issues the same count
+  // strip share sh of live group g (channel block g / gpc, tap row kh0 + g % gpc: inside the image):
+  // piece j = wave + 4 sh; past the strip (j >= NSP) it reads nothing into the sink, so every wave
+  // issues the same count
   auto issue_strip = [&](int g, int buf, int sh) __attribute__((always_inline)) {
     const int j = wave + 4 * sh;
     const bool inside = j < NSP;
     const int R = j * 8 + lrow;
-    const int cb = g / 3, kh = g - cb * 3;
-    const int ih = s_oh - p.pad + kh * dil;
+    const int cb = tap_div(rcp, 3 * g);
     const int iw = s_ow0 - p.pad + R;
     const bool ok = inside && R < TPX + 2 * dil && static_cast<unsigned>(iw) < static_cast<unsigned>(W);
-    const bool row_ok = static_cast<unsigned>(ih) < static_cast<unsigned>(H);   // wave-uniform
-    const uint32_t voff = ok && row_ok ? static_cast<uint32_t>((iw * cin + (lslot ^ (R & 7)) * CE) * ESZ) : kOOB;
-    const int soff = row_ok ? ((s_n * H + ih) * W * cin + cb * BK) * ESZ : 0;
+    const uint32_t voff = ok ? static_cast<uint32_t>((iw * cin + (lslot ^ (R & 7)) * CE) * ESZ) : kOOB;
+    const int soff = x_row0 + group_row(gpc, g, cb) * x_rowd + cb * BK * ESZ;
     dma(rs_x, voff, soff, inside ? 2 * AB + buf * SB + j * 1024 : C::SINK);
   };
 
@@ -333,7 +340,7 @@ __device__ __forceinline__ void conv_w1_body(const drnmi_conv_args& p, const W1S
 #pragma unroll
   for (int i = 0; i < AI; ++i) issue_a(1, 1, i);
 #pragma unroll
-  for (int sh = 0; sh < SPS; ++sh) issue_strip(1, 1, sh);
+  for (int sh = 0; sh < SPS; ++sh) issue_strip(ngroups > 1 ? 1 : 0, 1, sh);   // a lone live group: re-fetched, never read
   __builtin_amdgcn_sched_barrier(0);
 
   // K step t = 3 g + KW of strip buffer GP; LAST: the final step (no barrier, reads or DMA after it)
@@ -396,7 +403,7 @@ __device__ __forceinline__ void conv_w1_body(const drnmi_conv_args& p, const W1S
     // weights into stage ST, share set k' of group g' + 1's strip into buffer SGB) are computed in
     // the head groups' gaps and pinned there
     const int gn = KW == 2 ? g + 1 : g;              // g'
-    int sa = 0, ss = 0, s_ok = 0;
+    int sa = 0, ss = 0;
     auto ygroup_head = [&](auto fm_c) __attribute__((always_inline)) {
       constexpr int FMI = decltype(fm_c)::value;
       asm volatile("s_waitcnt lgkmcnt(%0)" :: "n"(FM - 1 - FMI) : "memory");   // a1[FMI] (b1 already)
@@ -405,15 +412,13 @@ __device__ __forceinline__ void conv_w1_body(const drnmi_conv_args& p, const W1S
         constexpr int KK = decltype(k_c)::value;
         if constexpr (!LAST && FMI == 0 && KK == (FN >= 8 ? 1 : 0)) {
           const int kt = t + 2 < nk ? t + 2 : nk - 1;   // past the end: re-fetch into the idle stage
-          const int cb = kt / 9;
-          sa = __builtin_amdgcn_readfirstlane((((kt - cb * 9) << lc) + cb * BK) * ESZ);
+          const int cb = tap_div(rcp, kt);
+          sa = __builtin_amdgcn_readfirstlane(((step_tap(gpc, kt, cb) << lc) + cb * BK) * ESZ);
           __builtin_amdgcn_sched_barrier(0);
         } else if constexpr (!LAST && FMI == 0 && KK == (FN >= 8 ? 3 : 1)) {
           const int g2 = gn + 1 < ngroups ? gn + 1 : ngroups - 1;   // past the end: a buffer never read again
-          const int cb = g2 / 3, kh = g2 - cb * 3;
-          const int ih = s_oh - p.pad + kh * dil;
-          s_ok = __builtin_amdgcn_readfirstlane(static_cast<unsigned>(ih) < static_cast<unsigned>(H) ? 1 : 0);
-          ss = __builtin_amdgcn_readfirstlane(s_ok ? ((s_n * H + ih) * W * cin + cb * BK) * ESZ : 0);
+          const int cb = tap_div(rcp, 3 * g2);
+          ss = __builtin_amdgcn_readfirstlane(x_row0 + group_row(gpc, g2, cb) * x_rowd + cb * BK * ESZ);
           __builtin_amdgcn_sched_barrier(0);
         }
       });
@@ -454,7 +459,7 @@ __device__ __forceinline__ void conv_w1_body(const drnmi_conv_args& p, const W1S
             const bool inside = j < NSP;
             const int R = j * 8 + lrow;
             const int iw = s_ow0 - p.pad + R;
-            const bool ok = inside && s_ok && R < TPX + 2 * dil && static_cast<unsigned>(iw) < static_cast<unsigned>(W);
+            const bool ok = inside && R < TPX + 2 * dil && static_cast<unsigned>(iw) < static_cast<unsigned>(W);
             const uint32_t voff = ok ? static_cast<uint32_t>((iw * cin + (lslot ^ (R & 7)) * CE) * ESZ) : kOOB;
             dma(rs_x, voff, ss, inside ? 2 * AB + SGB * SB + j * 1024 : C::SINK);
           }
@@ -500,7 +505,7 @@ __device__ __forceinline__ void conv_w1_body(const drnmi_conv_args& p, const W1S
   if constexpr (X2) {
     // the fused 1x1 downsample (x2 != NULL: D-22 layer4.0 / 5.0 / 6.0 conv2) as cin2 / 64 more K
     // steps after the taps, in conv_stag_x2's order (so the same bits): step e reads weight
-    // columns 9 cin + 64 e and, as its B strip, pixel R of the tile sampled at stride2 in x2
+    // columns 9 cin + 64 e (a_off holds the window's w_col0) and, as its B strip, pixel R of the tile sampled at stride2 in x2
     // (strip row R, read at tap column 0).  Not pipelined across steps (2-4 per tile): the other
     // workgroup of the CU (conv_w1h) or the partner waves' MFMAs cover the DMA latency
     const int nx2 = p.cin2 / BK;
@@ -510,7 +515,7 @@ __device__ __forceinline__ void conv_w1_body(const drnmi_conv_args& p, const W1S
     auto issue_x2 = [&](int e, int st) __attribute__((always_inline)) {
 #pragma unroll
       for (int i = 0; i < AI; ++i)
-        dma(rs_w, a_off[i & 1], ((i & ~1) * 8 * p.k_pad + 9 * cin + e * BK) * ESZ, st * AB + (wave * AI + i) * 1024);
+        dma(rs_w, a_off[i & 1], ((i & ~1) * 8 * p.k_pad + 9 * cin - w_col0 + e * BK) * ESZ, st * AB + (wave * AI + i) * 1024);
 #pragma unroll
       for (int sh = 0; sh < C::SH; ++sh) {
         const int j = wave + 4 * sh;
