@@ -35,7 +35,7 @@ int32_t drnmi_abi_version(void);
 int64_t drnmi_conv_args_size(void);
 
 enum drnmi_dtype { DRNMI_F32 = 0, DRNMI_BF16 = 1, DRNMI_U8 = 2, DRNMI_I64 = 3, DRNMI_I8 = 4, DRNMI_F32X3 = 5,
-                   DRNMI_F8 = 6, DRNMI_BF16_SP24 = 7 };
+                   DRNMI_F8 = 6, DRNMI_BF16_SP24 = 7, DRNMI_I8_SP24 = 8 };
 /* DRNMI_F32X3 (conv dtype only, the "fp32x" precision mode): x, res and y are fp32 NHWC as in
  * DRNMI_F32, wgt is three bf16 planes [3][cout_pad][k_pad] with w = w1 + w2 + w3 (an exact split
  * of the fp32 weight), and the conv runs fp32-accurate arithmetic on the bf16 MFMA pipe: each
@@ -94,6 +94,30 @@ enum drnmi_dtype { DRNMI_F32 = 0, DRNMI_BF16 = 1, DRNMI_U8 = 2, DRNMI_I64 = 3, D
  *        + 7 (two v_mfma_f32_16x16x32_bf16 B fragments side by side);
  *   D    4 fp32 per lane: rows 4 fq .. 4 fq + 3 of column fr, as the dense 16x16 MFMAs. */
 enum drnmi_sp24_tile { DRNMI_SP24_GATHER = 0, DRNMI_SP24_STRIP = 1 };
+
+/* DRNMI_I8_SP24 (conv dtype only; inference, opt-in: DRNSeg.set_sparse24 at precision "int8"): a DRNMI_I8
+ * launch whose weights are 2:4 along the input channels of a tap (the groups of DRNMI_BF16_SP24), run on
+ * v_smfmac_i32_16x16x128_i8 (csrc/conv_sp24_i8.hip).  Added under ABI version 7: a new enum value and
+ * three new symbols, drnmi_conv_args unchanged, so callers built against the earlier version-7 header
+ * keep working (backward compatible).  The contract is DRNMI_I8's exactly: x and res int8 NHWC, scale
+ * non-NULL, res_scale, ReLU, out_scale, output DRNMI_I8 (NHWC), DRNMI_BF16 or DRNMI_F32 at any strides;
+ * wgt is the blob drnmi_sp24_pack_i8 wrote (0.625 x the dense bytes).  int32 accumulation is exact, so
+ * the output equals the DRNMI_I8 launch on the dense weights bit for bit.
+ *   shapes   cin a power of two >= 128 (a K step is 128 dense channels of one tap), ks 1 or 3 at any
+ *            stride / dilation, any M, cout_pad % 128 == 0 (the 256 x 256 tile when cout_pad % 256 == 0
+ *            and cout > 128, else 128 x 256), k_pad == k == ks*ks*cin.
+ *   refused  DRNMI_ENOTSUP: x2, unit_mask, a NULL scale, cin 64, drnmi_conv_stag_seg; DRNMI_EINVAL: cin
+ *            not a power of two and whatever every launch is refused for.
+ *   tile     enum drnmi_sp24_tile as for DRNMI_BF16_SP24: DRNMI_TILE_AUTO is the gather; DRNMI_SP24_STRIP
+ *            (3x3, stride 1, pad == dil <= 4, wo % 256 == 0, the 256-channel tile) is bit-identical.
+ * Operand map of the instruction, measured on gfx950 (tests/test_gpu_sp24_i8.py::test_operand_map;
+ * lane = 16 fq + fr, D = A x B with A 16 x 128 sparse, B 128 x 16 dense):
+ *   A    16 int8 per lane: row fr, the kept values of dense k 32 fq .. 32 fq + 31; bytes 2 g and 2 g + 1
+ *        are the kept pair of group g (k 32 fq + 4 g .. + 3), lower position first;
+ *   idx  the whole 32-bit register: bits [2 s + 1 : 2 s] = byte s's position in its group; ABID unused;
+ *   B    32 int8 per lane: column fr, bytes 0-15 = k 16 fq .. 16 fq + 15, bytes 16-31 = k 64 + 16 fq ..
+ *        + 15 (two v_mfma_i32_16x16x64_i8 B fragments side by side);
+ *   D    4 int32 per lane: rows 4 fq .. 4 fq + 3 of column fr, as the dense 16x16 MFMAs. */
 
 enum drnmi_status {
   DRNMI_OK = 0,
@@ -347,6 +371,20 @@ int drnmi_sp24_mma_probe(const void* a, const void* b, const uint32_t* idx, floa
  * iters x 8 back-to-back MFMAs on 8 accumulators, operands in registers: sparse != 0 runs
  * v_smfmac_f32_16x16x64_bf16, else v_mfma_f32_16x16x32_bf16.  sink: blocks x 256 floats. */
 int drnmi_sp24_issue_probe(int32_t sparse, int32_t iters, int32_t blocks, float* sink, void* stream);
+
+/* 2:4 packing for DRNMI_I8_SP24 (csrc/conv_sp24_i8.hip), the rules of drnmi_sp24_pack on int8.  dense_i8:
+ * packed int8 weights [rows_pad][k_pad] (rows_pad % 32 == 0, k_pad % 128 == 0, device memory); out: device
+ * buffer of drnmi_sp24_pack_i8_bytes(rows_pad, k_pad) = rows_pad * k_pad * 5 / 8 bytes (-1 for other
+ * sizes: half the values plus 2 bits per kept value), 16-B aligned, layout private to the kernel.  A zero
+ * is the value 0; groups fill up from position 3 downwards; *violations (device int32, NULL-able, reset by
+ * every call) counts the groups with more than two non-zeros, and a blob with violations must not be
+ * launched.  Arguments are refused (DRNMI_EINVAL) before any HIP call.
+ * drnmi_sp24_mma_probe_i8: one v_smfmac_i32_16x16x128_i8 on one wave with a zero accumulator, for the
+ * operand-map test: a [64][16] int8, b [64][32] int8, idx [64] words, d [64][4] int32 per lane. */
+int64_t drnmi_sp24_pack_i8_bytes(int32_t rows_pad, int32_t k_pad);
+int drnmi_sp24_pack_i8(const void* dense_i8, int32_t rows_pad, int32_t k_pad, void* out, int32_t* violations,
+                       void* stream);
+int drnmi_sp24_mma_probe_i8(const void* a, const void* b, const uint32_t* idx, int32_t* d, void* stream);
 
 /* W8A8 helpers (BASELINE config C5; csrc/quant.hip).  The reference has no quantisation code
  * (SURVEY.md C5 row): the scheme is ours.  Activations are per-tensor symmetric int8.

@@ -200,6 +200,20 @@ ConvRoute sp24_route(const drnmi_conv_args& p) {
   return take(sp24_kernel(tile128, p.ks));
 }
 
+// --- the 2:4 weight-sparse int8 tiles (DRNMI_I8_SP24, conv_sp24_i8.hip): sp24_route's decisions on the
+// int8 contract (a non-NULL scale, the 8-bit epilogue).  Auto is the gather; the strip-staged form is a
+// forced variant (profiles/sp24_i8/README.txt)
+ConvRoute sp24_i8_route(const drnmi_conv_args& p) {
+  if (p.tile != DRNMI_TILE_AUTO && p.tile != DRNMI_SP24_GATHER && p.tile != DRNMI_SP24_STRIP) return refuse(DRNMI_EINVAL);
+  if (!sp24_i8_conv_supported(p)) return refuse(DRNMI_ENOTSUP);
+  const bool tile128 = p.cout_pad % 256 != 0 || p.cout <= 128;
+  const bool strip = !tile128 && strip_ok(p);
+  if (p.tile == DRNMI_SP24_STRIP && !strip) return refuse(DRNMI_ENOTSUP);
+  if (!rows_exist(p, tile128 ? 128 : 256)) return refuse(DRNMI_EINVAL);
+  if (p.tile == DRNMI_SP24_STRIP) return take(sp24_i8_strip_kernel());
+  return take(sp24_i8_kernel(tile128, p.ks));
+}
+
 // --- conv_x6.  A drnmi_conv_args.tile >= 0 forces variant tile % 6 and, when tile >= 6, tile / 6
 // split-K partitions (tests, micro-benchmarks; split-K only with a caller workspace).
 // 128-channel layers take the two-per-CU 128 x 128 tile: D-22 layer4's five launches 1631-1649 ->
@@ -318,7 +332,7 @@ ConvRoute conv_route(const drnmi_conv_args& p) {
                       !x6_conv_supported(p)))
     return refuse(DRNMI_EINVAL);
   if (p.algo == DRNMI_ALGO_PATCH) {
-    if (p.dtype == DRNMI_BF16_SP24) return refuse(DRNMI_EINVAL);
+    if (p.dtype == DRNMI_BF16_SP24 || p.dtype == DRNMI_I8_SP24) return refuse(DRNMI_EINVAL);
     if (p.x2 != nullptr) return refuse(DRNMI_ENOTSUP);     // fused second input: LDS-DMA kernels only
     if (p.n <= 0 || p.h <= 0 || p.w <= 0 || p.cout > p.cout_pad || !conv_geometry(p)) return refuse(DRNMI_EINVAL);
     return take(patch_kernel(p));
@@ -326,6 +340,8 @@ ConvRoute conv_route(const drnmi_conv_args& p) {
   if (p.algo != DRNMI_ALGO_IGEMM || p.src_u8) return refuse(DRNMI_EINVAL);
   // 2:4 sparse: no fused second input, unit mask or unfolded scale
   if (p.dtype == DRNMI_BF16_SP24 && (p.x2 != nullptr || p.unit_mask != nullptr || p.scale != nullptr)) return refuse(DRNMI_ENOTSUP);
+  // 2:4 sparse int8: no fused second input or unit mask; the int8 contract's scale
+  if (p.dtype == DRNMI_I8_SP24 && (p.x2 != nullptr || p.unit_mask != nullptr || p.scale == nullptr)) return refuse(DRNMI_ENOTSUP);
   const bool pow2 = p.cin >= 8 && (p.cin & (p.cin - 1)) == 0;
   if (!pow2 || p.n <= 0 || p.h <= 0 || p.w <= 0 || p.ho <= 0 || p.wo <= 0) return refuse(DRNMI_EINVAL);
   if (p.cout <= 0 || p.cout > p.cout_pad || p.k != p.ks * p.ks * p.cin + (p.x2 != nullptr ? p.cin2 : 0))
@@ -333,6 +349,8 @@ ConvRoute conv_route(const drnmi_conv_args& p) {
   if (p.k_pad < p.k || p.k_pad % kBK != 0 || p.stride <= 0 || p.dil <= 0 || p.pad < 0) return refuse(DRNMI_EINVAL);
   if (p.dtype == DRNMI_I8 || p.dtype == DRNMI_F8) {       // 8-bit: the code's own type, bf16 or fp32
     if (p.out_dtype != p.dtype && p.out_dtype != DRNMI_BF16 && p.out_dtype != DRNMI_F32) return refuse(DRNMI_EINVAL);
+  } else if (p.dtype == DRNMI_I8_SP24) {                  // the int8 route's outputs
+    if (p.out_dtype != DRNMI_I8 && p.out_dtype != DRNMI_BF16 && p.out_dtype != DRNMI_F32) return refuse(DRNMI_EINVAL);
   } else if (p.dtype == DRNMI_F32X3) {
     if (p.out_dtype != DRNMI_F32) return refuse(DRNMI_EINVAL);
   } else if ((p.dtype != DRNMI_BF16 && p.dtype != DRNMI_F32 && p.dtype != DRNMI_BF16_SP24) ||
@@ -346,6 +364,7 @@ ConvRoute conv_route(const drnmi_conv_args& p) {
   if (p.dtype == DRNMI_I8 || p.dtype == DRNMI_F8) return q8_route(p);       // 8-bit: one kernel family
   if (p.dtype == DRNMI_F32X3) return x6_route(p);
   if (p.dtype == DRNMI_BF16_SP24) return sp24_route(p);
+  if (p.dtype == DRNMI_I8_SP24) return sp24_i8_route(p);
   if (p.tile >= DRNMI_TILE_DMA128 || (p.tile < 0 && (big_conv_supported(p) || halo_conv_supported(p)))) return big_route(p);
   if (p.x2 != nullptr) return refuse(DRNMI_ENOTSUP);          // fused second input: LDS-DMA kernels only
   const int tile = p.tile < 0 ? auto_tile(p.cout) : p.tile;
@@ -368,7 +387,7 @@ struct SegRoute {
 // staggered one (the same partial logits, bit for bit: the bit-identity test).
 SegRoute seg_route(const drnmi_conv_args& p) {
   if (p.algo != DRNMI_ALGO_IGEMM || p.src_u8) return {DRNMI_EINVAL, nullptr};
-  if (p.dtype == DRNMI_F8 || p.dtype == DRNMI_BF16_SP24) return {DRNMI_ENOTSUP, nullptr};   // no seg-fused fp8 / 2:4 form
+  if (p.dtype == DRNMI_F8 || p.dtype == DRNMI_BF16_SP24 || p.dtype == DRNMI_I8_SP24) return {DRNMI_ENOTSUP, nullptr};   // no seg-fused fp8 / 2:4 form
   const bool i8 = p.dtype == DRNMI_I8;
   // int8 nets: the conv's int8 output (out_dtype I8, quantised with out_scale) feeds int8 seg
   // weights; int32 partials

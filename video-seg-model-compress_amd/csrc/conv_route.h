@@ -93,6 +93,10 @@ bool sp24_conv_supported(const drnmi_conv_args& p);
 bool big_body_shape_ok(const drnmi_conv_args& p, int min_cin);
 const ConvKernel* sp24_kernel(bool tile128, int ks);
 const ConvKernel* sp24_strip_kernel();           // 3x3 stride 1, wo % 256 == 0, the 256 x 256 tile (strip_ok)
+// conv_sp24_i8.hip: the 2:4 weight-sparse int8 tiles (dtype DRNMI_I8_SP24), cin >= 128, the same two tiles
+bool sp24_i8_conv_supported(const drnmi_conv_args& p);
+const ConvKernel* sp24_i8_kernel(bool tile128, int ks);
+const ConvKernel* sp24_i8_strip_kernel();        // strip_ok on the 256 x 256 tile, as sp24_strip_kernel
 
 // conv_halo.hip: halo-patch 3x3 stride-1 conv, cin / cout 64 or 128
 bool halo_conv_supported(const drnmi_conv_args& p);

@@ -12,6 +12,7 @@ from .build import LIB_PATH
 
 DRNMI_F32, DRNMI_BF16, DRNMI_U8, DRNMI_I64, DRNMI_I8, DRNMI_F32X3, DRNMI_F8 = 0, 1, 2, 3, 4, 5, 6
 DRNMI_BF16_SP24 = 7
+DRNMI_I8_SP24 = 8
 SP24_GATHER, SP24_STRIP = 0, 1          # include/drnmi.h enum drnmi_sp24_tile
 ALGO_IGEMM, ALGO_PATCH = 0, 1
 # include/drnmi.h enum drnmi_tile: the ids tests and micro-benchmarks force
@@ -140,6 +141,9 @@ SIGNATURES = {
     "drnmi_sp24_pack": (ctypes.c_int, [_VP, _I32, _I32, _VP, _VP, _VP]),
     "drnmi_sp24_mma_probe": (ctypes.c_int, [_VP, _VP, _VP, _VP, _I32, _VP]),
     "drnmi_sp24_issue_probe": (ctypes.c_int, [_I32, _I32, _I32, _VP, _VP]),
+    "drnmi_sp24_pack_i8_bytes": (ctypes.c_int64, [_I32, _I32]),
+    "drnmi_sp24_pack_i8": (ctypes.c_int, [_VP, _I32, _I32, _VP, _VP, _VP]),
+    "drnmi_sp24_mma_probe_i8": (ctypes.c_int, [_VP, _VP, _VP, _VP, _VP]),
     "drnmi_quantize_i8": (ctypes.c_int, [_VP, _I32, _VP, _I64, _F32, _VP]),
     "drnmi_quantize_f8": (ctypes.c_int, [_VP, _I32, _I64, _F32, _VP, _VP]),
     "drnmi_absmax": (ctypes.c_int, [_VP, _I32, _I64, _VP, _VP]),

@@ -31,7 +31,9 @@ EXTRA = {"front.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"], "block64.hip": ["-
          "conv_s2row.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"],
          # conv_sp24.hip: its dense issue-rate loop next to the sparse one (v_smfmac writes VGPRs only) without
          # accumulator copies between AGPRs and VGPRs in the loop
-         "conv_sp24.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"]}
+         "conv_sp24.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"],
+         # conv_sp24_i8.hip: the sparse int8 MFMA accumulates in VGPRs too
+         "conv_sp24_i8.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"]}
 
 
 def sources():

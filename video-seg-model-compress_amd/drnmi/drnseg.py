@@ -404,8 +404,14 @@ class DRNSeg(nn.Module):
         """bf16 inference: run every conv whose weights are 2:4 sparse along the input channels (at most
         two non-zeros in every four consecutive channels of a tap: NMPruner) and that has the sparse
         kernel's shape (cin >= 64, ks 1 / 3, no folded downsample) on the structured-sparse MFMA
-        (include/drnmi.h DRNMI_BF16_SP24).  Layers with a violating group stay dense; other precisions
-        are untouched.  Opt-in, off by default; takes effect at the next pack."""
+        (include/drnmi.h DRNMI_BF16_SP24).  Layers with a violating group stay dense.
+        int8 inference: the int8 launches with cin >= 128 whose int8 weights are 2:4 (a masked fp32 zero
+        quantises to 0) run on the sparse int8 MFMA (DRNMI_I8_SP24) where that measured faster than the
+        dense int8 tile (engine.SP24_I8_SHAPES; engine.SP24_I8_EVERY routes every eligible layer).
+        int32 sums are exact, so every sparse int8 launch is bit-identical to the dense one it
+        replaces: the switch changes no output of an int8 model, only launch names, weight bytes
+        (0.625 x) and time.  fp8, fp32 and fp32x are untouched.
+        Opt-in, off by default; takes effect at the next pack."""
         self.sparse24 = bool(enabled)
         for pk in self._packed.values():
             pk.sparse24 = self.sparse24
@@ -414,8 +420,8 @@ class DRNSeg(nn.Module):
 
     def sparse24_layers(self, device=None) -> list:
         """Names of the conv nodes the current precision's pack launches on the 2:4 sparse kernel
-        (packs first if needed; [] with the switch off or outside bf16)."""
-        if not self.sparse24 or self.precision != "bf16":
+        (packs first if needed; [] with the switch off or outside bf16 / int8)."""
+        if not self.sparse24 or self.precision not in ("bf16", "int8"):
             return []
         device = torch.device(device or next(self.parameters()).device)
         return self._packed_net(device).sparse24_layers()

@@ -56,6 +56,22 @@ INT8_MIN_COUT = 256
 # int8 128 x 128 tile (conv_w1h_i8_kernel, odd tap-group counts) serves them (INT8_LAYER4 = False
 # keeps them bf16)
 INT8_LAYER4 = True
+# 2:4 sparse int8 (set_sparse24 at precision "int8", include/drnmi.h DRNMI_I8_SP24): the launch shapes
+# (cin_stride, cout, ks, stride, dilation) that measured faster on conv_sp24_i8_kernel than on the dense
+# int8 tile they replace, by more than the spread of the dense repeats, in both recorded runs
+# (profiles/sp24_i8/README.txt): D-22's layer5, layer6 and layer7 launches.  Not listed: the 128 -> 128
+# launches and the seg 1x1 (slower sparse), and layer8's 512 -> 512 dilation-1 launch, which gains alone
+# but would give up the seg-fused launch for no measured gain of the step.
+# SP24_I8_EVERY routes every eligible layer sparse (tests, A/B runs): the outputs are the same bits.
+SP24_I8_SHAPES = frozenset({(128, 256, 3, 1, 2), (128, 256, 1, 1, 1), (256, 256, 3, 1, 2), (256, 512, 3, 1, 4),
+                            (256, 512, 1, 1, 1), (512, 512, 3, 1, 4), (512, 512, 3, 1, 2)})
+SP24_I8_EVERY = False
+
+
+def _sp24_i8_gains(nd: "ConvNode") -> bool:
+    c = nd.conv
+    return SP24_I8_EVERY or (nd.cin_stride, c.out_channels, c.kernel_size[0], c.stride[0], c.dilation[0]) in SP24_I8_SHAPES
+
 
 # (cin_stride, cout, ks, stride, dil) served by the LDS-patch kernel (bf16 only; include/drnmi.h)
 # (32 -> 64 stride 2 runs faster on the K-32 LDS-DMA implicit GEMM: 67 vs 108 us per 4 frames)
@@ -367,14 +383,28 @@ class PackedNet:
         """bf16 with sparse24 on: every conv that has the sparse kernel's shape (asked of the library's
         own route), a folded BN scale, no folded downsample on either side, no part in a fused block
         and not one group of four input channels with more than two non-zeros is packed 2:4
-        (include/drnmi.h drnmi_sp24_pack) and launched as DRNMI_BF16_SP24.  Everything else stays dense."""
+        (include/drnmi.h drnmi_sp24_pack) and launched as DRNMI_BF16_SP24.  Everything else stays dense.
+        int8 with sparse24 on: the same for the int8 wpk of every int8 node the sparse int8 route accepts
+        (cin >= 128) among the shapes that gain (_sp24_i8_gains), launched as DRNMI_I8_SP24: a masked fp32
+        zero quantises to 0, so a 2:4 fp32 mask is still 2:4 after _pack_q8.  The bf16 nodes of an int8
+        net and every other precision stay as they are."""
         for nd in self.graph.nodes:
             nd.wsp = None
-        if not self.sparse24 or self.precision != "bf16":
+        if not self.sparse24 or self.precision not in ("bf16", "int8"):
             return
         lib = _lib.load()
-        in_block = {j for pairs in self.block_pairs.values() for i in pairs for j in (i, i + 1)}
         cnt = torch.zeros(1, dtype=torch.int32, device=self.device)
+        if self.precision == "int8":
+            for i in self.sp24_i8_candidates():
+                nd = self.graph.nodes[i]
+                rows, kp = nd.wpk.shape
+                blob = torch.empty(int(lib.drnmi_sp24_pack_i8_bytes(rows, kp)), dtype=torch.uint8, device=self.device)
+                _lib.check(lib.drnmi_sp24_pack_i8(nd.wpk.data_ptr(), rows, kp, blob.data_ptr(), cnt.data_ptr(),
+                                                  ctypes.c_void_p(_lib.stream_ptr(self.device))), f"sp24_pack_i8 {nd.name}")
+                if int(cnt.item()) == 0:
+                    nd.wsp = blob
+            return
+        in_block = {j for pairs in self.block_pairs.values() for i in pairs for j in (i, i + 1)}
         for i, nd in enumerate(self.graph.nodes):
             if not nd.scale_folded or nd.i8 or nd.x6 or nd.fused or nd.fused_into >= 0 or i in in_block or \
                     nd.unit_mask is not None or nd.cin_stride < 64:
@@ -391,6 +421,22 @@ class PackedNet:
                                            ctypes.c_void_p(_lib.stream_ptr(self.device))), f"sp24_pack {nd.name}")
             if int(cnt.item()) == 0:            # read back once per (re)pack, never in the launch loop
                 nd.wsp = blob
+
+    def sp24_i8_candidates(self) -> list:
+        """Indices of the int8 nodes a 2:4 pack is tried on (host decisions only): int8 launches with
+        cin >= 128 among the shapes that gain (_sp24_i8_gains) that the library's DRNMI_I8_SP24 route accepts."""
+        lib = _lib.load()
+        out = []
+        for i, nd in enumerate(self.graph.nodes):
+            if self.qcode != _lib.DRNMI_I8 or not nd.i8 or nd.cin_stride < 128 or not _sp24_i8_gains(nd):
+                continue
+            a = _probe_args(nd, nd.cin_stride, nd.k, nd.k_pad)
+            a.dtype, a.scale, a.out_dtype = _lib.DRNMI_I8_SP24, 1, self.value_code(nd.dst)    # (scale: presence only)
+            if nd.out_fp32_nchw:
+                a.out_dtype, a.y_sp, a.y_sc = _lib.DRNMI_F32, 1, a.ho * a.wo
+            if lib.drnmi_conv_kernel_name(ctypes.byref(a)) is not None:
+                out.append(i)
+        return out
 
     def sparse24_layers(self) -> list:
         """Names of the nodes launched on the 2:4 sparse kernel."""
@@ -839,7 +885,7 @@ class Plan:
         name = lib.drnmi_conv_kernel_name(ctypes.byref(a))   # (routing does not read a.y)
         if name is None or not name.decode().startswith(("conv_big_kernel", "conv_i8_kernel", "conv_i8_occ2_kernel",
                                                         "conv_x6_kernel", "conv_f8_kernel", "conv_f8_occ2_kernel",
-                                                        "conv_sp24_kernel")):
+                                                        "conv_sp24_kernel", "conv_sp24_i8_kernel")):
             return
         if "logits_nhwc" not in self.bufs:      # only plans whose seg conv writes the NHWC rows
             self.bufs["logits_nhwc"] = torch.empty(self.n * lh * lw * cs, dtype=torch.float32, device=pk.device)
@@ -976,7 +1022,7 @@ class Plan:
         a.res_scale, a.out_scale = nd.res_scale, nd.out_scale
         a.unit_mask = nd.unit_mask.data_ptr() if nd.unit_mask is not None else None
         if nd.wsp is not None:                    # 2:4 sparse launch (never a node with a folded downsample)
-            a.wgt, a.dtype = nd.wsp.data_ptr(), _lib.DRNMI_BF16_SP24
+            a.wgt, a.dtype = nd.wsp.data_ptr(), (_lib.DRNMI_I8_SP24 if nd.i8 else _lib.DRNMI_BF16_SP24)
         if fused:
             f = fused
             a.wgt, a.shift, a.res = f["wpk"].data_ptr(), f["shift"].data_ptr(), None

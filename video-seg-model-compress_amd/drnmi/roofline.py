@@ -19,6 +19,8 @@ MFMA_PEAK = {"bf16": 2.5e15, "fp32": 157.3e12, "int8": 5.0e15, "fp32x": 2.5e15 /
 
 def kernel_peak(kernel_name: str, base: str) -> float:
     """MFMA peak of the arithmetic a kernel (named as rocprofv3 names it) runs."""
+    if kernel_name.startswith("conv_sp24_i8"):    # 2:4 sparse int8: dense-equivalent OPs against the 2x sparse peak
+        return 2 * MFMA_PEAK["int8"]
     # conv_i8_*, conv_w1_i8_*, conv_w1h_i8_*; conv_f8_*: e4m3 on the K-128 f8f6f4 MFMA runs at the same 8-bit peak
     if kernel_name.startswith(("conv_i8", "conv_f8")) or "_i8_" in kernel_name:
         return MFMA_PEAK["int8"]
