@@ -10,11 +10,16 @@ throughout (the reference's arithmetic).  Synthetic normalised inputs and labels
 resident in HBM; hash-initialised weights.
 
     python bench_finetune.py [--steps K] [--warmup W] [--batch B] [--gpus N]
+    python bench_finetune.py --distill [--teacher-precision {fp32,fp32x,bf16}]
     torchrun --nproc-per-node N bench_finetune.py --gpus N
 
 `--gpus N` outside torchrun spawns the N rank processes itself (bench.py's launcher); under
 torchrun a WORLD_SIZE different from --gpus is refused.  `--stub-step` (test hook, no GPU) runs
 a CPU stand-in step over gloo through the same launcher, seeding and max-over-ranks timing.
+
+`--distill` (opt-in) adds the reference's knowledge distillation (rmbsnn_main.py --mc-kd) to the
+step: a frozen dense teacher of the same arch runs its inference forward on the batch and the
+criterion becomes drnmi.train.DistillationLoss(0.5, 0.5, T=2); the JSON line gains a "distill" object.
 
 Prints ONE JSON line (rank 0).  Not the driver's headline bench (bench.py is).
 """
@@ -45,6 +50,11 @@ def parse(argv=None):
     ap.add_argument("--precision", default="fp32", choices=["fp32", "fp32x"],
                     help="fp32x: the convs (forward, data and weight gradients) on the fp32-accurate "
                          "split-bf16 kernels (conv_x6, X6 patch kernels, wgrad_f32x3); BN and the head stay exact fp32")
+    ap.add_argument("--distill", action="store_true",
+                    help="knowledge distillation: a frozen dense teacher of --arch (synthetic weights, another seed) "
+                         "runs inside the timed step and the criterion is DistillationLoss (CE + KL to the teacher)")
+    ap.add_argument("--teacher-precision", default="bf16", choices=["fp32", "fp32x", "bf16"],
+                    help="inference precision of the --distill teacher")
     ap.add_argument("--cpu-seconds", type=float, default=20.0)
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--stub-step", action="store_true",
@@ -219,6 +229,13 @@ def main(argv=None):
     net = DistributedDataParallel(m, device_ids=[local]) if world > 1 else m
     opt = SGD(m.optim_parameters(), 0.01, momentum=0.9, weight_decay=1e-4, pruner=pr, model=m if pr else None)
     crit = CrossEntropyLoss(ignore_index=255)
+    teacher = None
+    if args.distill:
+        from drnmi.train import DistillationLoss, teacher_logprobs
+        teacher = DRNSeg(args.arch, 19, pretrained=False)
+        teacher.load_state_dict(synth_state_dict(teacher, 1))
+        teacher = teacher.to(dev).eval().set_precision(args.teacher_precision)
+        crit = DistillationLoss(0.5, 0.5, 2.0, ignore_index=255)
     B, H, W = args.batch, args.height, args.width
     g = torch.Generator(device=dev).manual_seed(2000 + rank)
     x = torch.randn(B, 3, H, W, device=dev, generator=g)
@@ -227,7 +244,7 @@ def main(argv=None):
 
     def step():
         out = net(x)[0]
-        loss = crit(out, t)
+        loss = crit(out, t) if teacher is None else crit(out, teacher_logprobs(teacher, x), t)
         opt.zero_grad()
         loss.backward()
         opt.step()
@@ -279,6 +296,12 @@ def main(argv=None):
                      "peak_note": "conv time at each conv's kernel peak (step_t_star): frac = T* / T"},
         "final_loss": float(loss.detach()),
     }
+    if args.distill:
+        out["distill"] = {"teacher": f"{args.arch}, dense, frozen (eval mode), synthetic weights seed 1",
+                          "teacher_precision": args.teacher_precision, "student_wt": crit.student_wt,
+                          "distill_wt": crit.distill_wt, "temperature": crit.temperature,
+                          "kd_reduction": crit.kd_reduction, "final_ce": float(crit.ce), "final_kd": float(crit.kd),
+                          "note": "the teacher's forward and the CE + KL criterion run inside the timed step"}
     if rank == 0 and world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(args, args.cpu_seconds)
     if rank == 0:

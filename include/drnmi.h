@@ -770,6 +770,31 @@ int drnmi_ce_loss_bwd_f32(const float* logprobs, const int64_t* target, int32_t 
                           int64_t ignore_index, const float* dloss, const float* count,
                           float* g_logprobs, void* stream);
 
+/* Distillation loss (added under ABI version 7: new functions only): the CrossEntropyLoss above on
+ * the student's log-probs plus the KL divergence to a teacher's log-probs at a temperature, in one
+ * pass over both [n][c][hw] fp32 tensors.  Per pixel, in fp32, with a = s / T and b = t / T:
+ *   logp = a - lse(a), logq = b - lse(b), q = exp(logq), kd_i = sum_k q[k] * (logq[k] - logp[k])
+ * over EVERY pixel (labelled or not), and ce_i = lse(s) - s[target] over target != ignore_index.
+ *   CE = sum ce_i / count;  KD = sum kd_i / D, D = n * hw, or n with batchmean != 0 (F.kl_div's
+ *   size_average=False / shape[0]);  loss = student_wt * CE + distill_wt * KD.  No T^2 factor.
+ * out3 = {loss, CE, KD}, count[0] = number of labelled pixels: device scalars.  An out-of-range
+ * target other than ignore_index makes loss and CE NaN.  Bit-equal s and t give KD == 0 exactly.
+ * fp64 block partials in a fixed order: bit-reproducible.  ws of drnmi_distill_workspace_bytes.
+ * Asynchronous on the stream, no allocation, no synchronisation.  DRNMI_EINVAL before any HIP call:
+ * a NULL pointer, a non-positive size, a temperature not finite and > 0, a weight negative or not
+ * finite. */
+int64_t drnmi_distill_workspace_bytes(void);
+int drnmi_distill_loss_f32(const float* student_lp, const float* teacher_lp, const int64_t* target,
+                           int32_t n, int32_t c, int64_t hw, int64_t ignore_index, float student_wt,
+                           float distill_wt, float temperature, int32_t batchmean, float* out3,
+                           float* count, void* ws, void* stream);
+/* g_student_lp = dloss[0] * (student_wt / count[0] * (softmax(s) - onehot(target)) on labelled pixels
+ *                            + distill_wt / (D * T) * (exp(logp) - q)); the teacher gets no gradient. */
+int drnmi_distill_loss_bwd_f32(const float* student_lp, const float* teacher_lp, const int64_t* target,
+                               int32_t n, int32_t c, int64_t hw, int64_t ignore_index, float student_wt,
+                               float distill_wt, float temperature, int32_t batchmean, const float* dloss,
+                               const float* count, float* g_student_lp, void* stream);
+
 /* Multi-tensor torch.optim.SGD step (semantic_seg.py:963-966, torch semantics: d = g + wd*w;
  * buf = first ? d : momentum*buf + (1-dampening)*d; d = nesterov ? d + momentum*buf : buf;
  * w -= lr*d) with the pruner mask fused: w *= bit (mask_bits[t] NULL-able; NULL array = none).

@@ -16,11 +16,15 @@
 //   zero_insert        dy of a stride-s conv spread onto the input grid (dgrad input)
 //   up8_lsm_bwd        LogSoftmax backward + transpose of the fixed bilinear up-conv
 //   ce_loss            CrossEntropyLoss(ignore_index) forward / backward on log-probs
+//   distill_loss       that CE plus the KL divergence to a teacher's log-probs at a temperature
+//                      (knowledge distillation), forward / backward in one pass each
 //   sgd_step           torch.optim.SGD step (momentum, dampening, wd, nesterov) with the
 //                      pruner mask (bit-packed) applied in the same pass
 //
 // Every reduction accumulates in fp64 in a fixed order (no atomics), so results are
 // bit-reproducible run to run.
+#include <cmath>
+
 #include "common.h"
 
 namespace drnmi {
@@ -942,6 +946,202 @@ ce_bwd_kernel(const float* __restrict__ lp, const int64_t* __restrict__ tgt, int
   }
 }
 
+// ------------------------------------------------------------------ distillation (CE + KL to a teacher)
+// The reference's --mc-kd loss (rmbsnn_main.py:192-243) for the segmentation loop, on student and
+// teacher log-probs s, t [n][c][hw]: per pixel, with a = s / T and b = t / T,
+//   kd = sum_k q[k] * (logq[k] - logp[k]),  logp = a - lse(a), logq = b - lse(b), q = exp(logq)
+// over every pixel, and ce_pixel's lse(s) - s[target] over the labelled ones; one pass over both
+// tensors.  No T^2 factor (the reference has none).
+
+// one pixel's class values: NC > 0 held in registers (each plane read once), NC = 0 read from the
+// planes at every use (any c)
+template <int NC>
+struct KdRow {
+  float x[NC > 0 ? NC : 1];
+  const float* v;
+  int64_t hw;
+  __device__ __forceinline__ float operator[](int k) const {
+    if constexpr (NC > 0) return x[k];
+    else return v[k * hw];
+  }
+};
+
+// lse of r[k] * invT.  The student's and the teacher's rows both go through this function and kd_logp,
+// with nothing contracted, so bit-equal rows give bit-equal log-probabilities (kd == 0, p - q == 0).
+// invT = 1 is ce_pixel's lse: the same operations in the same order.
+template <int NC>
+__device__ __forceinline__ float kd_lse(const KdRow<NC>& r, int c, float invT) {
+#pragma clang fp contract(off)
+  const int nc = NC > 0 ? NC : c;
+  float mx = -INFINITY;
+#pragma unroll
+  for (int k = 0; k < nc; ++k) mx = fmaxf(mx, r[k] * invT);
+  float se = 0.f;
+#pragma unroll
+  for (int k = 0; k < nc; ++k) se += expf(r[k] * invT - mx);
+  return mx + logf(se);
+}
+
+template <int NC>
+__device__ __forceinline__ float kd_logp(const KdRow<NC>& r, int k, float invT, float lse) {
+#pragma clang fp contract(off)
+  return r[k] * invT - lse;
+}
+
+// r[t], 0 <= t < c, without indexing the registers (ce_pixel's selection).  The row by value: through a
+// reference the compiler turns the selects into an indexed load and the row moves to scratch memory
+template <int NC>
+__device__ __forceinline__ float kd_pick(const KdRow<NC> r, int64_t t) {
+  if constexpr (NC > 0) {
+    float xt = r.x[0];
+#pragma unroll
+    for (int k = 1; k < NC; ++k) xt = k == t ? r.x[k] : xt;
+    return xt;
+  } else {
+    return r.v[t * r.hw];
+  }
+}
+
+// PX consecutive pixels of image b from pixel p on: PX = 4 as one 16-B piece per plane (NC > 0, hw % 4 == 0)
+template <int NC, int PX>
+__device__ __forceinline__ void kd_load(const float* __restrict__ v, int64_t hw, KdRow<NC> (&r)[PX]) {
+  static_assert(PX == 1 || (PX == 4 && NC > 0), "the 16-B form holds its classes in registers");
+  if constexpr (PX == 4) {
+#pragma unroll
+    for (int k = 0; k < NC; ++k) {
+      const float4 a = *reinterpret_cast<const float4*>(v + k * hw);
+      r[0].x[k] = a.x;
+      r[1].x[k] = a.y;
+      r[2].x[k] = a.z;
+      r[3].x[k] = a.w;
+    }
+  } else if constexpr (NC > 0) {
+#pragma unroll
+    for (int k = 0; k < NC; ++k) r[0].x[k] = v[k * hw];
+  } else {
+    r[0].v = v;
+    r[0].hw = hw;
+  }
+}
+
+// block partials (ce sum, count, bad targets, kd sum) in fp64, fixed order; PX pixels per thread,
+// consecutive lanes on consecutive pixels (PX = 4: consecutive 16-B pieces) of a plane.  Two waves per
+// SIMD (the 16-B form holds 152 class values per lane): one wave's loads run under the other's expf
+template <int NC, int PX>
+__global__ void __launch_bounds__(kThreads, 2)
+distill_fwd_kernel(const float* __restrict__ slp, const float* __restrict__ tlp, const int64_t* __restrict__ tgt,
+                   int nimg, int c, int64_t hw, int64_t ignore, float invT, double* __restrict__ ws) {
+  const int nc = NC > 0 ? NC : c;
+  const int64_t hwq = hw / PX;
+  const int64_t total = static_cast<int64_t>(nimg) * hwq;
+  double sce = 0, cnt = 0, bad = 0, skd = 0;
+  for (int64_t i = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x; i < total;
+       i += static_cast<int64_t>(gridDim.x) * blockDim.x) {
+    const int64_t b = i / hwq, p = (i - b * hwq) * PX;
+    KdRow<NC> s[PX], t[PX];
+    kd_load<NC, PX>(slp + b * c * hw + p, hw, s);
+    kd_load<NC, PX>(tlp + b * c * hw + p, hw, t);
+#pragma unroll
+    for (int e = 0; e < PX; ++e) {
+      const float la = kd_lse(s[e], c, invT), lb = kd_lse(t[e], c, invT);
+      float kd = 0.f;
+#pragma unroll
+      for (int k = 0; k < nc; ++k) {
+        const float lq = kd_logp(t[e], k, invT, lb);
+        kd += expf(lq) * (lq - kd_logp(s[e], k, invT, la));
+      }
+      skd += static_cast<double>(kd);
+      const int64_t tg = tgt[b * hw + p + e];
+      if (tg == ignore) continue;
+      if (tg < 0 || tg >= c) { bad += 1; continue; }
+      sce += static_cast<double>(kd_lse(s[e], c, 1.f) - kd_pick(s[e], tg));
+      cnt += 1;
+    }
+  }
+  __shared__ double sh[4][kThreads];
+  sh[0][threadIdx.x] = sce;
+  sh[1][threadIdx.x] = cnt;
+  sh[2][threadIdx.x] = bad;
+  sh[3][threadIdx.x] = skd;
+  __syncthreads();
+  for (int o = kThreads / 2; o > 0; o >>= 1) {
+    if (threadIdx.x < o) {
+#pragma unroll
+      for (int j = 0; j < 4; ++j) sh[j][threadIdx.x] += sh[j][threadIdx.x + o];
+    }
+    __syncthreads();
+  }
+  if (threadIdx.x < 4) ws[threadIdx.x * kCeBlocks + blockIdx.x] = sh[threadIdx.x][0];
+}
+
+// the block partials summed in block order by one thread, as ce_final_kernel; out3 = loss, ce, kd
+__global__ void __launch_bounds__(64)
+distill_final_kernel(const double* __restrict__ ws, int blocks, double kd_div, float student_wt, float distill_wt,
+                     float* __restrict__ out3, float* __restrict__ count) {
+  __shared__ double sh[4 * kCeBlocks];
+  for (int e = threadIdx.x; e < 4 * kCeBlocks; e += 64) sh[e] = ws[e];
+  __syncthreads();
+  if (threadIdx.x != 0 || blockIdx.x != 0) return;
+  double s = 0, cnt = 0, bad = 0, skd = 0;
+  for (int b = 0; b < blocks; ++b) {
+    s += sh[b];
+    cnt += sh[kCeBlocks + b];
+    bad += sh[2 * kCeBlocks + b];
+    skd += sh[3 * kCeBlocks + b];
+  }
+  const float ce = bad > 0 ? __builtin_nanf("") : static_cast<float>(s / cnt);
+  const float kd = static_cast<float>(skd / kd_div);
+  out3[0] = student_wt * ce + distill_wt * kd;
+  out3[1] = ce;
+  out3[2] = kd;
+  count[0] = static_cast<float>(cnt);
+}
+
+// g_s[k] = dloss * (student_wt / count * (softmax(s)[k] - onehot[k]) on labelled pixels
+//                   + kd_scale * (p[k] - q[k])),  kd_scale = distill_wt / (D * T);
+// the CE term is ce_bwd_kernel's arithmetic, the teacher gets no gradient
+template <int NC, int PX>
+__global__ void __launch_bounds__(kThreads, 2)
+distill_bwd_kernel(const float* __restrict__ slp, const float* __restrict__ tlp, const int64_t* __restrict__ tgt,
+                   int nimg, int c, int64_t hw, int64_t ignore, float invT, float student_wt, float kd_scale,
+                   const float* __restrict__ dloss, const float* __restrict__ count, float* __restrict__ gs) {
+  const int nc = NC > 0 ? NC : c;
+  const float sc_ce = dloss[0] * student_wt / count[0];
+  const float sc_kd = dloss[0] * kd_scale;
+  const int64_t hwq = hw / PX;
+  const int64_t total = static_cast<int64_t>(nimg) * hwq;
+  for (int64_t i = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x; i < total;
+       i += static_cast<int64_t>(gridDim.x) * blockDim.x) {
+    const int64_t b = i / hwq, p = (i - b * hwq) * PX;
+    KdRow<NC> s[PX], t[PX];
+    kd_load<NC, PX>(slp + b * c * hw + p, hw, s);
+    kd_load<NC, PX>(tlp + b * c * hw + p, hw, t);
+    float ls[PX], la[PX], lb[PX];
+    int64_t tg[PX];
+    bool live[PX];
+#pragma unroll
+    for (int e = 0; e < PX; ++e) {
+      tg[e] = tgt[b * hw + p + e];
+      live[e] = !(tg[e] == ignore || tg[e] < 0 || tg[e] >= c);
+      ls[e] = kd_lse(s[e], c, 1.f);
+      la[e] = kd_lse(s[e], c, invT);
+      lb[e] = kd_lse(t[e], c, invT);
+    }
+    float* o = gs + b * c * hw + p;
+#pragma unroll
+    for (int k = 0; k < nc; ++k) {
+      float g[PX];
+#pragma unroll
+      for (int e = 0; e < PX; ++e) {
+        const float ce = live[e] ? sc_ce * (expf(s[e][k] - ls[e]) - (k == tg[e] ? 1.f : 0.f)) : 0.f;
+        g[e] = ce + sc_kd * (expf(kd_logp(s[e], k, invT, la[e])) - expf(kd_logp(t[e], k, invT, lb[e])));
+      }
+      if constexpr (PX == 4) *reinterpret_cast<float4*>(o + k * hw) = make_float4(g[0], g[1], g[2], g[3]);
+      else o[k * hw] = g[0];
+    }
+  }
+}
+
 // ------------------------------------------------------------------ SGD (+ mask)
 constexpr int kSgdBatch = 48;
 struct SgdBatch {
@@ -1303,6 +1503,75 @@ extern "C" int drnmi_ce_loss_bwd_f32(const float* logprobs, const int64_t* targe
     hipLaunchKernelGGL(ce_bwd_kernel<0>, dim3(grid_of(static_cast<int64_t>(n) * hw)), dim3(kThreads), 0,
                        reinterpret_cast<hipStream_t>(stream), logprobs, target, n, c, hw, ignore_index, dloss, count,
                        g_logprobs);
+  return static_cast<int>(hipGetLastError());
+}
+
+extern "C" int64_t drnmi_distill_workspace_bytes(void) { return 4LL * kCeBlocks * 8; }
+
+namespace {
+// the argument checks the two distillation entry points share (before any HIP call)
+bool distill_args_ok(const void* s, const void* t, const void* target, int32_t n, int32_t c, int64_t hw,
+                     float student_wt, float distill_wt, float temperature) {
+  return s != nullptr && t != nullptr && target != nullptr && n > 0 && c > 0 && hw > 0 && std::isfinite(temperature) &&
+         temperature > 0.f && std::isfinite(student_wt) && student_wt >= 0.f && std::isfinite(distill_wt) &&
+         distill_wt >= 0.f;
+}
+// KD = sum kd_i / D: every pixel ("mean"), or the reference's size_average=False / shape[0] ("batchmean")
+double distill_div(int32_t n, int64_t hw, int32_t batchmean) {
+  return batchmean != 0 ? static_cast<double>(n) : static_cast<double>(n) * static_cast<double>(hw);
+}
+}  // namespace
+
+extern "C" int drnmi_distill_loss_f32(const float* student_lp, const float* teacher_lp, const int64_t* target,
+                                      int32_t n, int32_t c, int64_t hw, int64_t ignore_index, float student_wt,
+                                      float distill_wt, float temperature, int32_t batchmean, float* out3,
+                                      float* count, void* ws, void* stream) {
+  if (!distill_args_ok(student_lp, teacher_lp, target, n, c, hw, student_wt, distill_wt, temperature) ||
+      out3 == nullptr || count == nullptr || ws == nullptr)
+    return DRNMI_EINVAL;
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  const float invT = 1.f / temperature;
+  double* part = reinterpret_cast<double*>(ws);
+  if (c == 19 && hw % 4 == 0 && aligned16(student_lp, teacher_lp, nullptr))
+    hipLaunchKernelGGL((distill_fwd_kernel<19, 4>), dim3(kCeBlocks), dim3(kThreads), 0, s, student_lp, teacher_lp,
+                       target, n, c, hw, ignore_index, invT, part);
+  else if (c == 19)
+    hipLaunchKernelGGL((distill_fwd_kernel<19, 1>), dim3(kCeBlocks), dim3(kThreads), 0, s, student_lp, teacher_lp,
+                       target, n, c, hw, ignore_index, invT, part);
+  else
+    hipLaunchKernelGGL((distill_fwd_kernel<0, 1>), dim3(kCeBlocks), dim3(kThreads), 0, s, student_lp, teacher_lp,
+                       target, n, c, hw, ignore_index, invT, part);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return static_cast<int>(e);
+  hipLaunchKernelGGL(distill_final_kernel, dim3(1), dim3(64), 0, s, part, kCeBlocks, distill_div(n, hw, batchmean),
+                     student_wt, distill_wt, out3, count);
+  return static_cast<int>(hipGetLastError());
+}
+
+extern "C" int drnmi_distill_loss_bwd_f32(const float* student_lp, const float* teacher_lp, const int64_t* target,
+                                          int32_t n, int32_t c, int64_t hw, int64_t ignore_index, float student_wt,
+                                          float distill_wt, float temperature, int32_t batchmean, const float* dloss,
+                                          const float* count, float* g_student_lp, void* stream) {
+  if (!distill_args_ok(student_lp, teacher_lp, target, n, c, hw, student_wt, distill_wt, temperature) ||
+      dloss == nullptr || count == nullptr || g_student_lp == nullptr)
+    return DRNMI_EINVAL;
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  const float invT = 1.f / temperature;
+  const float kd_scale = static_cast<float>(static_cast<double>(distill_wt) /
+                                            (distill_div(n, hw, batchmean) * static_cast<double>(temperature)));
+  const int64_t total = static_cast<int64_t>(n) * hw;
+  if (c == 19 && hw % 4 == 0 && aligned16(student_lp, teacher_lp, g_student_lp))
+    hipLaunchKernelGGL((distill_bwd_kernel<19, 4>), dim3(grid_of(total / 4)), dim3(kThreads), 0, s, student_lp,
+                       teacher_lp, target, n, c, hw, ignore_index, invT, student_wt, kd_scale, dloss, count,
+                       g_student_lp);
+  else if (c == 19)
+    hipLaunchKernelGGL((distill_bwd_kernel<19, 1>), dim3(grid_of(total)), dim3(kThreads), 0, s, student_lp,
+                       teacher_lp, target, n, c, hw, ignore_index, invT, student_wt, kd_scale, dloss, count,
+                       g_student_lp);
+  else
+    hipLaunchKernelGGL((distill_bwd_kernel<0, 1>), dim3(grid_of(total)), dim3(kThreads), 0, s, student_lp,
+                       teacher_lp, target, n, c, hw, ignore_index, invT, student_wt, kd_scale, dloss, count,
+                       g_student_lp);
   return static_cast<int>(hipGetLastError());
 }
 

@@ -135,6 +135,11 @@ SIGNATURES = {
     "drnmi_ce_workspace_bytes": (ctypes.c_int64, []),
     "drnmi_ce_loss_f32": (ctypes.c_int, [_VP, _VP, _I32, _I32, _I64, _I64, _VP, _VP, _VP, _VP]),
     "drnmi_ce_loss_bwd_f32": (ctypes.c_int, [_VP, _VP, _I32, _I32, _I64, _I64, _VP, _VP, _VP, _VP]),
+    "drnmi_distill_workspace_bytes": (ctypes.c_int64, []),
+    "drnmi_distill_loss_f32": (ctypes.c_int, [_VP, _VP, _VP, _I32, _I32, _I64, _I64, _F32, _F32, _F32, _I32, _VP, _VP,
+                                              _VP, _VP]),
+    "drnmi_distill_loss_bwd_f32": (ctypes.c_int, [_VP, _VP, _VP, _I32, _I32, _I64, _I64, _F32, _F32, _F32, _I32, _VP,
+                                                  _VP, _VP, _VP]),
     "drnmi_sgd_step_f32": (ctypes.c_int, [_I32, _VP, _VP, _VP, _VP, _VP, _VP, _F32, _F32, _F32, _F32, _I32, _VP]),
     "drnmi_weight_unit_mask": (ctypes.c_int, [_VP, _I32, _I32, _I32, _VP, _VP, _VP]),
     "drnmi_sp24_pack_bytes": (ctypes.c_int64, [_I32, _I32]),

@@ -17,6 +17,8 @@ gradient-ready callback per node lets the data-parallel wrapper (drnmi.parallel)
 bucketed RCCL all-reduce of finished buckets while earlier layers are still in backward.
 `CrossEntropyLoss` and `SGD` below are the HIP drop-ins for the criterion and optimizer (the
 optimizer can fuse the pruner's mask into the update: `SGD(..., pruner=p)`).
+`DistillationLoss` is the criterion with a teacher: that CE plus the KL divergence to the
+log-probs of a frozen dense model (`teacher_logprobs`), the reference's --mc-kd.
 
 Precision: fp32 (the reference trains in fp32; model.set_precision("fp32"), the default) or
 "fp32x": the forward and data-gradient convs with >= 32 input channels run on the fp32-accurate
@@ -723,6 +725,110 @@ class CrossEntropyLoss(torch.nn.Module):
         if target.shape != (logprobs.shape[0],) + tuple(logprobs.shape[2:]):
             raise ValueError(f"target shape {tuple(target.shape)} does not match {tuple(logprobs.shape)}")
         return _CEFn.apply(logprobs.contiguous(), target.contiguous(), self.ignore_index)
+
+
+class _DistillFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, lp, tlp, target, ignore_index, student_wt, distill_wt, temperature, batchmean):
+        lib = _lib.load()
+        n, c = lp.shape[0], lp.shape[1]
+        hw = lp[0, 0].numel()
+        dev = lp.device
+        out3 = torch.empty(3, dtype=torch.float32, device=dev)
+        count = torch.empty((), dtype=torch.float32, device=dev)
+        ws = torch.empty(lib.drnmi_distill_workspace_bytes(), dtype=torch.uint8, device=dev)
+        _lib.check(lib.drnmi_distill_loss_f32(_vp(lp), _vp(tlp), _vp(target), n, c, hw, int(ignore_index), student_wt,
+                                              distill_wt, temperature, batchmean, _vp(out3), _vp(count), _vp(ws),
+                                              ctypes.c_void_p(_lib.stream_ptr(dev))), "distill_loss")
+        ctx.save_for_backward(lp, tlp, target, count)
+        ctx.args = (int(ignore_index), student_wt, distill_wt, temperature, batchmean)
+        loss, ce, kd = out3.unbind(0)
+        ctx.mark_non_differentiable(ce, kd)
+        return loss, ce, kd
+
+    @staticmethod
+    def backward(ctx, g, _g_ce, _g_kd):
+        lp, tlp, target, count = ctx.saved_tensors
+        n, c = lp.shape[0], lp.shape[1]
+        hw = lp[0, 0].numel()
+        glp = torch.empty_like(lp)
+        g = g.contiguous().to(torch.float32)
+        _lib.check(_lib.load().drnmi_distill_loss_bwd_f32(_vp(lp), _vp(tlp), _vp(target), n, c, hw, *ctx.args, _vp(g),
+                                                          _vp(count), _vp(glp),
+                                                          ctypes.c_void_p(_lib.stream_ptr(lp.device))),
+                   "distill_loss_bwd")
+        return (glp,) + (None,) * 7
+
+
+class DistillationLoss(torch.nn.Module):
+    """Knowledge distillation from a dense teacher into the pruned student (the reference's
+    --mc-kd, rmbsnn_main.py:192-243, for the segmentation loop) as one HIP pass forward and one
+    backward over the two log-prob tensors:
+
+        loss = student_wt * CE + distill_wt * KD
+        CE   = CrossEntropyLoss(ignore_index) of the student's log-probs (the criterion above)
+        KD   = sum over pixels of KL(softmax(teacher / T) || softmax(student / T)) / D
+
+    Every pixel counts for KD, labelled or not (the teacher supervises the pixels ignore_index
+    hides from CE); only labelled pixels count for CE.  kd_reduction="mean" divides by the number
+    of pixels n * h * w; "batchmean" by n, which is the reference's
+    F.kl_div(size_average=False) / shape[0].  There is NO T^2 factor on the KD term: the reference
+    has none, so at T > 1 the KD gradient is 1 / T of the T = 1 one — fold T^2 into distill_wt if
+    Hinton's scaling is wanted.  The teacher gets no gradient.  A batch with no labelled pixel
+    gives a NaN CE (0 / 0, as CrossEntropyLoss) and so a NaN loss, whatever student_wt is.
+
+    After a forward, `.ce` and `.kd` hold the two terms as detached device scalars (no host
+    synchronisation).  No CPU or ATen fallback."""
+
+    def __init__(self, student_wt: float = 0.5, distill_wt: float = 0.5, temperature: float = 1.0,
+                 ignore_index: int = -100, kd_reduction: str = "mean"):
+        super().__init__()
+        student_wt, distill_wt, temperature = float(student_wt), float(distill_wt), float(temperature)
+        if not (temperature > 0 and temperature != float("inf")):
+            raise ValueError("temperature must be finite and > 0")
+        for w in (student_wt, distill_wt):
+            if not (0 <= w < float("inf")):
+                raise ValueError("student_wt and distill_wt must be finite and >= 0")
+        if kd_reduction not in ("mean", "batchmean"):
+            raise ValueError("kd_reduction must be 'mean' (per pixel) or 'batchmean' (per image, the reference's)")
+        self.student_wt, self.distill_wt, self.temperature = student_wt, distill_wt, temperature
+        self.ignore_index = ignore_index
+        self.kd_reduction = kd_reduction
+        self.ce = self.kd = None
+
+    def forward(self, logprobs: torch.Tensor, teacher_logprobs: torch.Tensor, target: torch.Tensor):
+        if logprobs.dtype != torch.float32 or teacher_logprobs.dtype != torch.float32:
+            raise ValueError("expected fp32 log-probs (student and teacher)")
+        if target.dtype != torch.int64:
+            raise ValueError("expected int64 targets (semantic_seg.py:195 target.long())")
+        if logprobs.dim() < 2 or teacher_logprobs.shape != logprobs.shape:
+            raise ValueError(f"teacher log-probs {tuple(teacher_logprobs.shape)} do not match the student's "
+                             f"{tuple(logprobs.shape)}")
+        if target.shape != (logprobs.shape[0],) + tuple(logprobs.shape[2:]):
+            raise ValueError(f"target shape {tuple(target.shape)} does not match {tuple(logprobs.shape)}")
+        if teacher_logprobs.requires_grad:
+            raise ValueError("the teacher gets no gradient: compute its log-probs under torch.no_grad() "
+                             "(teacher_logprobs()) or detach them")
+        if not logprobs.is_cuda:
+            raise RuntimeError("drnmi DistillationLoss runs on the HIP kernels (no CPU fallback)")
+        if teacher_logprobs.device != logprobs.device or target.device != logprobs.device:
+            raise ValueError("student log-probs, teacher log-probs and target must be on one device")
+        loss, ce, kd = _DistillFn.apply(logprobs.contiguous(), teacher_logprobs.contiguous(), target.contiguous(),
+                                        self.ignore_index, self.student_wt, self.distill_wt, self.temperature,
+                                        1 if self.kd_reduction == "batchmean" else 0)
+        self.ce, self.kd = ce, kd
+        return loss
+
+
+def teacher_logprobs(teacher, x: torch.Tensor) -> torch.Tensor:
+    """The frozen teacher's log-probs for DistillationLoss: teacher(x)[0] under torch.no_grad(), at
+    whichever inference precision the teacher is set to (bf16 is the fast engine).  The teacher must
+    be in eval mode: its BatchNorm has to use the running statistics and must not update them."""
+    if teacher.training:
+        raise RuntimeError("the distillation teacher must be in eval mode (teacher.eval()): train-mode "
+                           "BatchNorm would use batch statistics and update the running ones")
+    with torch.no_grad():
+        return teacher(x)[0]
 
 
 # ====================================================================== eval score
