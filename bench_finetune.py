@@ -11,6 +11,7 @@ resident in HBM; hash-initialised weights.
 
     python bench_finetune.py [--steps K] [--warmup W] [--batch B] [--gpus N]
     python bench_finetune.py --distill [--teacher-precision {fp32,fp32x,bf16}]
+    python bench_finetune.py --precision fp32x --qat
     torchrun --nproc-per-node N bench_finetune.py --gpus N
 
 `--gpus N` outside torchrun spawns the N rank processes itself (bench.py's launcher); under
@@ -20,6 +21,12 @@ a CPU stand-in step over gloo through the same launcher, seeding and max-over-ra
 `--distill` (opt-in) adds the reference's knowledge distillation (rmbsnn_main.py --mc-kd) to the
 step: a frozen dense teacher of the same arch runs its inference forward on the batch and the
 criterion becomes drnmi.train.DistillationLoss(0.5, 0.5, T=2); the JSON line gains a "distill" object.
+
+`--qat` (opt-in) fine-tunes quantisation-aware (DRNSeg.set_qat("int8")): the model is
+calibrated on synthetic frames of the crop size first, and the step is timed with QAT on and with QAT
+off in alternating rounds of one process (--qat-rounds, each round --steps steps after an untimed step
+that rebuilds the weight-pack table); the headline is the QAT-on median and the JSON line gains a "qat"
+object with both.
 
 Prints ONE JSON line (rank 0).  Not the driver's headline bench (bench.py is).
 """
@@ -55,6 +62,10 @@ def parse(argv=None):
                          "runs inside the timed step and the criterion is DistillationLoss (CE + KL to the teacher)")
     ap.add_argument("--teacher-precision", default="bf16", choices=["fp32", "fp32x", "bf16"],
                     help="inference precision of the --distill teacher")
+    ap.add_argument("--qat", action="store_true",
+                    help="quantisation-aware fine-tuning: calibrate int8 activation scales on synthetic frames, then "
+                         "time the step with set_qat('int8') and, in the same process, with QAT off")
+    ap.add_argument("--qat-rounds", type=int, default=3, help="alternating QAT-on / QAT-off timing rounds of --qat")
     ap.add_argument("--cpu-seconds", type=float, default=20.0)
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--stub-step", action="store_true",
@@ -237,6 +248,11 @@ def main(argv=None):
         teacher = teacher.to(dev).eval().set_precision(args.teacher_precision)
         crit = DistillationLoss(0.5, 0.5, 2.0, ignore_index=255)
     B, H, W = args.batch, args.height, args.width
+    if args.qat:
+        from drnmi.weights import synth_frames
+        m.eval()
+        m.calibrate_int8(torch.from_numpy(synth_frames(3000 + rank, 1, H, W)).to(dev))
+        m.train().set_qat("int8")
     g = torch.Generator(device=dev).manual_seed(2000 + rank)
     x = torch.randn(B, 3, H, W, device=dev, generator=g)
     t = torch.randint(0, 19, (B, H, W), device=dev, generator=g)
@@ -263,6 +279,31 @@ def main(argv=None):
     if world > 1:
         dist.barrier()
     el = max_over_ranks(time.perf_counter() - t0, device=dev)
+    qat = None
+    if args.qat:
+        # QAT on / off in alternating rounds of this process: one untimed step after each switch (the
+        # weight-pack table follows the pack's source buffers), then --steps timed steps
+        ms = {"int8": [el / args.steps * 1e3], None: []}
+        for mode in [None] + [md for _ in range(args.qat_rounds - 1) for md in ("int8", None)]:
+            m.set_qat(mode)
+            step()
+            torch.cuda.synchronize()
+            if world > 1:
+                dist.barrier()
+            t1 = time.perf_counter()
+            for _ in range(args.steps):
+                loss = step()
+            torch.cuda.synchronize()
+            ms[mode].append(max_over_ranks(time.perf_counter() - t1, device=dev) / args.steps * 1e3)
+        m.set_qat("int8")
+        med = lambda v: sorted(v)[len(v) // 2]
+        layers, values = m.qat_layers()
+        qat = {"mode": "int8", "ms_per_step_qat": [round(v, 3) for v in ms["int8"]],
+               "ms_per_step_off": [round(v, 3) for v in ms[None]], "median_qat": round(med(ms["int8"]), 3),
+               "median_off": round(med(ms[None]), 3), "qat_over_off": round(med(ms["int8"]) / med(ms[None]), 4),
+               "convs": len(layers), "values": len(values),
+               "note": "alternating rounds in one process; calibrated (absmax) on one synthetic frame"}
+        el = med(ms["int8"]) * args.steps / 1e3
     fl = train_flops(m, B, H, W)
     ach = fl * args.steps / el / 1e12
     peak = MFMA_PEAK["fp32"] / 1e12
@@ -302,6 +343,8 @@ def main(argv=None):
                           "distill_wt": crit.distill_wt, "temperature": crit.temperature,
                           "kd_reduction": crit.kd_reduction, "final_ce": float(crit.ce), "final_kd": float(crit.kd),
                           "note": "the teacher's forward and the CE + KL criterion run inside the timed step"}
+    if qat is not None:
+        out["qat"] = qat
     if rank == 0 and world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(args, args.cpu_seconds)
     if rank == 0:

@@ -740,6 +740,34 @@ int drnmi_conv_wgrad_plan(const drnmi_wgrad_args* args, int32_t x6, int32_t* ker
  * each step): the three weight planes of a DRNMI_F32X3 launch. */
 int drnmi_split3_bf16(const float* w, int64_t n, void* out, void* stream);
 
+/* Quantisation-aware fine-tuning (csrc/qat.hip): the int8 engine's grids as fp32
+ * values in the train step, straight-through in the backward.  One fp32 rounding per step, no FMA.
+ * All four run on the caller's stream and allocate nothing; NULL or misaligned pointers (16 bytes;
+ * 4 for row_scale), n % 8 != 0 or a scale that is not a positive finite number: DRNMI_EINVAL before any
+ * HIP call; n == 0 / rows == 0: DRNMI_OK, nothing launched.
+ *   drnmi_fake_quant_f32: y[i] = float(clamp(rint(x[i] * inv_scale), -127, 127)) * scale -- the code
+ *     drnmi_quantize_i8 gives, dequantised; inv_scale is the caller's fp32 rounding of 1 / scale (the
+ *     one the int8 plan passes).  A zero level is +0.
+ *   drnmi_fake_quant_bwd_f32: the straight-through gradient of that, g = dq[i] where
+ *     |rint(x[i] * inv_scale)| <= 127 (the level was not clamped; recomputed from x, no stored mask),
+ *     else 0; dx[i] = g, or dx[i] + g (one rounding) with accumulate = 1.
+ *   drnmi_fake_quant_rows_f32: per row of w [rows][cols] (an OIHW conv weight: one output channel),
+ *     a = max |w|, q = clamp(rint(w * (127 / a)), -127, 127), wq = float(q) * (a / 127),
+ *     row_scale = a / 127; an all-zero row gives zeros and scale 1.  q is the int8 code the int8 pack
+ *     (drnmi/engine.py _pack_q8) stores for that weight.  cols: any positive count.
+ *   drnmi_fake_quant_rows_batched_f32: the same for every entry of a DEVICE table in one launch (one
+ *     workgroup per row), n <= 512 entries of DRNMI_FQ_ROWS_ENTRY_WORDS int64 each:
+ *     [0] w, [1] wq, [2] row_scale, [3] rows, [4] cols, [5] first row of the entry (prefix sum of rows).
+ *     total_rows = sum of rows.  drnmi_fake_quant_rows_table_check validates a HOST copy first. */
+#define DRNMI_FQ_ROWS_ENTRY_WORDS 6
+int drnmi_fake_quant_f32(const float* x, int64_t n, float scale, float inv_scale, float* y, void* stream);
+int drnmi_fake_quant_bwd_f32(const float* dq, const float* x, int64_t n, float inv_scale, float* dx,
+                             int32_t accumulate, void* stream);
+int drnmi_fake_quant_rows_f32(const float* w, int64_t rows, int32_t cols, float* wq, float* row_scale,
+                              void* stream);
+int drnmi_fake_quant_rows_table_check(const int64_t* table_host, int32_t n, int64_t* total_rows_out);
+int drnmi_fake_quant_rows_batched_f32(const int64_t* table, int32_t n, int64_t total_rows, void* stream);
+
 /* out[n][y][x][c] = dy[n][y/s][x/s][c] where y, x are multiples of s (and inside dy), else 0;
  * out is [n][hu][wu][c] (c % 4 == 0).  Input of the stride-1 dgrad conv of a stride-s conv. */
 int drnmi_zero_insert_f32(const float* dy, int32_t n, int32_t ho, int32_t wo, int32_t c, int32_t stride,

@@ -129,6 +129,11 @@ SIGNATURES = {
                                              ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int64),
                                              ctypes.POINTER(ctypes.c_int32)]),
     "drnmi_split3_bf16": (ctypes.c_int, [_VP, ctypes.c_int64, _VP, _VP]),
+    "drnmi_fake_quant_f32": (ctypes.c_int, [_VP, _I64, _F32, _F32, _VP, _VP]),
+    "drnmi_fake_quant_bwd_f32": (ctypes.c_int, [_VP, _VP, _I64, _F32, _VP, _I32, _VP]),
+    "drnmi_fake_quant_rows_f32": (ctypes.c_int, [_VP, _I64, _I32, _VP, _VP, _VP]),
+    "drnmi_fake_quant_rows_table_check": (ctypes.c_int, [_VP, _I32, ctypes.POINTER(ctypes.c_int64)]),
+    "drnmi_fake_quant_rows_batched_f32": (ctypes.c_int, [_VP, _I32, _I64, _VP]),
     "drnmi_zero_insert_f32": (ctypes.c_int, [_VP, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _VP, _VP]),
     "drnmi_up8_lsm_bwd_f32": (ctypes.c_int, [_VP, _VP, _VP, _VP, _F32, _I32, _I32, _I32, _I32, _VP, _VP, _VP]),
     "drnmi_up8_bilinear_lsm_bwd_f32": (ctypes.c_int, [_VP, _VP, _VP, _F32, _I32, _I32, _I32, _I32, _VP, _VP, _VP]),

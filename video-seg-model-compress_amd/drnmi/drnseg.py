@@ -94,6 +94,7 @@ class DRNSeg(nn.Module):
         self._int8_hists = None      # value -> |x| histogram of the last histogram calibration
         self._int8_method = None     # how _act_scales were derived (int8_state)
         self._int8_percentile = None
+        self._qat = None             # "int8": quantisation-aware fine-tuning (set_qat)
         self._packed = {}
         self._plans = {}
         self._pack_key = None
@@ -114,6 +115,7 @@ class DRNSeg(nn.Module):
         st.update(_packed={}, _plans={}, _pack_key=None, _key_tensors=None, _key_ids=None, _key_dicts=[],
                   timing_hook=None, _int8_hists=None)
         st.pop("_train_runner", None)
+        st.pop("_qat", None)         # like the runner: a copy fine-tunes without QAT until set_qat
         return st
 
     def __setstate__(self, st):
@@ -389,6 +391,44 @@ class DRNSeg(nn.Module):
         self._install_act_scales({v: float(scales[v]) for v in self._int8_values()}, state.get("method"),
                                  state.get("percentile"))
         return self
+
+    def set_qat(self, mode: str | None) -> "DRNSeg":
+        """Quantisation-aware fine-tuning: with "int8" the train-mode forward (precision "fp32" or
+        "fp32x") reads the int8 engine's grids wherever precision "int8" would launch W8A8 for this
+        model: those convs (qat_layers()[0]) see their weights on the per-output-channel int8 grid and,
+        as input and residual, the activations (qat_layers()[1]) on their calibrated per-tensor grid;
+        the backward is straight-through.  The scales are the installed ones
+        (calibrate_int8 / rescale_int8 / load_int8_state), read at every forward and fixed during a
+        step; without them this call raises the engine's "no calibrated activation scale"
+        RuntimeError.  Eval-mode paths are untouched: after the fine-tune, re-calibrate and
+        set_precision("int8").  None switches it off (the default): the step is then launch for launch
+        what it was.  The DRN-D family only, like precision "int8"."""
+        if mode not in ("int8", None):
+            raise ValueError("set_qat takes 'int8' or None")
+        if mode is not None:
+            if self.arch != "D":
+                raise NotImplementedError(f"quantisation-aware fine-tuning covers the DRN-D family only, as precision "
+                                          f"'int8' does; {self.model_name} fine-tunes in 'fp32' or 'fp32x'")
+            self._qat_scales()
+        self._qat = mode
+        return self
+
+    def qat_layers(self):
+        """(names of the convs that fine-tune on int8-grid weights and inputs, the graph values that
+        are fake-quantised for them): precision "int8"'s W8A8 launches and what they read.  A
+        property of the architecture; needs neither a device nor scales."""
+        from .engine import channel_strides, int8_layout
+        elig, _, need = int8_layout(self._graph, channel_strides(self._graph))
+        return [self._graph.nodes[i].name for i in sorted(elig)], sorted(need, key=lambda v: (len(v), v))
+
+    def _qat_scales(self) -> dict:
+        """{value: calibrated scale} of the fake-quantised values (the engine's error without them)."""
+        _, need = self.qat_layers()
+        scales = self._act_scales or {}
+        missing = sorted(v for v in need if v not in scales)
+        if missing:
+            raise RuntimeError(f"int8: no calibrated activation scale for {missing} (DRNSeg.calibrate_int8)")
+        return {v: float(scales[v]) for v in need}
 
     def set_block_sparse(self, enabled: bool) -> "DRNSeg":
         """bf16: let pruned (all-zero) 16 x 32 weight units skip their MFMAs (opt-in; results are

@@ -234,6 +234,51 @@ def _fold_bn(bn: nn.BatchNorm2d):
     return scale, shift
 
 
+def int8_layout(graph: Graph, cstride: dict):
+    """The 8-bit layout decision of a graph, from the graph and its channel strides alone (no
+    device, no scales): (elig, q8_values, need).  elig: indices of the nodes that launch W8A8;
+    q8_values: the values that are 8-bit in HBM (an 8-bit launch produces them and only 8-bit
+    launches read them), in elig's order; need: the values some node of elig reads as src or res.
+    PackedNet builds its plan on it; quantisation-aware fine-tuning (drnmi.train) fake-quantises
+    exactly the weights of elig and the values of need."""
+    g = graph
+    # (cout >= 128 too: the int8 tiles are 128 channels wide; the 64-channel layer3 convs keep
+    # the bf16 halo kernel)
+    producer = {nd.dst: i for i, nd in enumerate(g.nodes)}
+
+    def layer4_shape(nd):
+        c = nd.conv
+        if not INT8_LAYER4 or (c.in_channels, c.out_channels, c.kernel_size[0], c.stride[0], c.groups) != \
+                (128, 128, 3, 1, 1) or cstride[nd.src] != 128:
+            return False
+        # a block conv2 whose residual is a downsample keeps the bf16 tile with it folded in
+        return not (nd.res and nd.res in producer and g.nodes[producer[nd.res]].name.endswith("downsample.0"))
+    elig = {i for i, nd in enumerate(g.nodes)
+            if cstride[nd.src] >= INT8_MIN_CIN and nd.conv.kernel_size[0] in (1, 3)
+            and (nd.conv.out_channels >= INT8_MIN_COUT or nd.out_fp32_nchw or layer4_shape(nd))}
+    readers = {}
+    for i, nd in enumerate(g.nodes):
+        for v in (nd.src, nd.res):
+            if v:
+                readers.setdefault(v, []).append(i)
+    q8_values = []
+    for i in elig:
+        nd = g.nodes[i]
+        if not nd.out_fp32_nchw and readers.get(nd.dst) and all(j in elig for j in readers[nd.dst]):
+            q8_values.append(nd.dst)
+    need = {v for i in elig for v in (g.nodes[i].src, g.nodes[i].res) if v}
+    return elig, q8_values, need
+
+
+def channel_strides(graph: Graph) -> dict:
+    """Channel stride of every value in HBM: 8 for the input, the next power of two elsewhere."""
+    cs = {"input": 8}
+    for v, c in graph.channels.items():
+        if v != "input":
+            cs[v] = _pow2_at_least(c)
+    return cs
+
+
 class PackedNet:
     """Device-resident packed weights for one precision.
 
@@ -270,30 +315,10 @@ class PackedNet:
         int8 launch produces it and only int8 launches read it; a bf16 value read by an int8
         launch gets an int8 copy "q:<value>" quantised right after its producer."""
         g = self.graph
-        # (cout >= 128 too: the int8 tiles are 128 channels wide; the 64-channel layer3 convs keep
-        # the bf16 halo kernel)
         producer = {nd.dst: i for i, nd in enumerate(g.nodes)}
-
-        def layer4_shape(nd):
-            c = nd.conv
-            if not INT8_LAYER4 or (c.in_channels, c.out_channels, c.kernel_size[0], c.stride[0], c.groups) != \
-                    (128, 128, 3, 1, 1) or self.cstride[nd.src] != 128:
-                return False
-            # a block conv2 whose residual is a downsample keeps the bf16 tile with it folded in
-            return not (nd.res and nd.res in producer and g.nodes[producer[nd.res]].name.endswith("downsample.0"))
-        elig = {i for i, nd in enumerate(g.nodes)
-                if self.cstride[nd.src] >= INT8_MIN_CIN and nd.conv.kernel_size[0] in (1, 3)
-                and (nd.conv.out_channels >= INT8_MIN_COUT or nd.out_fp32_nchw or layer4_shape(nd))}
-        readers = {}
-        for i, nd in enumerate(g.nodes):
-            for v in (nd.src, nd.res):
-                if v:
-                    readers.setdefault(v, []).append(i)
-        for i in elig:
-            nd = g.nodes[i]
-            if not nd.out_fp32_nchw and readers.get(nd.dst) and all(j in elig for j in readers[nd.dst]):
-                self.vcode[nd.dst] = self.qcode
-        need = {v for i in elig for v in (g.nodes[i].src, g.nodes[i].res) if v}
+        elig, q8_values, need = int8_layout(g, self.cstride)
+        for v in q8_values:
+            self.vcode[v] = self.qcode
         missing = sorted(v for v in need | set(self.vcode) if v not in self.act_scales)
         if missing:
             raise RuntimeError(f"{self.precision}: no calibrated activation scale for {missing} (DRNSeg.calibrate_int8)")

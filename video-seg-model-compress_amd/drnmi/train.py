@@ -26,6 +26,10 @@ split-bf16 kernel (csrc/conv_x6.hip: exact 3-way bf16 split of weights and activ
 products above 2^-24, fp32 accumulation, 2.5 PF / 6 peak) instead of the exact-f32 MFMA
 (157 TF), and so do their weight gradients (drnmi_conv_wgrad_f32x3, the same split on dy and x);
 BN, the head and the small-channel convs stay exact fp32.
+Quantisation-aware fine-tuning (model.set_qat("int8")), in either precision: the convs
+precision "int8" launches W8A8 read their weights and activations on the int8 grids (csrc/qat.hip,
+fake quantisation in fp32), straight-through in the backward.  Off by default; with it off no launch,
+buffer or record of the step differs.
 Activations NHWC with a power-of-two channel stride, like the inference engine.  There is no
 CPU or ATen fallback.
 """
@@ -37,7 +41,7 @@ import os
 import torch
 
 from . import _lib
-from .engine import COUT_ALIGN, K_ALIGN, X6_PATCH_SHAPES, _conv_out, _pow2_at_least, _round_up
+from .engine import COUT_ALIGN, K_ALIGN, X6_PATCH_SHAPES, _conv_out, _pow2_at_least, _round_up, int8_layout
 
 F32 = _lib.DRNMI_F32
 # TrainRunner default (tests switch it off to compare against the per-layer packs)
@@ -61,13 +65,16 @@ class _NodeState:
     """Per-node packed weights (forward / dgrad layouts) cached across steps."""
 
     __slots__ = ("wf", "wd", "wfx", "wdx", "k", "k_pad", "cout_pad", "kd", "kd_pad", "rows_d", "shift", "patch",
-                 "dpatch", "dys", "s2_step", "s2_cls", "s2_planes")
+                 "dpatch", "dys", "s2_step", "s2_cls", "s2_planes", "wq", "wq_scale", "wsrc")
 
     def __init__(self):
         self.wf = self.wd = self.wfx = self.wdx = self.shift = None
         self.patch = self.dpatch = False
         self.dys = None
         self.s2_step = self.s2_cls = self.s2_planes = None   # stride-2 dgrad parity classes (per step)
+        # QAT: the fake-quantised OIHW shadow of the weight and its per-row scales; wsrc is what this
+        # step's packs read in place of conv.weight (the shadow, or None)
+        self.wq = self.wq_scale = self.wsrc = None
 
 
 class TrainRunner:
@@ -106,6 +113,15 @@ class TrainRunner:
         self._pack_tab = None
         self._pack_total = 0
         self._packed_now = False
+        # quantisation-aware fine-tuning (model.set_qat): the node indices whose weights and inputs are
+        # on the int8 grids this step (None: off) and {value: (scale, 1 / scale)} of the fake-quantised
+        # values; the device table of the one weight launch, rebuilt when a buffer moves
+        self._qat_layout = None
+        self._qat_E = None
+        self._qat_sc = {}
+        self._qat_key = None
+        self._qat_tab = None
+        self._qat_rows = 0
 
     # ------------------------------------------------------------------ helpers
     def _ws(self, attr, nbytes, device):
@@ -161,6 +177,68 @@ class TrainRunner:
                 acc[id(p)] = True
         return acc
 
+    @staticmethod
+    def _weight(nd, st):
+        """The OIHW fp32 weight this step's packs read: the QAT shadow where there is one."""
+        return st.wsrc if st.wsrc is not None else nd.conv.weight.detach()
+
+    def _qat_begin(self, device, stream):
+        """QAT on: fake-quantise the weights of the int8 engine's W8A8 convs into their shadows in one
+        launch (drnmi_fake_quant_rows_batched_f32), before any pack reads them, and fix this step's
+        activation scales.  QAT off: nothing is launched or allocated."""
+        if getattr(self.model, "_qat", None) is None:
+            if self._qat_E is not None:
+                for st in self.state:
+                    st.wsrc = None
+                self._qat_E, self._qat_sc = None, {}
+            return
+        scales = self.model._qat_scales()         # raises the engine's error without calibrated scales
+        if self._qat_layout is None:
+            self._qat_layout = int8_layout(self.graph, self.cstride)
+        elig = sorted(self._qat_layout[0])
+        self._qat_E = self._qat_layout[0]
+        self._qat_sc = {v: (s, 1.0 / s) for v, s in scales.items()}
+        key = []
+        for i in elig:
+            nd, st = self.nodes[i], self.state[i]
+            w = nd.conv.weight.detach()
+            if not (w.is_contiguous() and w.dtype == torch.float32):
+                raise RuntimeError(f"{nd.name}: expected a contiguous fp32 weight")
+            if st.wq is None or st.wq.shape != w.shape or st.wq.device != w.device:
+                st.wq = torch.empty_like(w)
+                st.wq_scale = torch.empty(w.shape[0], dtype=torch.float32, device=w.device)
+            st.wsrc = st.wq
+            key.append((w.data_ptr(), st.wq.data_ptr(), st.wq_scale.data_ptr()))
+        key = tuple(key)
+        lib = _lib.load()
+        if key != self._qat_key:
+            rows, total = [], 0
+            for i, (pw, pq, ps) in zip(elig, key):
+                w = self.nodes[i].conv.weight
+                rows.append([pw, pq, ps, w.shape[0], w[0].numel(), total])
+                total += w.shape[0]
+            tab = torch.tensor(rows, dtype=torch.int64)
+            tot = ctypes.c_int64(0)
+            _lib.check(lib.drnmi_fake_quant_rows_table_check(ctypes.c_void_p(tab.data_ptr()), len(rows),
+                                                             ctypes.byref(tot)), "fake-quant weight table")
+            self._qat_tab, self._qat_rows, self._qat_key = tab.to(device), int(tot.value), key
+        _lib.check(lib.drnmi_fake_quant_rows_batched_f32(_vp(self._qat_tab), self._qat_tab.shape[0], self._qat_rows,
+                                                         stream), "fake-quant weights")
+        if self.record is not None:
+            for i in elig:
+                nd, st = self.nodes[i], self.state[i]
+                self._rec("fq_rows", nd.name, w=self._snap(nd.conv.weight), wq=self._snap(st.wq),
+                          scale=self._snap(st.wq_scale))
+
+    def _fake_quant(self, v, z, stream):
+        """fq(v) of this step (drnmi_fake_quant_f32), computed once, right after v's producer."""
+        s, inv = self._qat_sc[v]
+        zq = torch.empty_like(z)
+        _lib.check(_lib.load().drnmi_fake_quant_f32(_vp(z), z.numel(), s, inv, _vp(zq), stream), f"fake_quant {v}")
+        if self.record is not None:
+            self._rec("fq", v, x=z, y=zq, scale=s, inv_scale=inv)
+        return zq
+
     def _pack(self, nd, st, device, stream):
         lib = _lib.load()
         conv = nd.conv
@@ -172,7 +250,7 @@ class TrainRunner:
             st.cout_pad = _round_up(cout, COUT_ALIGN)
             st.wf = torch.empty(st.cout_pad, st.k_pad, dtype=torch.float32, device=device)
             st.shift = torch.zeros(st.cout_pad, dtype=torch.float32, device=device)
-        w = conv.weight.detach()
+        w = self._weight(nd, st)
         if not (w.is_contiguous() and w.dtype == torch.float32):
             raise RuntimeError(f"{nd.name}: expected a contiguous fp32 weight")
         if not self._packed_now:
@@ -198,7 +276,7 @@ class TrainRunner:
         st.dys = dys
         if self._packed_now:                      # packed with the forward weights (batched launch)
             return dys
-        _lib.check(lib.drnmi_pack_conv_weight(_vp(nd.conv.weight.detach()), cout, cin, ks, dys, st.rows_d,
+        _lib.check(lib.drnmi_pack_conv_weight(_vp(self._weight(nd, st)), cout, cin, ks, dys, st.rows_d,
                                               st.kd_pad, 1, None, F32, _vp(st.wd), stream), f"pack dgrad {nd.name}")
         # fp32x: a data gradient whose (stride-1) conv is a patch-kernel shape (layer1's 16 -> 16
         # at full resolution) runs split-bf16 on the patch kernel, not on the f32 igemm
@@ -263,7 +341,7 @@ class TrainRunner:
         for nd, st in zip(self.nodes, self.state):
             if st.wf is None or (nd.src != "input" and st.wd is None):
                 return False
-            key.append((nd.conv.weight.data_ptr(), st.wf.data_ptr(), st.wfx.data_ptr() if st.wfx is not None else 0,
+            key.append((self._weight(nd, st).data_ptr(), st.wf.data_ptr(), st.wfx.data_ptr() if st.wfx is not None else 0,
                         st.wd.data_ptr() if st.wd is not None else 0,
                         st.wdx.data_ptr() if st.wdx is not None else 0))
         key = tuple(key)
@@ -272,7 +350,7 @@ class TrainRunner:
             total = 0
             for nd, st in zip(self.nodes, self.state):
                 cout, cin, ks, _ = nd.conv.weight.shape
-                w = nd.conv.weight.detach()
+                w = self._weight(nd, st)
                 if not (w.is_contiguous() and w.dtype == torch.float32):
                     return False
                 ents = [(st.wf, st.wfx, self.cstride[nd.src], st.cout_pad, st.k_pad, 0)]
@@ -365,11 +443,15 @@ class TrainRunner:
                    "nchw_to_nhwc")
         vals["input"] = xin
         self._packed_now = False
+        self._qat_begin(dev, ctypes.c_void_p(stream))
         self._packed_now = self._batched_pack(dev, stream)
         per_node = []
         logits = None
-        for nd, st in zip(self.nodes, self.state):
+        qvals = {}                       # QAT: value -> fq(value), what the W8A8 convs read
+        for idx, (nd, st) in enumerate(zip(self.nodes, self.state)):
             c = nd.conv
+            # a conv the int8 engine runs W8A8 reads fq(src) / fq(res); every other conv the values
+            rd = qvals if self._qat_E is not None and idx in self._qat_E else vals
             ih, iw = shapes[nd.src]
             ks, s, p, d = c.kernel_size[0], c.stride[0], c.padding[0], c.dilation[0]
             oh, ow = _conv_out(ih, ks, s, p, d), _conv_out(iw, ks, s, p, d)
@@ -379,12 +461,12 @@ class TrainRunner:
             cs_in = self.cstride[nd.src]
             if nd.out_fp32_nchw:        # seg 1x1 + bias -> fp32 NCHW logits
                 logits = torch.empty(n, cout, oh, ow, dtype=torch.float32, device=dev)
-                self._conv(vals[nd.src], cs_in, ih, iw, st.wf, st.k, st.k_pad, st.cout_pad, cout, ks, s, p, d,
+                self._conv(rd[nd.src], cs_in, ih, iw, st.wf, st.k, st.k_pad, st.cout_pad, cout, ks, s, p, d,
                            logits, (cout * oh * ow, 1, oh * ow), st.shift, None, n, oh, ow, stream, nd.name, st.wfx)
                 vals[nd.dst] = logits
                 per_node.append(None)
                 if self.record is not None:
-                    self._rec("conv", nd.name, x=vals[nd.src], y=logits, **self._last_conv)
+                    self._rec("conv", nd.name, x=rd[nd.src], y=logits, **self._last_conv)
                 continue
             cs = self.cstride[nd.dst]
             if cs != cout:
@@ -395,13 +477,13 @@ class TrainRunner:
             if bn.momentum is None or not bn.track_running_stats:
                 raise NotImplementedError("BatchNorm2d with momentum=None / no running stats")
             # conv_x6 launches write the BN statistics partials in their epilogue (no pass over y)
-            g_rows = self._conv(vals[nd.src], cs_in, ih, iw, st.wf, st.k, st.k_pad, st.cout_pad, cout, ks, s, p,
+            g_rows = self._conv(rd[nd.src], cs_in, ih, iw, st.wf, st.k, st.k_pad, st.cout_pad, cout, ks, s, p,
                                 d, y, (oh * ow * cs, cs, 1), st.shift, None, n, oh, ow, stream, nd.name, st.wfx,
                                 _lib.ALGO_PATCH if st.patch else _lib.ALGO_IGEMM, want_stats=FUSED_BN_STATS)
             mean = torch.empty(cs, dtype=torch.float32, device=dev)
             invstd = torch.empty(cs, dtype=torch.float32, device=dev)
             if self.record is not None:
-                self._rec("conv", nd.name, x=vals[nd.src], y=y, **self._last_conv)
+                self._rec("conv", nd.name, x=rd[nd.src], y=y, **self._last_conv)
                 run0 = [self._snap(b) for b in (bn.running_mean, bn.running_var, bn.num_batches_tracked)]
             if g_rows > 0:
                 # the epilogue wrote [2][g_rows][cout] partials (row stride = cout); cs == cout here
@@ -419,7 +501,7 @@ class TrainRunner:
             for b in (bn.running_mean, bn.running_var, bn.num_batches_tracked):
                 torch.autograd.graph.increment_version(b)
             z = torch.empty(rows, cs, dtype=torch.float32, device=dev)
-            res = vals[nd.res] if nd.res else None
+            res = rd[nd.res] if nd.res else None
             _lib.check(lib.drnmi_bn_act_f32(_vp(y), _vp(mean), _vp(invstd), _vp(bn.weight.detach()),
                                             _vp(bn.bias.detach()), _vp(res), 1 if nd.relu else 0, rows, cs, _vp(z),
                                             ctypes.c_void_p(stream)), f"bn_act {nd.name}")
@@ -430,6 +512,8 @@ class TrainRunner:
                 self._rec("bn_stats", nd.name, y=y, mean=mean, invstd=invstd, fused=g_rows > 0, before=run0,
                           after=run1)
                 self._rec("bn_act", nd.name, y=y, mean=mean, invstd=invstd, res=res, z=z)
+            if nd.dst in self._qat_sc:
+                qvals[nd.dst] = self._fake_quant(nd.dst, z, ctypes.c_void_p(stream))
         lh, lw = shapes["logits"]
         logprobs = torch.empty(n, logits.shape[1], 8 * lh, 8 * lw, dtype=torch.float32, device=dev)
         if self.model.use_torch_up:      # UpsamplingBilinear2d(8) head (lmodels/drnseg.py:285-287)
@@ -446,7 +530,8 @@ class TrainRunner:
             self._rec("head", None, logits=logits, logprobs=logprobs, up=up)
         saved = None
         if save:
-            saved = {"vals": vals, "shapes": shapes, "nodes": per_node, "n": n, "up": up}
+            saved = {"vals": vals, "shapes": shapes, "nodes": per_node, "n": n, "up": up,
+                     "qat": (self._qat_E, qvals, dict(self._qat_sc))}
         return logprobs, logits, saved
 
     # ------------------------------------------------------------------ backward
@@ -477,9 +562,16 @@ class TrainRunner:
             self._rec("head_bwd", None, g_lp=glp, g_logits=glg, logprobs=logprobs, up=saved["up"],
                       grad_scale=float(self.grad_scale), dlog=self._snap(dlog))
         grads = {}          # value -> NHWC fp32 gradient buffer
+        # QAT (the forward's layout and scales): the W8A8 convs read fq(v), so their data and residual
+        # gradients collect in qgrads[v] = d fq(v), folded into grads[v] straight-through (where the
+        # level was not clamped) before v's producer consumes it
+        q_e, qvals, q_sc = saved["qat"]
+        qgrads = {}
         for idx in range(len(self.nodes) - 1, -1, -1):
             nd, st = self.nodes[idx], self.state[idx]
             c = nd.conv
+            is_q = q_e is not None and idx in q_e
+            rd, gd = (qvals, qgrads) if is_q else (vals, grads)
             cout, cin, ks, _ = c.weight.shape
             s, p, d = c.stride[0], c.padding[0], c.dilation[0]
             ih, iw = shapes[nd.src]
@@ -504,6 +596,19 @@ class TrainRunner:
                         self._rec("bias_grad", nd.name, dy=dy_rec, before=before, after=self._snap(c.bias.grad))
             else:
                 dys = self.cstride[nd.dst]
+                dq = qgrads.pop(nd.dst, None)
+                if dq is not None:
+                    prev = grads.get(nd.dst)
+                    dx = prev if prev is not None else torch.empty_like(dq)
+                    before = self._snap(prev) if self.record is not None else None
+                    _lib.check(lib.drnmi_fake_quant_bwd_f32(_vp(dq), _vp(vals[nd.dst]), dq.numel(), q_sc[nd.dst][1],
+                                                            _vp(dx), 1 if prev is not None else 0, sp),
+                               f"fake_quant_bwd {nd.dst}")
+                    grads[nd.dst] = dx
+                    if self.record is not None:
+                        self._rec("fq_bwd", nd.dst, dq=dq, x=vals[nd.dst], inv_scale=q_sc[nd.dst][1], before=before,
+                                  after=self._snap(dx))
+                    del dq
                 dz = grads.pop(nd.dst, None)
                 if dz is None:
                     raise RuntimeError(f"no gradient reached {nd.name}")
@@ -513,10 +618,10 @@ class TrainRunner:
                 dres = None
                 dres_acc = 0
                 if nd.res:
-                    dres = grads.get(nd.res)
+                    dres = gd.get(nd.res)
                     if dres is None:
                         dres = torch.empty_like(vals[nd.res])
-                        grads[nd.res] = dres
+                        gd[nd.res] = dres
                     else:
                         dres_acc = 1
                 gw, gb = bn.weight, bn.bias
@@ -551,7 +656,7 @@ class TrainRunner:
             # weight gradient
             if c.weight.requires_grad:
                 wa = _lib.WgradArgs()
-                wa.dy, wa.x, wa.dw = dy.data_ptr(), vals[nd.src].data_ptr(), c.weight.grad.data_ptr()
+                wa.dy, wa.x, wa.dw = dy.data_ptr(), rd[nd.src].data_ptr(), c.weight.grad.data_ptr()
                 wa.n, wa.h, wa.w, wa.cin, wa.cin_stride = n, ih, iw, cin, self.cstride[nd.src]
                 wa.ho, wa.wo, wa.cout, wa.dy_stride = oh, ow, cout, dys
                 wa.ks, wa.stride, wa.pad, wa.dil = ks, s, p, d
@@ -570,7 +675,7 @@ class TrainRunner:
                 _lib.check(wg(ctypes.byref(wa), sp), f"wgrad {nd.name}")
                 done.append(c.weight)
                 if self.record is not None:
-                    self._rec("wgrad", nd.name, dy=dy_rec, x=vals[nd.src], before=before,
+                    self._rec("wgrad", nd.name, dy=dy_rec, x=rd[nd.src], before=before,
                               after=self._snap(c.weight.grad), x3=x3, plan=_lib.wgrad_plan(wa, x3))
             if self.grad_ready is not None and done:
                 self.grad_ready(done)
@@ -580,7 +685,7 @@ class TrainRunner:
             if classes is not None:
                 # stride 2: four parity-class convs of dy itself, no zero-inserted copy
                 cs_src = self.cstride[nd.src]
-                prev = grads.get(nd.src)
+                prev = gd.get(nd.src)
                 if prev is not None:
                     out = prev
                 elif len(classes) < 4:          # pixels no tap reaches keep a zero gradient
@@ -603,7 +708,7 @@ class TrainRunner:
                     if self.record is not None:
                         self._rec("dgrad", nd.name, form="class", cls=(a_, b_), fill=fill, dy=dy_rec, before=before,
                                   after=self._snap(out), **self._last_conv)
-                grads[nd.src] = out
+                gd[nd.src] = out
             elif nd.src != "input":
                 dys_d = self._pack_dgrad(nd, st, dev, sp)
                 assert dys_d == dys
@@ -616,7 +721,7 @@ class TrainRunner:
                     src = torch.empty(n * hu * wu, dys, dtype=torch.float32, device=dev)
                     _lib.check(lib.drnmi_zero_insert_f32(_vp(dy), n, oh, ow, dys, s, hu, wu, _vp(src), sp),
                                f"zero_insert {nd.name}")
-                prev = grads.get(nd.src)
+                prev = gd.get(nd.src)
                 out = prev if prev is not None else torch.empty(n * ih * iw, cs_src, dtype=torch.float32, device=dev)
                 patch = st.dpatch and prev is None       # the patch kernels take no residual
                 before = self._snap(prev) if self.record is not None else None
@@ -628,7 +733,7 @@ class TrainRunner:
                     self._rec("dgrad", nd.name, form="zero_insert" if s > 1 else "s1", cls=None,
                               fill="prev" if prev is not None else "empty", dy=dy_rec, before=before,
                               after=self._snap(out), **self._last_conv)
-                grads[nd.src] = out
+                gd[nd.src] = out
             del dy
 
 
