@@ -189,7 +189,7 @@ typedef struct drnmi_conv_args {
    * drnmi_conv_workspace_bytes (0 = the plan is the inference one: pass NULL).  ws = NULL keeps
    * the inference plan (the inference engine's launches).  DRNMI_F32 launches of the implicit GEMM
    * read only whether it is set: with one (any 16-B aligned pointer, nothing is written) a conv of
-   * K >= 1024 sums K in chains of 256 folded into a second fp32 accumulator, which keeps its
+   * K >= 1024 sums K in chains of 256 (K = 512 .. 1023: of 128) folded into a second fp32 accumulator, which keeps its
    * error against float64 at that of a blocked fp32 sum; without, K is one fmaf chain, the order
    * the fp32 inference parity is pinned in.  Other dtypes ignore it. */
   void* ws;

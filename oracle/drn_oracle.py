@@ -37,6 +37,8 @@ ARCHS = {
     "drn_d_40": ("basic", [1, 1, 3, 4, 6, 3, 2, 2]),
     "drn_d_54": ("bottleneck", [1, 1, 3, 4, 6, 3, 1, 1]),
     "drn_d_56": ("bottleneck", [1, 1, 3, 4, 6, 3, 2, 2]),
+    "drn_d_105": ("bottleneck", [1, 1, 3, 4, 23, 3, 1, 1]),
+    "drn_d_107": ("bottleneck", [1, 1, 3, 4, 23, 3, 2, 2]),
 }
 
 INFO_MEAN = (0.29010095242892997, 0.32808144844279574, 0.28696394422942517)

@@ -63,13 +63,20 @@ def im2col_nhwc(x: np.ndarray, ks: int, stride: int, pad: int, dil: int):
 
 def conv_i8(x: np.ndarray, wpk: np.ndarray, scale: np.ndarray, shift: np.ndarray, cout: int,
             ks: int, stride: int, pad: int, dil: int, relu: bool, res: np.ndarray | None = None,
-            res_scale: float = 0.0, out: str = "i8", out_scale: float = 1.0) -> np.ndarray:
+            res_scale: float = 0.0, out: str = "i8", out_scale: float = 1.0, acc_via_f64: bool = False) -> np.ndarray:
     """One int8 conv launch.  x int8 NHWC [n, h, w, cin]; wpk int8 [cout_pad, k_pad] packed;
-    res int8 [n, ho, wo, cout].  Returns NHWC [n, ho, wo, cout]: int8, uint16 bf16 bits or fp32."""
+    res int8 [n, ho, wo, cout].  Returns NHWC [n, ho, wo, cout]: int8, uint16 bf16 bits or fp32.
+    acc_via_f64: the same integer sums through a float64 (BLAS) matmul -- every product is at most
+    127^2 and a sum of k <= 2^17 of them stays below 2^31 < 2^53, so every partial sum is an exact
+    integer in any order; for whole networks, where numpy's int64 matmul takes seconds per launch."""
     n = x.shape[0]
     cols, ho, wo = im2col_nhwc(x, ks, stride, pad, dil)
     k = cols.shape[1]
-    acc = cols.astype(np.int64) @ wpk[:cout, :k].astype(np.int64).T      # exact
+    if acc_via_f64:
+        assert k <= 2 ** 17
+        acc = (cols.astype(np.float64) @ wpk[:cout, :k].astype(np.float64).T).astype(np.int64)
+    else:
+        acc = cols.astype(np.int64) @ wpk[:cout, :k].astype(np.int64).T      # exact
     assert np.abs(acc).max(initial=0) < 2 ** 31
     v = acc.astype(np.int32).astype(F32) * scale[:cout].astype(F32)
     v = (v + shift[:cout].astype(F32)).astype(F32)

@@ -37,6 +37,11 @@ CONFIGS = {
     "d22_int8_2x72x2048": ("drn_d_22", "int8", 2, 72, 2048),
     "d38_bf16_1x72x2048": ("drn_d_38", "bf16", 1, 72, 2048),
     "d54_bf16_1x72x2048": ("drn_d_54", "bf16", 1, 72, 2048),
+    # two conv+BN+ReLU units in layer7 and layer8: layer.8.0 a plain 512 -> 512 dilation-1 launch, the
+    # seg classifier in layer.8.3's epilogue (and 8-bit values between all of them in the int8 plan)
+    "d24_bf16_1x72x2048": ("drn_d_24", "bf16", 1, 72, 2048),
+    "d24_int8_1x72x2048": ("drn_d_24", "int8", 1, 72, 2048),
+    "d56_bf16_1x72x2048": ("drn_d_56", "bf16", 1, 72, 2048),
 }
 GROUPS = ("front", "layer3", "layer4", "layer5", "layer6", "layer7", "layer8+seg", "head")
 F32, F64 = np.float32, np.float64

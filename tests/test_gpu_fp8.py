@@ -274,7 +274,8 @@ def _norm():
     return INFO_MEAN, INFO_STD
 
 
-@pytest.mark.parametrize("model,shape", [("drn_d_22", (2, 64, 128)), ("drn_d_54", (1, 32, 64))])
+@pytest.mark.parametrize("model,shape", [("drn_d_22", (2, 64, 128)), ("drn_d_54", (1, 32, 64)),
+                                         ("drn_d_24", (2, 72, 136)), ("drn_d_107", (1, 32, 64))])
 def test_fp8_network_every_launch(model, shape):
     """keep_all fp8 plan, synthetic weights, absmax scales of one calibration batch: every fp8 launch
     re-stated from the kernel's own input buffers, every quantised copy byte for byte, and the same
@@ -318,7 +319,12 @@ def test_fp8_network_every_launch(model, shape):
         got = plan.bufs[nd.dst].cpu()
         got = got.permute(0, 2, 3, 1).contiguous() if out == "f32" else got.view(n, oh, ow, -1)
         _check_real(got, ref, out, nd.out_scale, f"{model} {nd.name}")
-    assert has_f8_res == (model == "drn_d_54")      # Bottleneck 1x1s with an fp8 residual
+    assert has_f8_res == (model in ("drn_d_54", "drn_d_107"))      # Bottleneck 1x1s with an fp8 residual
+    if model in ("drn_d_24", "drn_d_107"):         # the two-conv tail: every unit 8-bit, fp8 values in between
+        names = {pk.graph.nodes[i].name for i in want}
+        assert {"layer.7.0", "layer.7.3", "layer.8.0", "layer.8.3", "seg"} <= names
+        by = {nd.name: nd for nd in pk.graph.nodes}
+        assert all(pk.value_code(by[k].dst) == L.DRNMI_F8 for k in ("layer.7.0", "layer.7.3", "layer.8.0", "layer.8.3"))
 
 
 _NET = {}

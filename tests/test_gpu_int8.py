@@ -188,24 +188,28 @@ def test_conv_i8_rejects_bad_args():
 _NET = {}
 
 
-def _int8_net(golden):
-    if "m" not in _NET:
+def _int8_net(golden, arch="drn_d_22", case="d22_2x128x256"):
+    """The int8 net of `arch` with the weights of golden case `case`, calibrated (absmax) on that case's
+    frames; cached per (arch, case)."""
+    key = (arch, case)
+    if key not in _NET:
         from drnmi.drnseg import build
-        case = "d22_2x128x256"
         seed = int(golden[case + "/meta"][0])
-        m = build("drn_d_22", 19, seed=seed, device=DEV)
+        m = build(arch, 19, seed=seed, device=DEV)
         frames = torch.from_numpy(golden[case + "/frames"]).to(DEV)
         m.calibrate_int8(frames)
         m.set_precision("int8")
-        _NET["m"], _NET["frames"] = m, frames
-    return _NET["m"], _NET["frames"]
+        _NET[key] = (m, frames)
+    return _NET[key]
 
 
-def test_int8_network_every_launch_exact(golden_forward):
-    """Run the int8 D-22 plan with all activations kept and re-check every int8 launch (and the
-    bf16 -> int8 boundary quantisation) from its own HBM inputs."""
+def check_int8_every_launch(m, frames, acc_via_f64=False):
+    """Run m's int8 plan on `frames` with all activations kept and re-check every int8 launch (and every
+    bf16 -> int8 boundary quantisation) from its own HBM inputs, bit for bit against
+    oracle/int8_oracle.py (acc_via_f64: its exact float64 form of the integer sums).  Returns (names
+    of the int8 nodes checked, values whose copy was checked, largest saturated fraction of an int8
+    output)."""
     from drnmi import _lib as L
-    m, frames = _int8_net(golden_forward)
     n, h, w = frames.shape[:3]
     plan = m.plan(n, h, w, keep_all=True)
     pk = plan.packed
@@ -214,12 +218,13 @@ def test_int8_network_every_launch_exact(golden_forward):
     plan.run_backbone(stream)
     torch.cuda.synchronize()
     i8_nodes = [(i, nd) for i, nd in enumerate(pk.graph.nodes) if nd.i8]
-    assert len(i8_nodes) >= 10 and pk.quant_after, "D-22: layer4..seg should run int8"
+    copies = []
     for i, vals in pk.quant_after.items():
         for v in vals:
             src = plan.bufs[v].float().cpu().numpy()
             ref = Q.quantize_i8(src, np.float32(1.0 / pk.act_scales[v]))
             np.testing.assert_array_equal(plan.bufs["q:" + v].cpu().numpy(), ref)
+            copies.append(v)
     sat = []
     for i, nd in i8_nodes:
         c = nd.conv
@@ -231,17 +236,26 @@ def test_int8_network_every_launch_exact(golden_forward):
         out = "f32" if nd.out_fp32_nchw else ("i8" if pk.value_code(nd.dst) == L.DRNMI_I8 else "bf16")
         ref = Q.conv_i8(x, nd.wpk.cpu().numpy(), nd.scale.cpu().numpy(), nd.shift.cpu().numpy(), c.out_channels,
                         c.kernel_size[0], c.stride[0], c.padding[0], c.dilation[0], nd.relu, res, nd.res_scale,
-                        out, nd.out_scale)
-        got = plan.bufs[nd.dst].cpu().numpy()
-        if out == "f32":
-            got = got.transpose(0, 2, 3, 1)
-        elif out == "bf16":
-            got = got.view(np.uint16).reshape(ref.shape)
+                        out, nd.out_scale, acc_via_f64=acc_via_f64)
+        got = plan.bufs[nd.dst]
+        if out == "bf16":       # (numpy has no bf16: the bits.  Bottleneck nets have such launches, D-22 none)
+            got = got.view(torch.int16).cpu().numpy().view(np.uint16).reshape(ref.shape)
+        elif out == "f32":
+            got = got.cpu().numpy().transpose(0, 2, 3, 1)
         else:
-            got = got.reshape(ref.shape)
+            got = got.cpu().numpy().reshape(ref.shape)
             sat.append(float((np.abs(ref.astype(np.int32)) == 127).mean()))
         np.testing.assert_array_equal(got, ref, err_msg=nd.name)
-    print(f"int8 launches checked: {len(i8_nodes)}, max saturated fraction {max(sat):.4f}")
+    return [nd.name for _, nd in i8_nodes], copies, max(sat)
+
+
+def test_int8_network_every_launch_exact(golden_forward):
+    """Run the int8 D-22 plan with all activations kept and re-check every int8 launch (and the
+    bf16 -> int8 boundary quantisation) from its own HBM inputs."""
+    m, frames = _int8_net(golden_forward)
+    names, copies, sat = check_int8_every_launch(m, frames)
+    assert len(names) >= 10 and copies, "D-22: layer4..seg should run int8"
+    print(f"int8 launches checked: {len(names)}, max saturated fraction {sat:.4f}")
 
 
 def _norm():

@@ -55,8 +55,8 @@ def test_plan_launches_match_reference(cfg, group):
 @pytest.mark.gpu
 @pytest.mark.parametrize("cfg", list(A.CONFIGS))
 def test_plan_launches_all_audited(cfg):
-    """Every captured launch falls in exactly one audited group and has a reference; the D-22
-    plans run the kernels DESIGN.md §3.1 lists, all of them and no other."""
+    """Every captured launch falls in exactly one audited group and has a reference; the D-22 and
+    D-24 plans run the kernels DESIGN.md §3.1 lists, all of them and no other."""
     recs = A.capture(cfg)
     assert [r.index for r in recs] == sorted({r.index for r in recs})
     assert sum(len(A.launches(cfg, g)) for g in A.GROUPS) == len(recs)
@@ -66,9 +66,10 @@ def test_plan_launches_all_audited(cfg):
     assert {r.group for r in recs} == set(A.GROUPS)
     names = {A.short_name(r.kernel) for r in recs}
     print(f"{cfg}: {len(recs)} launches, kernels {sorted(names)}")
-    if cfg.startswith("d22_bf16"):
+    # (D-24: D-22 with a second conv+BN+ReLU unit in layer7 and layer8, on the kernels D-22 runs)
+    if cfg.startswith(("d22_bf16", "d24_bf16")):
         assert names == D22_BF16_KERNELS, names ^ D22_BF16_KERNELS
-    elif cfg.startswith("d22_int8"):
+    elif cfg.startswith(("d22_int8", "d24_int8")):
         assert names == D22_INT8_KERNELS, names ^ D22_INT8_KERNELS
         assert any(r.quant for r in recs), "no bf16 -> int8 copy audited"
     else:
@@ -298,6 +299,8 @@ def test_groups_and_names():
     assert [A.group_of(s) for s in ("layer.0.0", "layer.2.0", "layer.3.1.conv2", "layer.6.0.downsample.0",
                                     "layer.8.0", "seg", None)] == \
         ["front", "front", "layer3", "layer6", "layer8+seg", "layer8+seg", "head"]
+    # the second conv+BN+ReLU unit of layer7 / layer8 (D-24 / 40 / 56 / 107)
+    assert [A.group_of(s) for s in ("layer.7.0", "layer.7.3", "layer.8.3")] == ["layer7", "layer7", "layer8+seg"]
     assert A.short_name("conv_s2row_kernel<32, 7, 2>") == "conv_s2row<32>"
     assert A.short_name("conv_big_kernel<1, 128, 2, 2, 64, false, 4, false, true>") == "conv_big"
     assert A.short_name("conv_w1h_x2_kernel") == "conv_w1h_x2" and A.short_name("front3_kernel") == "front3"

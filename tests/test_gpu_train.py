@@ -96,9 +96,23 @@ def test_train_steps_match_reference(fused_mask):
 
 # D-54 (Bottleneck, 2048-channel 1x1 convs) has many pre-activations near zero: the reference's
 # own fp32 CPU gradients are 6e-3 (max-abs rel) away from fp64 on this case (scripts/archive/train_diag.py)
+# D-24 / D-56 (two conv+BN+ReLU units in layer7 and layer8), seeds chosen on the CPU from the oracle alone:
+#  * D-24, seed 5: the oracle's own fp32 CPU gradients are 4.0e-6 rel-L2 (worst parameter, layer.2.1.bias)
+#    from its fp64 ones on this case (seeds 5 .. 8 tried: 4.0e-6, 1.3e-2, 4.4e-6, 1.1e-5), far inside the
+#    2.5e-4 a case may spend of the 1e-3 gate;
+#  * D-56, seed 7: tol = 4 x 4.75e-3 = 1.9e-2, 4.75e-3 being the rel-L2 of the oracle's fp32 CPU gradients
+#    from its fp64 ones, worst over parameters (layer.6.2.conv1.weight): pre-activations within an ulp
+#    of zero, as on D-54.  Seeds 5 .. 7 tried: 5.47e-3 (4 x that exceeds D-54's 2e-2), 1.2e-5, 4.75e-3.
+#    Seed 6 is the one seed of the three on which torch's fp32 order happens to flip no ReLU; two in
+#    three do, so another valid fp32 order (ours) may flip one there as well, and a tolerance of 4 x
+#    rounding noise would gate on that luck, not on the kernels -- the first seed whose figure shows the
+#    architecture's flips and stays within D-54's bound is taken.  (Every launch of a D-56 step is held
+#    to fp64 without that slack in tests/train_audit.py d56_fp32x_1x64x64.)
 @pytest.mark.parametrize("arch,seed,shape,tol", [("drn_d_38", 2, (1, 3, 64, 64), 1e-3),
                                                  ("drn_d_54", 3, (2, 3, 128, 128), 2e-2),
-                                                 ("drn_d_22", 4, (1, 3, 72, 40), 1e-3)])
+                                                 ("drn_d_22", 4, (1, 3, 72, 40), 1e-3),
+                                                 ("drn_d_24", 5, (1, 3, 72, 40), 1e-3),
+                                                 ("drn_d_56", 7, (1, 3, 64, 64), 1.9e-2)])
 def test_train_step_matches_oracle(arch, seed, shape, tol):
     from drnmi.drnseg import DRNSeg
     from drnmi.weights import synth_state_dict
@@ -443,3 +457,46 @@ def test_sgd_matches_torch(nesterov, damp):
         o.step()
     for r, q in zip(ref, mine):
         assert TC.rel_err(q.detach().cpu(), r.detach()) <= 1e-6
+
+
+def test_sgd_matches_torch_100_tensors_masked():
+    """100 small tensors, every third with a pruner mask: three 48-tensor launches, the last ragged (4
+    tensors), masked and unmasked parameters mixed in each -- the batching a 109 / 111-conv net's step
+    goes through (about 7 launches) -- against torch.optim.SGD followed by the mask multiply."""
+    from drnmi import pruners as P
+    from drnmi.train import SGD
+
+    class Masks(P.Pruner):
+        def parse_config_file(self, config_fp):
+            return []
+
+    torch.manual_seed(3)
+    shapes = [(1 + i % 7, 3 + i % 5) if i % 2 else (5 + 11 * (i % 9),) for i in range(100)]
+    ps = [torch.randn(*s) for s in shapes]
+    masks = {i: (torch.rand(*shapes[i]) < 0.5).float() for i in range(0, 100, 3)}
+    ref = [p.clone().requires_grad_(True) for p in ps]
+    model = torch.nn.Module()
+    model.ps = torch.nn.ParameterList([torch.nn.Parameter(p.clone().to(DEV)) for p in ps])
+    mine = list(model.ps)
+    pr = Masks(None, on_gpu=True)
+    for i, mk in masks.items():
+        pr.mask_dict[f"ps.{i}"] = mk.to(DEV)
+    kw = dict(lr=0.05, momentum=0.9, dampening=0.0, weight_decay=1e-3, nesterov=False)
+    o_ref = torch.optim.SGD(ref, **kw)
+    o = SGD(mine, pruner=pr, model=model, **kw)
+    assert len(o._mask_of) == 34
+    for step in range(3):
+        gs = [torch.randn_like(p) for p in ps]
+        for r, q, gg in zip(ref, mine, gs):
+            r.grad = gg.clone()
+            q.grad = gg.to(DEV)
+        o_ref.step()
+        with torch.no_grad():
+            for i, mk in masks.items():
+                ref[i].mul_(mk)
+        o.step()
+    for i, (r, q) in enumerate(zip(ref, mine)):
+        assert TC.rel_err(q.detach().cpu(), r.detach()) <= 1e-6, i
+        if i in masks:
+            assert bool((q.detach().cpu()[masks[i] == 0] == 0).all()), i
+            assert TC.rel_err(o.state[q]["momentum_buffer"].cpu(), o_ref.state[r]["momentum_buffer"]) <= 1e-6, i

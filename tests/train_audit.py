@@ -41,6 +41,10 @@ CONFIGS = {
     "d54_fp32_2x96x64": ("drn_d_54", "fp32", (2, 3, 96, 64), 1),
     "d54_fp32x_2x96x64": ("drn_d_54", "fp32x", (2, 3, 96, 64), 1),
     "d22_fp32x_2x64x64_acc": ("drn_d_22", "fp32x", (2, 3, 64, 64), 2),
+    # two conv+BN+ReLU units in layer7 and layer8 (BasicBlock and Bottleneck trunks)
+    "d24_fp32_1x72x40": ("drn_d_24", "fp32", (1, 3, 72, 40), 1),
+    "d24_fp32x_1x72x40": ("drn_d_24", "fp32x", (1, 3, 72, 40), 1),
+    "d56_fp32x_1x64x64": ("drn_d_56", "fp32x", (1, 3, 64, 64), 1),
 }
 # every kind a record may have; each has exactly one check below
 NODE_KINDS = ("conv", "bn_stats", "bn_act", "seg_nhwc", "bias_grad", "bn_bwd", "wgrad", "dgrad")

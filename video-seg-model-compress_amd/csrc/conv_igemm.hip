@@ -16,8 +16,10 @@
 //     drnmi_conv_args.ws (the training plan: the fine-tune's forward and data-gradient convs) folds
 //     the chain into a second accumulator every 256 k (kFoldSteps) from K = 1024 on: one chain over
 //     K = 4608 erred up to 10 x a blocked fp32 sum against float64 (profiles/train_audit), the
-//     folded one ~1.5 x.  Inference launches (ws = NULL) and shorter K keep the single chain, bit
-//     for bit: the fp32 mode's labels are pinned against the reference in that order.
+//     folded one ~1.5 x.  K = 512 .. 1023 folds every 128 k (kFoldShortSteps): one chain over K = 576
+//     errs ~3.5 x on average and was measured at 5.3 x on a D-24 layer3 data gradient, the folded
+//     one 0.5 x.  Inference launches (ws = NULL) and K < 512 keep the single chain, bit for bit:
+//     the fp32 mode's labels are pinned against the reference in that order.
 // The per-lane K permutation (lane holds k = 8*(lane>>4) + j) is identical for A and B,
 // so one LDS image and one fragment read serve both MFMA shapes.
 //
@@ -34,7 +36,9 @@ namespace {
 constexpr int kBK = 32;
 constexpr int kThreads = 256;
 constexpr int kFoldSteps = 8;       // fp32 mode: K steps per chain before it is folded (256 k)
-constexpr int kFoldMinSteps = 32;   // ... in a training launch of at least this many K steps (K >= 1024)
+constexpr int kFoldLongSteps = 32;  // ... in a training launch of at least this many K steps (K >= 1024);
+constexpr int kFoldShortSteps = 4;  // a shorter one folds every 128 k
+constexpr int kFoldMinSteps = 16;   // ... from this many K steps on (K >= 512)
 
 template <typename T>
 __device__ __forceinline__ void mma_step(f32x4& acc, const T* a, const T* b);
@@ -207,6 +211,7 @@ conv_igemm_kernel(const drnmi_conv_args p) {
 
   const int nk = p.k_pad / kBK;
   const bool fold = kFold && p.ws != nullptr && nk >= kFoldMinSteps;
+  const int fold_mask = (nk >= kFoldLongSteps ? kFoldSteps : kFoldShortSteps) - 1;
   load_tiles(0);
   store_tiles(0);
   __syncthreads();
@@ -229,7 +234,7 @@ conv_igemm_kernel(const drnmi_conv_args p) {
       }
     }
     if constexpr (kFold) {
-      if (fold && (kt % kFoldSteps == kFoldSteps - 1 || !more)) {
+      if (fold && ((kt & fold_mask) == fold_mask || !more)) {
 #pragma unroll
         for (int fm = 0; fm < FM; ++fm)
 #pragma unroll

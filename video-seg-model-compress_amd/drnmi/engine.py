@@ -61,7 +61,9 @@ INT8_LAYER4 = True
 # int8 tile they replace, by more than the spread of the dense repeats, in both recorded runs
 # (profiles/sp24_i8/README.txt): D-22's layer5, layer6 and layer7 launches.  Not listed: the 128 -> 128
 # launches and the seg 1x1 (slower sparse), and layer8's 512 -> 512 dilation-1 launch, which gains alone
-# but would give up the seg-fused launch for no measured gain of the step.
+# but would give up the seg-fused launch for no measured gain of the step.  (The list is by shape: in the
+# variants with two units in layer8 -- D-24 / 40 / 56 / 107 -- layer.8.0 has that shape without being the
+# seg-fused producer and stays dense with it, unmeasured; tests/test_gpu_drn_d_variants.py.)
 # SP24_I8_EVERY routes every eligible layer sparse (tests, A/B runs): the outputs are the same bits.
 SP24_I8_SHAPES = frozenset({(128, 256, 3, 1, 2), (128, 256, 1, 1, 1), (256, 256, 3, 1, 2), (256, 512, 3, 1, 4),
                             (256, 512, 1, 1, 1), (512, 512, 3, 1, 4), (512, 512, 3, 1, 2)})
