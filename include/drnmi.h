@@ -97,7 +97,7 @@ enum drnmi_sp24_tile { DRNMI_SP24_GATHER = 0, DRNMI_SP24_STRIP = 1 };
 
 /* DRNMI_I8_SP24 (conv dtype only; inference, opt-in: DRNSeg.set_sparse24 at precision "int8"): a DRNMI_I8
  * launch whose weights are 2:4 along the input channels of a tap (the groups of DRNMI_BF16_SP24), run on
- * v_smfmac_i32_16x16x128_i8 (csrc/conv_sp24_i8.hip).  Added under ABI version 7: a new enum value and
+ * v_smfmac_i32_16x16x128_i8 (csrc/conv_sp24.hip).  Added under ABI version 7: a new enum value and
  * three new symbols, drnmi_conv_args unchanged, so callers built against the earlier version-7 header
  * keep working (backward compatible).  The contract is DRNMI_I8's exactly: x and res int8 NHWC, scale
  * non-NULL, res_scale, ReLU, out_scale, output DRNMI_I8 (NHWC), DRNMI_BF16 or DRNMI_F32 at any strides;
@@ -372,7 +372,7 @@ int drnmi_sp24_mma_probe(const void* a, const void* b, const uint32_t* idx, floa
  * v_smfmac_f32_16x16x64_bf16, else v_mfma_f32_16x16x32_bf16.  sink: blocks x 256 floats. */
 int drnmi_sp24_issue_probe(int32_t sparse, int32_t iters, int32_t blocks, float* sink, void* stream);
 
-/* 2:4 packing for DRNMI_I8_SP24 (csrc/conv_sp24_i8.hip), the rules of drnmi_sp24_pack on int8.  dense_i8:
+/* 2:4 packing for DRNMI_I8_SP24 (csrc/conv_sp24.hip), the rules of drnmi_sp24_pack on int8.  dense_i8:
  * packed int8 weights [rows_pad][k_pad] (rows_pad % 32 == 0, k_pad % 128 == 0, device memory); out: device
  * buffer of drnmi_sp24_pack_i8_bytes(rows_pad, k_pad) = rows_pad * k_pad * 5 / 8 bytes (-1 for other
  * sizes: half the values plus 2 bits per kept value), 16-B aligned, layout private to the kernel.  A zero

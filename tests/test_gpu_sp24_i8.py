@@ -1,5 +1,5 @@
 """2:4 weight sparsity at int8 on v_smfmac_i32_16x16x128_i8 (include/drnmi.h DRNMI_I8_SP24,
-csrc/conv_sp24_i8.hip) on the GPU: the instruction's operand map, the packer, every launch bit for bit
+csrc/conv_sp24.hip) on the GPU: the instruction's operand map, the packer, every launch bit for bit
 against oracle/int8_oracle.conv_i8 on the dense masked weights, and a 2:4-pruned, calibrated D-22 whose
 labels must equal the dense int8 network's.
 

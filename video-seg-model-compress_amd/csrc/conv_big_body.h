@@ -1,7 +1,7 @@
 // conv_big_body: the LDS-DMA implicit-GEMM tile of conv_big.hip (its header comment describes the
 // structure), one template over the element types of conv_tile.h KT<T>: bf16, int8 and fp8.  Internal
-// header (anonymous namespace, as conv_tile.h).  The 2:4 tile of conv_sp24.hip keeps its own main loop
-// and shares this body's gather pieces through conv_tile.h (profiles/sp24_fold/README.txt).
+// header (anonymous namespace, as conv_tile.h).  The 2:4 tiles of conv_sp24.hip (bf16 and int8, one body)
+// keep their own main loop and share this body's gather pieces through conv_tile.h (profiles/sp24_fold/README.txt).
 #pragma once
 #include "common.h"
 #include "conv_tile.h"

@@ -184,34 +184,22 @@ ConvRoute q8_route(const drnmi_conv_args& p) {
   return take(&v.k[ks3]);
 }
 
-// --- the 2:4 weight-sparse bf16 tiles (DRNMI_BF16_SP24, conv_sp24.hip).  tile is this dtype's own
-// variant (enum drnmi_sp24_tile).  The strip-staged form takes conv_strip_kernel's geometry on the
-// 256 x 256 tile and is a forced variant only: with the MFMA time of a K step halved, its two-stage ring
-// that waits for all of a step's DMA measured slower than the gather's three counted stages at
-// cin 512 (758 vs 707 us) and equal at cin 256 (profiles/sp24), so auto is the gather everywhere
+// --- the 2:4 weight-sparse tiles (DRNMI_BF16_SP24 / DRNMI_I8_SP24, conv_sp24.hip), one route; the int8 contract
+// (a non-NULL scale, the 8-bit epilogue) is sp24_conv_supported's.  tile is these dtypes' own variant (enum
+// drnmi_sp24_tile).  The strip-staged form takes conv_strip_kernel's geometry on the 256 x 256 tile and is a
+// forced variant only: with the MFMA time of a K step halved, its two-stage ring that waits for all of a
+// step's DMA measured slower than the gather's three counted stages at cin 512 (758 vs 707 us) and equal at
+// cin 256 (profiles/sp24; int8: profiles/sp24_i8/README.txt), so auto is the gather everywhere.
+// (The strip tile's rows always exist: cout_pad % 256 == 0 and conv_route() has refused cout > cout_pad.)
 ConvRoute sp24_route(const drnmi_conv_args& p) {
   if (p.tile != DRNMI_TILE_AUTO && p.tile != DRNMI_SP24_GATHER && p.tile != DRNMI_SP24_STRIP) return refuse(DRNMI_EINVAL);
   if (!sp24_conv_supported(p)) return refuse(DRNMI_ENOTSUP);
   const bool tile128 = p.cout_pad % 256 != 0 || p.cout <= 128;
   const bool strip = !tile128 && strip_ok(p);
   if (p.tile == DRNMI_SP24_STRIP && !strip) return refuse(DRNMI_ENOTSUP);
-  if (p.tile == DRNMI_SP24_STRIP) return take(sp24_strip_kernel());
   if (!rows_exist(p, tile128 ? 128 : 256)) return refuse(DRNMI_EINVAL);
-  return take(sp24_kernel(tile128, p.ks));
-}
-
-// --- the 2:4 weight-sparse int8 tiles (DRNMI_I8_SP24, conv_sp24_i8.hip): sp24_route's decisions on the
-// int8 contract (a non-NULL scale, the 8-bit epilogue).  Auto is the gather; the strip-staged form is a
-// forced variant (profiles/sp24_i8/README.txt)
-ConvRoute sp24_i8_route(const drnmi_conv_args& p) {
-  if (p.tile != DRNMI_TILE_AUTO && p.tile != DRNMI_SP24_GATHER && p.tile != DRNMI_SP24_STRIP) return refuse(DRNMI_EINVAL);
-  if (!sp24_i8_conv_supported(p)) return refuse(DRNMI_ENOTSUP);
-  const bool tile128 = p.cout_pad % 256 != 0 || p.cout <= 128;
-  const bool strip = !tile128 && strip_ok(p);
-  if (p.tile == DRNMI_SP24_STRIP && !strip) return refuse(DRNMI_ENOTSUP);
-  if (!rows_exist(p, tile128 ? 128 : 256)) return refuse(DRNMI_EINVAL);
-  if (p.tile == DRNMI_SP24_STRIP) return take(sp24_i8_strip_kernel());
-  return take(sp24_i8_kernel(tile128, p.ks));
+  if (p.tile == DRNMI_SP24_STRIP) return take(sp24_strip_kernel(p.dtype));
+  return take(sp24_kernel(p.dtype, tile128, p.ks));
 }
 
 // --- conv_x6.  A drnmi_conv_args.tile >= 0 forces variant tile % 6 and, when tile >= 6, tile / 6
@@ -363,8 +351,7 @@ ConvRoute conv_route(const drnmi_conv_args& p) {
   if (p.y_sr == 0 && !conv_geometry(p)) return refuse(DRNMI_EINVAL);
   if (p.dtype == DRNMI_I8 || p.dtype == DRNMI_F8) return q8_route(p);       // 8-bit: one kernel family
   if (p.dtype == DRNMI_F32X3) return x6_route(p);
-  if (p.dtype == DRNMI_BF16_SP24) return sp24_route(p);
-  if (p.dtype == DRNMI_I8_SP24) return sp24_i8_route(p);
+  if (p.dtype == DRNMI_BF16_SP24 || p.dtype == DRNMI_I8_SP24) return sp24_route(p);
   if (p.tile >= DRNMI_TILE_DMA128 || (p.tile < 0 && (big_conv_supported(p) || halo_conv_supported(p)))) return big_route(p);
   if (p.x2 != nullptr) return refuse(DRNMI_ENOTSUP);          // fused second input: LDS-DMA kernels only
   const int tile = p.tile < 0 ? auto_tile(p.cout) : p.tile;

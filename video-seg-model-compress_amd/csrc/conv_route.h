@@ -87,16 +87,13 @@ const ConvKernel* w1_kernel(bool i8, bool x2);          // i8: no x2 form
 const ConvKernel* w1h_kernel(bool i8, bool x2);
 const SegKernel* w1_seg_kernel(bool i8);
 
-// conv_sp24.hip: the 2:4 weight-sparse bf16 tiles (dtype DRNMI_BF16_SP24), 256 x 256 or 128 x 256
+// conv_sp24.hip: the 2:4 weight-sparse tiles, bf16 (dtype DRNMI_BF16_SP24, cin >= 64) and int8 (DRNMI_I8_SP24,
+// cin >= 128, the int8 route's contract), 256 x 256 or 128 x 256
 bool sp24_conv_supported(const drnmi_conv_args& p);
 // conv_big.hip: the size and shape terms common to big_conv_supported, q8_conv_supported and sp24_conv_supported
 bool big_body_shape_ok(const drnmi_conv_args& p, int min_cin);
-const ConvKernel* sp24_kernel(bool tile128, int ks);
-const ConvKernel* sp24_strip_kernel();           // 3x3 stride 1, wo % 256 == 0, the 256 x 256 tile (strip_ok)
-// conv_sp24_i8.hip: the 2:4 weight-sparse int8 tiles (dtype DRNMI_I8_SP24), cin >= 128, the same two tiles
-bool sp24_i8_conv_supported(const drnmi_conv_args& p);
-const ConvKernel* sp24_i8_kernel(bool tile128, int ks);
-const ConvKernel* sp24_i8_strip_kernel();        // strip_ok on the 256 x 256 tile, as sp24_strip_kernel
+const ConvKernel* sp24_kernel(int dtype, bool tile128, int ks);
+const ConvKernel* sp24_strip_kernel(int dtype);  // 3x3 stride 1, wo % 256 == 0, the 256 x 256 tile (strip_ok)
 
 // conv_halo.hip: halo-patch 3x3 stride-1 conv, cin / cout 64 or 128
 bool halo_conv_supported(const drnmi_conv_args& p);

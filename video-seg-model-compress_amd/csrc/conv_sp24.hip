@@ -1,36 +1,55 @@
-// 2:4 weight-sparse NHWC implicit-GEMM convolution, bf16, on v_smfmac_f32_16x16x64_bf16
-// (dtype DRNMI_BF16_SP24, include/drnmi.h: inference, opt-in through DRNSeg.set_sparse24).
+// 2:4 weight-sparse NHWC implicit-GEMM convolution, one family over the element type (Sp24<T> below):
+//   bf16  on v_smfmac_f32_16x16x64_bf16 (dtype DRNMI_BF16_SP24, include/drnmi.h: inference, opt-in through
+//         DRNSeg.set_sparse24),
+//   int8  (W8A8) on v_smfmac_i32_16x16x128_i8 (dtype DRNMI_I8_SP24: the same at precision "int8").
 //
 // conv_big.hip's per-tap gather with the sparse MFMA in place of two dense ones: A = weights with at
 // most two non-zeros in every four consecutive input channels of a tap, stored compressed (the kept
-// values + 2-bit positions, drnmi_sp24_pack), B = pixels, dense.  conv_sp24_body is a main loop of its
-// own, written out next to conv_big_body (conv_big_body.h): as one template over a fourth element type the
-// sparse kernels lost their schedule (profiles/sp24_fold/README.txt).  From conv_tile.h, one copy for both:
+// values + 2-bit positions, drnmi_sp24_pack / drnmi_sp24_pack_i8), B = pixels, dense.  conv_sp24_body is a
+// main loop of its own, written out next to conv_big_body (conv_big_body.h): as one template over a fourth
+// element type of that body the sparse kernels lost their schedule (profiles/sp24_fold/README.txt); the two
+// element types of this body share it (profiles/sp24_twins/README.txt).  bf16 starts from shift + residual
+// and ends in store_tile / store_tile_x4; int8 has int32 accumulators and the dense int8 epilogue
+// (store_tile_q8 / store_tile_q8_x4): the DRNMI_I8 contract.  Integer sums are exact, so an int8 launch
+// equals the dense int8 launch on the same (masked) weights bit for bit.  From conv_tile.h, one copy for all:
 // the swizzles, glds16 / glds4, the XCD-major tile deal, the strip source (strip_src), the strip geometry,
-// init_tile / store_tile / store_tile_x4.  Built with VGPR-form MFMAs (build.py).
+// init_tile / zero_tile and the epilogues.  Built with VGPR-form MFMAs (build.py).
 //
-// Operand map of the instruction (measured, tests/test_gpu_sp24.py::test_operand_map), lane = 16 fq + fr:
+// Operand map of the bf16 instruction (measured, tests/test_gpu_sp24.py::test_operand_map), lane = 16 fq + fr:
 //   A  lane holds row fr's 8 kept values of dense k 16 fq .. 16 fq + 15: slots (2 g, 2 g + 1) are the
 //      kept pair of group g = k 16 fq + 4 g .. + 3, in ascending position;
 //   idx bits [2 s + 1 : 2 s] of the 16-bit half ABID selects = slot s's position inside its group;
 //   B  lane holds column fr's k 8 fq .. 8 fq + 7 (elements 0-7) and 32 + 8 fq .. + 7 (elements 8-15):
 //      two v_mfma_f32_16x16x32_bf16 B fragments side by side;
 //   D  as the dense 16x16 MFMAs: lane holds rows 4 fq .. 4 fq + 3 of column fr.
+// Of the int8 instruction (measured, tests/test_gpu_sp24_i8.py::test_operand_map):
+//   A  lane holds row fr's 16 kept values of dense k 32 fq .. 32 fq + 31: bytes (2 g, 2 g + 1) are the
+//      kept pair of group g = k 32 fq + 4 g .. + 3, in ascending position;
+//   idx the whole 32-bit register: bits [2 s + 1 : 2 s] = byte s's position inside its group (ABID unused);
+//   B  lane holds column fr's k 16 fq .. 16 fq + 15 (bytes 0-15) and 64 + 16 fq .. + 15 (bytes 16-31):
+//      two v_mfma_i32_16x16x64_i8 B fragments side by side;
+//   D  as above.
 //
-// K step = 64 dense channels of one tap.  LDS image of a stage (3 stages):
-//   A values  BCO rows x 64 B (32 kept values in channel order), 16-B chunk c of row r at slot
+// K step = 64 (bf16) / 128 (int8, so cin >= 128) dense channels of one tap.  LDS image of a stage (3 stages):
+//   A values  BCO rows x 64 B (32 / 64 kept values in channel order), 16-B chunk c of row r at slot
 //             swzb<64>(r, c): lane (fr, fq) reads chunk fq, the 64-B-row fragment read of conv_big's
 //             BK-32 tiles, conflict-free for the reason given at swzb;
-//   A index   BCO / 32 blocks of 64 words: word 16 fq + fr of block f2 holds the 16 index bits of row
-//             32 f2 + fr (low half) and of row 32 f2 + 16 + fr (high half) for k 16 fq .. + 15, so a
-//             wave reads 64 consecutive words (one ds_read_b32 per fragment pair: no two lanes of a
-//             32-lane half on one bank) and the pair's two MFMAs take ABID 0 and 1 of one register;
+//   A index   blocks of 64 words, a wave reads 64 consecutive words (no two lanes of a 32-lane half on one
+//             bank).  bf16: BCO / 32 blocks, word 16 fq + fr of block f2 holds the 16 index bits of row
+//             32 f2 + fr (low half) and of row 32 f2 + 16 + fr (high half) for k 16 fq .. + 15: one
+//             ds_read_b32 per fragment pair, whose two MFMAs take ABID 0 and 1 of one register.
+//             int8: BCO / 16 blocks, word 16 fq + fr of block f holds the 32 index bits of row 16 f + fr
+//             for k 32 fq .. + 31: one read per fragment;
 //   B         256 pixel rows x 128 B with conv_big's 128-B swizzle: lane (fr, fq) reads chunks fq and
 //             4 + fq, the dense kernel's two conflict-free substep reads, as one 32-B fragment.
-// 256 x 256 tile (8 waves): 16 + 2 + 32 KB per stage; 128 x 256 (4 waves): 8 + 1 + 32 KB.
-// The blob (private to this file): the value plane [cout_pad][k_pad / 2] bf16, then the index plane
-// [cout_pad / 32][k_pad / 64][64] words in the LDS order above, so a K step's index block of 32 rows
-// is one 256-B DMA (global_load_lds_dword) by the wave with that number.
+// 256 x 256 tile (8 waves): 16 + 2 + 32 KB per stage (int8: 16 + 4 + 32); 128 x 256 (4 waves): 8 + 1 + 32 KB
+// (int8: 8 + 2 + 32).
+// The blob (private to this file): the value plane [cout_pad][k_pad / 2] of T, then the index plane in the LDS
+// order above, bf16 [cout_pad / 32][k_pad / 64][64] words, int8 [cout_pad / 16][k_pad / 128][64] words, so a
+// K step's index block is one 256-B DMA (global_load_lds_dword): bf16 the block with the wave's number, int8
+// the two blocks 2 wave and 2 wave + 1.
+#include <type_traits>
+
 #include "common.h"
 #include "conv_tile.h"
 #include "kernels.h"
@@ -40,9 +59,42 @@ namespace {
 
 typedef __bf16 bf16x16 __attribute__((ext_vector_type(16)));
 
-template <int WCO, int WC>
-struct Sp24Cfg {
+// What the element type decides.  The MFMA loop nest with its (word, ABID) convention, the accumulator start
+// and the epilogue are `if constexpr (Sp24<T>::I8)` in the body, where each type's statements stand as they
+// did in its own file: as trait methods they moved registers (profiles/sp24_twins/README.txt).
+template <typename T> struct Sp24;
+template <> struct Sp24<uint16_t> {
+  static constexpr bool I8 = false;
   static constexpr int BK = 64;                     // dense channels per K step
+  static constexpr int CE = 8;                      // elements per 16-B chunk
+  static constexpr int IROWS = 32;                  // weight rows of a 256-B index block
+  static constexpr int IW = 1;                      // index words per fragment pair
+  typedef bf16x8 afrag;
+  typedef bf16x16 bfrag;
+  typedef f32x4 acc;
+  __device__ __forceinline__ static bfrag join(afrag lo, afrag hi) {
+    return __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15);
+  }
+  __device__ __forceinline__ static bool is_zero(uint16_t v) { return (v & 0x7fff) == 0; }
+};
+template <> struct Sp24<int8_t> {
+  static constexpr bool I8 = true;
+  static constexpr int BK = 128;
+  static constexpr int CE = 16;
+  static constexpr int IROWS = 16;
+  static constexpr int IW = 2;
+  typedef i32x4 afrag;
+  typedef i32x8 bfrag;
+  typedef i32x4 acc;
+  __device__ __forceinline__ static bfrag join(afrag lo, afrag hi) {
+    return __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
+  }
+  __device__ __forceinline__ static bool is_zero(int8_t v) { return v == 0; }
+};
+
+template <typename T, int WCO, int WC>
+struct Sp24Cfg {
+  static constexpr int BK = Sp24<T>::BK;
   static constexpr int NST = 3;
   static constexpr int BCO = WCO * WC;
   static constexpr int FM = WCO / 16;
@@ -50,29 +102,33 @@ struct Sp24Cfg {
   static constexpr int NW = 4 * WC;
   static constexpr int THREADS = 64 * NW;
   static constexpr int A_BYTES = BCO * 64;          // kept values: 64-B rows
-  static constexpr int I_BYTES = BCO * 8;           // positions: 2 bits per kept value
+  static constexpr int I_BYTES = BCO * BK / 8;      // positions: 2 bits per kept value
   static constexpr int B_BYTES = kBPX * 128;
   static constexpr int STAGE = A_BYTES + I_BYTES + B_BYTES;
   static constexpr int A_INSTR = BCO / 16 / NW;     // 1-KB pieces (16 rows) per wave per step
+  static constexpr int I_INSTR = 32 / Sp24<T>::IROWS;   // 256-B index blocks per wave per step
   static constexpr int B_INSTR = kBPX / 8 / NW;     // 1-KB pieces (8 rows)
-  static constexpr int GLDS = A_INSTR + 1 + B_INSTR;
+  static constexpr int GLDS = A_INSTR + I_INSTR + B_INSTR;
   static constexpr int LDS = NST * STAGE;
   static constexpr int GR = FM / 2;                 // MFMA groups per step: one fragment pair each
-  static_assert(BCO / 32 == NW, "one 32-row index block per wave");
+  static_assert(BCO / Sp24<T>::IROWS == I_INSTR * NW && I_BYTES == I_INSTR * NW * 256, "index blocks per wave");
   static_assert(LDS <= 160 * 1024, "LDS");
 };
 
 // STRIP (3x3 stride 1, wo % 256 == 0, the 256 x 256 tile): conv_big's strip-staged B.  The three kw taps
-// of one (64-channel block, kh) read one strip of 256 + 2 dil pixel rows at row offset kw * dil, staged
+// of one (BK-channel block, kh) read one strip of 256 + 2 dil pixel rows at row offset kw * dil, staged
 // once per three K steps into one of two strip buffers (conv_tile.h kStripBytes) in five shares per wave;
 // A (values + index) rides a two-stage ring and every step waits for all of its DMA, as conv_strip_kernel.
 // Same K order and MFMAs as the gather form: bit-identical.
-template <int KS, int WCO, int WC, bool STRIP = false>
+template <typename T, int KS, int WCO, int WC, bool STRIP = false>
 __device__ __forceinline__ void conv_sp24_body(const drnmi_conv_args& p) {
-  using C = Sp24Cfg<WCO, WC>;
+  using S = Sp24<T>;
+  using C = Sp24Cfg<T, WCO, WC>;
+  using afrag = typename S::afrag;
   constexpr int NST = STRIP ? 2 : C::NST, BK = C::BK;
   static_assert(!STRIP || (KS == 3 && C::NW == 8), "strip mode: the 256 x 256 3x3 tile");
   constexpr int STAGE = STRIP ? C::A_BYTES + C::I_BYTES : C::STAGE;   // strip: the ring holds A only
+  constexpr int AI = C::A_INSTR + C::I_INSTR;                         // A pieces of a step: values, then index
   extern __shared__ __attribute__((aligned(16))) char smem[];
 
   const int tid = threadIdx.x;
@@ -89,10 +145,10 @@ __device__ __forceinline__ void conv_sp24_body(const drnmi_conv_args& p) {
   const int cin = p.cin;
   const int lc = 31 - __builtin_clz(cin);
   const int H = p.h, W = p.w, dil = p.dil;
-  const uint16_t* __restrict__ x = reinterpret_cast<const uint16_t*>(p.x);
+  const T* __restrict__ x = reinterpret_cast<const T*>(p.x);
   const int kh2 = p.k_pad / 2;                      // kept values per weight row
   const int nk = p.k_pad / BK;
-  const uint16_t* __restrict__ vals = reinterpret_cast<const uint16_t*>(p.wgt);
+  const T* __restrict__ vals = reinterpret_cast<const T*>(p.wgt);
   const uint32_t* __restrict__ idxp = reinterpret_cast<const uint32_t*>(vals + static_cast<int64_t>(p.cout_pad) * kh2);
   const int fr = lane & 15;
   const int fq = lane >> 4;
@@ -102,14 +158,14 @@ __device__ __forceinline__ void conv_sp24_body(const drnmi_conv_args& p) {
   const int co0 = (tile % nco) * C::BCO;
 
   // --- DMA assignment.  A values: lane l fills row l / 4, slot l % 4 of a 16-row piece; index: the
-  // wave's own 32-row block, lane l its word l; pixels: row l / 8, slot l % 8 of an 8-row piece
+  // wave's own I_INSTR blocks, lane l its word l; pixels: row l / 8, slot l % 8 of an 8-row piece
   int a_off[C::A_INSTR];
 #pragma unroll
   for (int i = 0; i < C::A_INSTR; ++i) {
     const int r = (wave * C::A_INSTR + i) * 16 + (lane >> 2);
-    a_off[i] = (co0 + r) * kh2 + swzb<64>(r, lane & 3) * 8;
+    a_off[i] = (co0 + r) * kh2 + swzb<64>(r, lane & 3) * S::CE;
   }
-  const int i_off = ((co0 >> 5) + wave) * nk * 64 + lane;
+  const int i_off = ((co0 >> __builtin_ctz(S::IROWS)) + wave * C::I_INSTR) * nk * 64 + lane;
   // pixel rows as conv_big: (ih0, iw0) of tap (0,0) as two int16 and the element offset of that tap's chunk
   uint32_t b_hw[C::B_INSTR];
   int b_off[C::B_INSTR];
@@ -128,7 +184,7 @@ __device__ __forceinline__ void conv_sp24_body(const drnmi_conv_args& p) {
       const int ih0 = oh * p.stride - p.pad;
       const int iw0 = ow * p.stride - p.pad;
       b_hw[i] = (static_cast<uint32_t>(ih0) << 16) | (static_cast<uint32_t>(iw0) & 0xffffu);
-      b_off[i] = ((n * H + ih0) * W + iw0) * cin + swzb<128>(r, lane & 7) * 8;
+      b_off[i] = ((n * H + ih0) * W + iw0) * cin + swzb<128>(r, lane & 7) * S::CE;
     }
   }
 
@@ -144,15 +200,21 @@ __device__ __forceinline__ void conv_sp24_body(const drnmi_conv_args& p) {
     sp.toff = (static_cast<int64_t>(sp.dh) * W + sp.dw) * cin + cb * BK;
     return sp;
   };
-  // pieces [0, A_INSTR) kept values, A_INSTR the index block, then pixel rows
+  // pieces [0, A_INSTR) kept values, then the index blocks, then pixel rows
   auto issue_piece = [&](const StepP& sp, int stage, int i) {
     char* sa = smem + stage * STAGE;
     if (i < C::A_INSTR) {
       glds16(vals + (a_off[i] + (sp.k0 >> 1)), sa + (wave * C::A_INSTR + i) * 1024);
-    } else if (i == C::A_INSTR) {
-      glds4(idxp + (i_off + (sp.k0 >> 6) * 64), sa + C::A_BYTES + wave * 256);
+    } else if (i < AI) {
+      // block j of the wave's, nk blocks apart.  (One block: written without the j * nk term, which even folded
+      // to zero exchanges two scalar registers of conv_sp24_strip_kernel, profiles/sp24_twins/README.txt.)
+      const int j = i - C::A_INSTR;
+      if constexpr (C::I_INSTR == 1)
+        glds4(idxp + (i_off + (sp.k0 >> __builtin_ctz(BK)) * 64), sa + C::A_BYTES + (wave * C::I_INSTR + j) * 256);
+      else
+        glds4(idxp + (i_off + (j * nk + (sp.k0 >> __builtin_ctz(BK))) * 64), sa + C::A_BYTES + (wave * C::I_INSTR + j) * 256);
     } else if constexpr (!STRIP) {
-      const int j = i - C::A_INSTR - 1;
+      const int j = i - AI;
       const int ih0 = static_cast<int>(b_hw[j]) >> 16;
       const int iw0 = static_cast<int16_t>(b_hw[j] & 0xffffu);
       const bool ok = static_cast<unsigned>(ih0 + sp.dh) < static_cast<unsigned>(H) &&
@@ -174,17 +236,18 @@ __device__ __forceinline__ void conv_sp24_body(const drnmi_conv_args& p) {
     const int j = wave + 8 * sh;
     if (j >= kStripPieces) return;                 // wave-uniform
     const int R = j * 8 + (lane >> 3);
-    const void* src = strip_src<BK, 8>(p, x, g, R, lane & 7, s_n, s_oh, s_ow0, H, W, cin, dil, zero_src);
+    const void* src = strip_src<BK, S::CE>(p, x, g, R, lane & 7, s_n, s_oh, s_ow0, H, W, cin, dil, zero_src);
     glds16(src, strips + (g & 1) * kStripBytes + j * 1024);
   };
-  constexpr int GL = STRIP ? C::A_INSTR + 1 + 2 : C::GLDS;   // pieces a wave issues per step (strip: + two strip shares)
+  constexpr int GL = STRIP ? AI + 2 : C::GLDS;     // pieces a wave issues per step (strip: + two strip shares)
 
-  f32x4 acc[C::FM][C::FN];
-  init_tile<C::FM, WCO, C::FN>(p, acc, px0, co0, wc, wp, fr, fq);   // shift + residual (scale is NULL)
+  typename S::acc acc[C::FM][C::FN];
+  if constexpr (S::I8) zero_tile(acc);
+  else init_tile<C::FM, WCO, C::FN>(p, acc, px0, co0, wc, wp, fr, fq);   // shift + residual (scale is NULL)
   for (int t = 0; t < NST - 1 && t < nk; ++t) {
     const StepP sp = step_params(t);
 #pragma unroll
-    for (int i = 0; i < (STRIP ? C::A_INSTR + 1 : C::GLDS); ++i) issue_piece(sp, t, i);
+    for (int i = 0; i < (STRIP ? AI : C::GLDS); ++i) issue_piece(sp, t, i);
   }
   if constexpr (STRIP) {
 #pragma unroll
@@ -211,24 +274,29 @@ __device__ __forceinline__ void conv_sp24_body(const drnmi_conv_args& p) {
     // the next ring slot's step (clamped: the last steps re-fetch the last step into the idle stage)
     const StepP sp = step_params(t + NST - 1 < nk ? t + NST - 1 : nk - 1);
     const int nst = (t + NST - 1) % NST;
-    bf16x8 af[2][2];
-    uint32_t ix[2];
-    bf16x16 bfr[C::FN];
-    auto load_a = [&](bf16x8 (&dst)[2], uint32_t& w, int q) {
+    afrag af[2][2];
+    uint32_t ix[2][S::IW];
+    typename S::bfrag bfr[C::FN];
+    // fragment pair q of the wave's rows and its index word(s): int8 a word per fragment beside it, bf16 one
+    // for the pair.  (The row r is f * 16 + fr for both; each type keeps its own spelling of it, and int8 the
+    // local f: with the other's, three VGPRs moved in a strip kernel, profiles/sp24_twins/README.txt.)
+    auto load_a = [&](afrag (&dst)[2], uint32_t (&w)[S::IW], int q) {
 #pragma unroll
       for (int h = 0; h < 2; ++h) {
-        const int r = wc * WCO + (q * 2 + h) * 16 + fr;
-        dst[h] = *reinterpret_cast<const bf16x8*>(sa + r * 64 + swzb<64>(r, fq) * 16);
+        const int f = wc * C::FM + q * 2 + h;
+        const int r = S::I8 ? f * 16 + fr : wc * WCO + (q * 2 + h) * 16 + fr;
+        dst[h] = *reinterpret_cast<const afrag*>(sa + r * 64 + swzb<64>(r, fq) * 16);
+        if constexpr (S::IW == 2) w[h] = *reinterpret_cast<const uint32_t*>(si + f * 256 + lane * 4);
       }
-      w = *reinterpret_cast<const uint32_t*>(si + (wc * (WCO / 32) + q) * 256 + lane * 4);
+      if constexpr (S::IW == 1) w[0] = *reinterpret_cast<const uint32_t*>(si + (wc * (WCO / 32) + q) * 256 + lane * 4);
     };
 #pragma unroll
     for (int fn = 0; fn < C::FN; ++fn) {
       const int r = wp * 64 + fn * 16 + fr + kwd;
       const int z = STRIP ? (r & 7) : swzb<128>(r, 0);   // both swizzles are an XOR on the chunk number
-      const bf16x8 lo = *reinterpret_cast<const bf16x8*>(sb + r * 128 + (fq ^ z) * 16);
-      const bf16x8 hi = *reinterpret_cast<const bf16x8*>(sb + r * 128 + ((4 + fq) ^ z) * 16);
-      bfr[fn] = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15);
+      const afrag lo = *reinterpret_cast<const afrag*>(sb + r * 128 + (fq ^ z) * 16);
+      const afrag hi = *reinterpret_cast<const afrag*>(sb + r * 128 + ((4 + fq) ^ z) * 16);
+      bfr[fn] = S::join(lo, hi);
     }
     load_a(af[0], ix[0], 0);
 #pragma unroll
@@ -236,20 +304,31 @@ __device__ __forceinline__ void conv_sp24_body(const drnmi_conv_args& p) {
       // group q's fragments were issued a group ago (conv_big's schedule)
       if (q + 1 < C::GR) load_a(af[(q + 1) & 1], ix[(q + 1) & 1], q + 1);
       __builtin_amdgcn_sched_barrier(0);
+      // bf16: the pair shares one word, halves ABID 0 / 1; int8: a word per fragment.  (Each type's loop nest
+      // as its kernels were tuned: as one nest the other type's registers move, profiles/sp24_twins/README.txt.)
+      if constexpr (S::I8) {
 #pragma unroll
-      for (int fn = 0; fn < C::FN; ++fn)
-        acc[2 * q][fn] = __builtin_amdgcn_smfmac_f32_16x16x64_bf16(af[q & 1][0], bfr[fn], acc[2 * q][fn],
-                                                                   static_cast<int>(ix[q & 1]), 0, 0);
+        for (int h = 0; h < 2; ++h)
 #pragma unroll
-      for (int fn = 0; fn < C::FN; ++fn)
-        acc[2 * q + 1][fn] = __builtin_amdgcn_smfmac_f32_16x16x64_bf16(af[q & 1][1], bfr[fn], acc[2 * q + 1][fn],
-                                                                       static_cast<int>(ix[q & 1]), 0, 1);
+          for (int fn = 0; fn < C::FN; ++fn)
+            acc[2 * q + h][fn] = __builtin_amdgcn_smfmac_i32_16x16x128_i8(af[q & 1][h], bfr[fn], acc[2 * q + h][fn],
+                                                                          static_cast<int>(ix[q & 1][h]), 0, 0);
+      } else {
+#pragma unroll
+        for (int fn = 0; fn < C::FN; ++fn)
+          acc[2 * q][fn] = __builtin_amdgcn_smfmac_f32_16x16x64_bf16(af[q & 1][0], bfr[fn], acc[2 * q][fn],
+                                                                     static_cast<int>(ix[q & 1][0]), 0, 0);
+#pragma unroll
+        for (int fn = 0; fn < C::FN; ++fn)
+          acc[2 * q + 1][fn] = __builtin_amdgcn_smfmac_f32_16x16x64_bf16(af[q & 1][1], bfr[fn], acc[2 * q + 1][fn],
+                                                                         static_cast<int>(ix[q & 1][0]), 0, 1);
+      }
 #pragma unroll
       for (int k = 0; k < PPG; ++k) {
         const int i = q * PPG + k;
         if constexpr (STRIP) {
-          if (i <= C::A_INSTR) issue_piece(sp, nst, i);
-          else if (i < GL) issue_strip(sg, 2 * (t % 3) + (i - C::A_INSTR - 1));
+          if (i < AI) issue_piece(sp, nst, i);
+          else if (i < GL) issue_strip(sg, 2 * (t % 3) + (i - AI));
         } else {
           if (i < C::GLDS) issue_piece(sp, nst, i);
         }
@@ -258,57 +337,87 @@ __device__ __forceinline__ void conv_sp24_body(const drnmi_conv_args& p) {
     }
   }
 
-  // whole tile inside a dense bf16 NHWC output: 16-B stores (conv_tile.h store_tile_x4)
-  const bool x4 = p.out_dtype == DRNMI_BF16 && p.y_sc == 1 && p.y_sp == p.cout &&
-                  p.y_sn == static_cast<int64_t>(p.ho) * p.wo * p.cout && px0 + kBPX <= M && co0 + C::BCO <= p.cout;
-  if (x4) store_tile_x4<C::FM, WCO, C::FN>(p, acc, px0, co0, wc, wp, fr, fq);
-  else store_tile<C::FM, WCO, C::FN>(p, acc, px0, co0, wc, wp, fr, fq);
+  if constexpr (S::I8) {
+    // the dense int8 epilogue: whole tiles of a dense int8 NHWC output take the 16-B form (conv_big_body.h)
+    const bool x4 = q8_dense_x4<int8_t>(p) && px0 + kBPX <= M && co0 + C::BCO <= p.cout;
+    if (x4) store_tile_q8_x4<int8_t, C::FM, WCO, C::FN>(p, acc, px0, co0, wc, wp, fr, fq);
+    else store_tile_q8<int8_t, C::FM, WCO, C::FN>(p, acc, px0, co0, wc, wp, fr, fq);
+  } else {
+    // whole tile inside a dense bf16 NHWC output: 16-B stores (conv_tile.h store_tile_x4)
+    const bool x4 = p.out_dtype == DRNMI_BF16 && p.y_sc == 1 && p.y_sp == p.cout &&
+                    p.y_sn == static_cast<int64_t>(p.ho) * p.wo * p.cout && px0 + kBPX <= M && co0 + C::BCO <= p.cout;
+    if (x4) store_tile_x4<C::FM, WCO, C::FN>(p, acc, px0, co0, wc, wp, fr, fq);
+    else store_tile<C::FM, WCO, C::FN>(p, acc, px0, co0, wc, wp, fr, fq);
+  }
 }
 
 template <int KS, int WCO, int WC>
 __global__ void __launch_bounds__(256 * WC, 1)
 conv_sp24_kernel(const drnmi_conv_args p) {
-  conv_sp24_body<KS, WCO, WC>(p);
+  conv_sp24_body<uint16_t, KS, WCO, WC>(p);
+}
+template <int KS, int WCO, int WC>
+__global__ void __launch_bounds__(256 * WC, 1)
+conv_sp24_i8_kernel(const drnmi_conv_args p) {
+  conv_sp24_body<int8_t, KS, WCO, WC>(p);
 }
 
-// the strip-staged form of the 256 x 256 3x3 tile: 2 x (16 + 2) KB of A + 2 x 33 KB strips
+// the strip-staged form of the 256 x 256 3x3 tile: 2 x (16 + 2) KB of A (int8: 16 + 4) + 2 x 33 KB strips
 __global__ void __launch_bounds__(512, 1)
 conv_sp24_strip_kernel(const drnmi_conv_args p) {
-  conv_sp24_body<3, 128, 2, true>(p);
+  conv_sp24_body<uint16_t, 3, 128, 2, true>(p);
+}
+__global__ void __launch_bounds__(512, 1)
+conv_sp24_i8_strip_kernel(const drnmi_conv_args p) {
+  conv_sp24_body<int8_t, 3, 128, 2, true>(p);
 }
 
 // the three dynamic LDS sizes and the DMA pieces per wave and step (the counted vmcnt), pinned
-constexpr int kSp24StripLds = 2 * (Sp24Cfg<128, 2>::A_BYTES + Sp24Cfg<128, 2>::I_BYTES) + 2 * kStripBytes;
-static_assert(Sp24Cfg<128, 2>::LDS == 3 * 50 * 1024 && Sp24Cfg<128, 2>::GLDS == 2 + 1 + 4, "256 x 256 gather");
-static_assert(Sp24Cfg<128, 1>::LDS == 3 * 41 * 1024 && Sp24Cfg<128, 1>::GLDS == 2 + 1 + 8, "128 x 256 gather");
-static_assert(kSp24StripLds == (2 * 18 + 2 * 33) * 1024, "strip form");
+template <typename T>
+constexpr int kSp24StripLds = 2 * (Sp24Cfg<T, 128, 2>::A_BYTES + Sp24Cfg<T, 128, 2>::I_BYTES) + 2 * kStripBytes;
+static_assert(Sp24Cfg<uint16_t, 128, 2>::LDS == 3 * 50 * 1024 && Sp24Cfg<uint16_t, 128, 2>::GLDS == 2 + 1 + 4, "256 x 256 gather");
+static_assert(Sp24Cfg<uint16_t, 128, 1>::LDS == 3 * 41 * 1024 && Sp24Cfg<uint16_t, 128, 1>::GLDS == 2 + 1 + 8, "128 x 256 gather");
+static_assert(kSp24StripLds<uint16_t> == (2 * 18 + 2 * 33) * 1024, "strip form");
+static_assert(Sp24Cfg<int8_t, 128, 2>::LDS == 3 * 52 * 1024 && Sp24Cfg<int8_t, 128, 2>::GLDS == 2 + 2 + 4, "256 x 256 gather, int8");
+static_assert(Sp24Cfg<int8_t, 128, 1>::LDS == 3 * 42 * 1024 && Sp24Cfg<int8_t, 128, 1>::GLDS == 2 + 2 + 8, "128 x 256 gather, int8");
+static_assert(kSp24StripLds<int8_t> == (2 * 20 + 2 * 33) * 1024, "strip form, int8");
 
-template <auto KERNEL>
+// conv_sp24_strip_kernel / conv_sp24_i8_strip_kernel
+template <typename T, auto KERNEL>
 hipError_t launch_sp24_strip(const drnmi_conv_args& p, hipStream_t s) {
   const int64_t M = static_cast<int64_t>(p.n) * p.ho * p.wo;
   const int64_t blocks = (M / kBPX) * ((p.cout + 255) / 256);
-  return launch_lds<KERNEL>(dim3(static_cast<unsigned>(blocks)), dim3(512), kSp24StripLds, s, p);
+  return launch_lds<KERNEL>(dim3(static_cast<unsigned>(blocks)), dim3(512), kSp24StripLds<T>, s, p);
 }
 
-template <int KS, int WCO, int WC>
+// conv_sp24_kernel / conv_sp24_i8_kernel
+template <typename T, int KS, int WCO, int WC>
 hipError_t launch_sp24(const drnmi_conv_args& p, hipStream_t s) {
-  using C = Sp24Cfg<WCO, WC>;
+  using C = Sp24Cfg<T, WCO, WC>;
+  constexpr auto kernel = [] {   // if constexpr: only the kernel picked is instantiated
+    if constexpr (Sp24<T>::I8) return &conv_sp24_i8_kernel<KS, WCO, WC>;
+    else return &conv_sp24_kernel<KS, WCO, WC>;
+  }();
   const int64_t M = static_cast<int64_t>(p.n) * p.ho * p.wo;
   const int64_t blocks = ((M + kBPX - 1) / kBPX) * ((p.cout + C::BCO - 1) / C::BCO);
-  return launch_lds<&conv_sp24_kernel<KS, WCO, WC>>(dim3(static_cast<unsigned>(blocks)), dim3(C::THREADS), C::LDS, s, p);
+  return launch_lds<kernel>(dim3(static_cast<unsigned>(blocks)), dim3(C::THREADS), C::LDS, s, p);
 }
 
-
-// One lane per (32-row block, K step, index word): rows rb * 32 + fr and + 16 + fr, dense columns
-// kt * 64 + 16 fq .. + 15 -> 2 x 8 kept values (one 16-B store each) and one index word.  A group keeps
-// its non-zeros in ascending position; with fewer than two it is filled up from position 3 downwards
-// (the values there are the zeros themselves); of more than two (a violation) the first two are kept.
+// One lane per (IROWS-row index block, K step, index word): bf16 rows rb * 32 + fr and + 16 + fr, dense
+// columns kt * 64 + 16 fq .. + 15; int8 row rb * 16 + fr, dense columns kt * 128 + 32 fq .. + 31 -> per row CE
+// kept values (one 16-B store), and one index word.  A group keeps its non-zeros in ascending position; with
+// fewer than two it is filled up from position 3 downwards (the values there are the zeros themselves); of
+// more than two (a violation) the first two are kept.
+template <typename T>
 __global__ void __launch_bounds__(256)
-sp24_pack_kernel(const uint16_t* __restrict__ w, int rows_pad, int k_pad, uint16_t* __restrict__ vals,
-                 uint32_t* __restrict__ idx, int* __restrict__ violations) {
+sp24_pack_kernel(const T* __restrict__ w, int rows_pad, int k_pad, T* __restrict__ vals, uint32_t* __restrict__ idx,
+                 int* __restrict__ violations) {
+  using S = Sp24<T>;
+  using U = std::make_unsigned_t<T>;
+  constexpr int PW = 16 * sizeof(T);                // bits of a kept pair
   const int64_t gid = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
-  const int nk = k_pad >> 6;
-  if (gid >= static_cast<int64_t>(rows_pad >> 5) * nk * 64) return;
+  const int nk = k_pad >> __builtin_ctz(S::BK);
+  if (gid >= static_cast<int64_t>(rows_pad >> __builtin_ctz(S::IROWS)) * nk * 64) return;
   const int l = static_cast<int>(gid & 63);
   const int kt = static_cast<int>((gid >> 6) % nk);
   const int rb = static_cast<int>((gid >> 6) / nk);
@@ -316,16 +425,16 @@ sp24_pack_kernel(const uint16_t* __restrict__ w, int rows_pad, int k_pad, uint16
   uint32_t word = 0;
   int bad = 0;
 #pragma unroll
-  for (int h = 0; h < 2; ++h) {
-    const int row = rb * 32 + h * 16 + fr;
-    const uint16_t* src = w + static_cast<int64_t>(row) * k_pad + kt * 64 + fq * 16;
-    uint16_t kept[8];
+  for (int h = 0; h < S::IROWS / 16; ++h) {
+    const int row = rb * S::IROWS + h * 16 + fr;
+    const T* src = w + static_cast<int64_t>(row) * k_pad + kt * S::BK + fq * 2 * S::CE;
+    uint32_t o[4] = {0, 0, 0, 0};
 #pragma unroll
-    for (int g = 0; g < 4; ++g) {
+    for (int g = 0; g < S::CE / 2; ++g) {
       int p0 = -1, p1 = -1, nz = 0;
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
-        if ((src[4 * g + j] & 0x7fff) == 0) continue;
+        if (S::is_zero(src[4 * g + j])) continue;
         if (nz == 0) p0 = j;
         else if (nz == 1) p1 = j;
         ++nz;
@@ -342,22 +451,18 @@ sp24_pack_kernel(const uint16_t* __restrict__ w, int rows_pad, int k_pad, uint16
           p1 = 3;
         }
       }
-      kept[2 * g] = src[4 * g + p0];
-      kept[2 * g + 1] = src[4 * g + p1];
+      const uint32_t pair = static_cast<U>(src[4 * g + p0]) | (static_cast<uint32_t>(static_cast<U>(src[4 * g + p1])) << (PW / 2));
+      o[g * PW / 32] |= pair << (g * PW % 32);
       word |= static_cast<uint32_t>(p0 | (p1 << 2)) << (16 * h + 4 * g);
     }
-    uint4 o;
-    o.x = kept[0] | (static_cast<uint32_t>(kept[1]) << 16);
-    o.y = kept[2] | (static_cast<uint32_t>(kept[3]) << 16);
-    o.z = kept[4] | (static_cast<uint32_t>(kept[5]) << 16);
-    o.w = kept[6] | (static_cast<uint32_t>(kept[7]) << 16);
-    *reinterpret_cast<uint4*>(vals + static_cast<int64_t>(row) * (k_pad >> 1) + kt * 32 + fq * 8) = o;
+    *reinterpret_cast<uint4*>(vals + static_cast<int64_t>(row) * (k_pad >> 1) + kt * (S::BK / 2) + fq * S::CE) =
+        make_uint4(o[0], o[1], o[2], o[3]);
   }
   idx[gid] = word;
   if (violations != nullptr && bad != 0) atomicAdd(violations, bad);
 }
 
-// one wave, one instruction: the operand-map probe
+// one wave, one instruction: the operand-map probes
 template <int ABID>
 __global__ void __launch_bounds__(64)
 sp24_mma_probe_kernel(const bf16x8* __restrict__ a, const bf16x16* __restrict__ b, const uint32_t* __restrict__ idx,
@@ -365,6 +470,13 @@ sp24_mma_probe_kernel(const bf16x8* __restrict__ a, const bf16x16* __restrict__ 
   const int l = threadIdx.x;
   const f32x4 z = {0.f, 0.f, 0.f, 0.f};
   d[l] = __builtin_amdgcn_smfmac_f32_16x16x64_bf16(a[l], b[l], z, static_cast<int>(idx[l]), 0, ABID);
+}
+__global__ void __launch_bounds__(64)
+sp24_mma_probe_i8_kernel(const i32x4* __restrict__ a, const i32x8* __restrict__ b, const uint32_t* __restrict__ idx,
+                         i32x4* __restrict__ d) {
+  const int l = threadIdx.x;
+  const i32x4 z = {0, 0, 0, 0};
+  d[l] = __builtin_amdgcn_smfmac_i32_16x16x128_i8(a[l], b[l], z, static_cast<int>(idx[l]), 0, 0);
 }
 
 // Issue-rate loop (scripts/sp24_micro.py): every wave runs iters x 8 MFMAs on 8 independent accumulators with
@@ -397,40 +509,17 @@ sp24_issue_kernel(int iters, float* __restrict__ sink) {
   sink[blockIdx.x * 256 + l] = t;
 }
 
-}  // namespace
-
-const ConvKernel* sp24_kernel(bool tile128, int ks) {
-  static const ConvKernel k[2][2] = {
-      {DRNMI_KERNEL_ROW(conv_sp24_kernel, launch_sp24, 1, 128, 2), DRNMI_KERNEL_ROW(conv_sp24_kernel, launch_sp24, 3, 128, 2)},
-      {DRNMI_KERNEL_ROW(conv_sp24_kernel, launch_sp24, 1, 128, 1), DRNMI_KERNEL_ROW(conv_sp24_kernel, launch_sp24, 3, 128, 1)}};
-  return &k[tile128][ks == 3];
+// drnmi_sp24_pack_bytes / drnmi_sp24_pack_i8_bytes: the value plane + 2 bits per kept value
+template <typename T>
+int64_t sp24_pack_bytes(int32_t rows_pad, int32_t k_pad) {
+  if (rows_pad <= 0 || rows_pad % 32 != 0 || k_pad <= 0 || k_pad % Sp24<T>::BK != 0) return -1;
+  return static_cast<int64_t>(rows_pad) * k_pad / 2 * sizeof(T) + static_cast<int64_t>(rows_pad) * k_pad / 8;
 }
 
-const ConvKernel* sp24_strip_kernel() {
-  static const ConvKernel k = DRNMI_KERNEL_ROW0(conv_sp24_strip_kernel, launch_sp24_strip);
-  return &k;
-}
-
-// the sparse kernel's shapes: conv_big's with cin >= 64 and a folded scale; no second input, no unit mask
-bool sp24_conv_supported(const drnmi_conv_args& p) {
-  return p.dtype == DRNMI_BF16_SP24 && p.x2 == nullptr && p.unit_mask == nullptr && p.scale == nullptr &&
-         big_body_shape_ok(p, 64) && p.k == p.ks * p.ks * p.cin &&
-         static_cast<int64_t>(p.cout_pad) * p.k_pad < (int64_t(1) << 31) &&
-         (p.out_dtype == DRNMI_F32 || (p.out_dtype == DRNMI_BF16 && p.y_sc == 1 && p.y_sp == p.cout));
-}
-
-}  // namespace drnmi
-
-using namespace drnmi;
-
-extern "C" int64_t drnmi_sp24_pack_bytes(int32_t rows_pad, int32_t k_pad) {
-  if (rows_pad <= 0 || rows_pad % 32 != 0 || k_pad <= 0 || k_pad % 64 != 0) return -1;
-  return static_cast<int64_t>(rows_pad) * k_pad + static_cast<int64_t>(rows_pad) * k_pad / 8;
-}
-
-extern "C" int drnmi_sp24_pack(const void* dense_bf16, int32_t rows_pad, int32_t k_pad, void* out, int32_t* violations,
-                               void* stream) {
-  if (dense_bf16 == nullptr || out == nullptr || drnmi_sp24_pack_bytes(rows_pad, k_pad) < 0 ||
+// drnmi_sp24_pack / drnmi_sp24_pack_i8
+template <typename T>
+int sp24_pack(const void* dense, int32_t rows_pad, int32_t k_pad, void* out, int32_t* violations, void* stream) {
+  if (dense == nullptr || out == nullptr || sp24_pack_bytes<T>(rows_pad, k_pad) < 0 ||
       (reinterpret_cast<uintptr_t>(out) & 15) != 0)
     return DRNMI_EINVAL;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
@@ -438,12 +527,64 @@ extern "C" int drnmi_sp24_pack(const void* dense_bf16, int32_t rows_pad, int32_t
     const hipError_t e = hipMemsetAsync(violations, 0, sizeof(int), s);
     if (e != hipSuccess) return static_cast<int>(e);
   }
-  uint16_t* vals = reinterpret_cast<uint16_t*>(out);
+  T* vals = reinterpret_cast<T*>(out);
   uint32_t* idx = reinterpret_cast<uint32_t*>(vals + static_cast<int64_t>(rows_pad) * (k_pad / 2));
-  const int64_t lanes = static_cast<int64_t>(rows_pad / 32) * (k_pad / 64) * 64;
-  hipLaunchKernelGGL(sp24_pack_kernel, dim3(static_cast<unsigned>((lanes + 255) / 256)), dim3(256), 0, s,
-                     reinterpret_cast<const uint16_t*>(dense_bf16), rows_pad, k_pad, vals, idx, violations);
+  const int64_t lanes = static_cast<int64_t>(rows_pad / Sp24<T>::IROWS) * (k_pad / Sp24<T>::BK) * 64;
+  hipLaunchKernelGGL(sp24_pack_kernel<T>, dim3(static_cast<unsigned>((lanes + 255) / 256)), dim3(256), 0, s,
+                     reinterpret_cast<const T*>(dense), rows_pad, k_pad, vals, idx, violations);
   return static_cast<int>(hipGetLastError());
+}
+
+}  // namespace
+
+// launch_sp24<T, ARGS>, rows [tile128][ks == 3]
+#define SP24_ROW(KERNEL, T, ...) \
+  ConvKernel { #KERNEL "<" #__VA_ARGS__ ">", &launch_unsplit<&launch_sp24<T, __VA_ARGS__>> }
+#define SP24_TABLE(KERNEL, T)                                            \
+  {                                                                      \
+    {SP24_ROW(KERNEL, T, 1, 128, 2), SP24_ROW(KERNEL, T, 3, 128, 2)},    \
+    {SP24_ROW(KERNEL, T, 1, 128, 1), SP24_ROW(KERNEL, T, 3, 128, 1)},    \
+  }
+const ConvKernel* sp24_kernel(int dtype, bool tile128, int ks) {
+  static const ConvKernel k[2][2][2] = {SP24_TABLE(conv_sp24_kernel, uint16_t), SP24_TABLE(conv_sp24_i8_kernel, int8_t)};
+  return &k[dtype == DRNMI_I8_SP24][tile128][ks == 3];
+}
+
+const ConvKernel* sp24_strip_kernel(int dtype) {
+#define SP24_STRIP_ROW(KERNEL, T) \
+  ConvKernel { #KERNEL, &launch_unsplit<&launch_sp24_strip<T, &KERNEL>> }
+  static const ConvKernel k[2] = {SP24_STRIP_ROW(conv_sp24_strip_kernel, uint16_t),
+                                  SP24_STRIP_ROW(conv_sp24_i8_strip_kernel, int8_t)};
+  return &k[dtype == DRNMI_I8_SP24];
+}
+
+// the sparse kernels' shapes: conv_big's with a K step inside one tap (bf16: cin >= 64, int8: cin >= 128); no
+// second input, no unit mask.  bf16: a folded scale, fp32 or channel-dense bf16 out; int8: the int8 route's
+// contract, a non-NULL scale and its three outputs
+bool sp24_conv_supported(const drnmi_conv_args& p) {
+  if (p.dtype != DRNMI_BF16_SP24 && p.dtype != DRNMI_I8_SP24) return false;
+  const bool i8 = p.dtype == DRNMI_I8_SP24;
+  const bool out_ok = i8 ? p.out_dtype == DRNMI_F32 || p.out_dtype == DRNMI_BF16 || p.out_dtype == DRNMI_I8
+                         : p.out_dtype == DRNMI_F32 || (p.out_dtype == DRNMI_BF16 && p.y_sc == 1 && p.y_sp == p.cout);
+  return p.x2 == nullptr && p.unit_mask == nullptr && (p.scale != nullptr) == i8 &&
+         big_body_shape_ok(p, i8 ? Sp24<int8_t>::BK : Sp24<uint16_t>::BK) && p.k == p.ks * p.ks * p.cin &&
+         static_cast<int64_t>(p.cout_pad) * p.k_pad < (int64_t(1) << 31) && out_ok;
+}
+
+}  // namespace drnmi
+
+using namespace drnmi;
+
+extern "C" int64_t drnmi_sp24_pack_bytes(int32_t rows_pad, int32_t k_pad) { return sp24_pack_bytes<uint16_t>(rows_pad, k_pad); }
+extern "C" int64_t drnmi_sp24_pack_i8_bytes(int32_t rows_pad, int32_t k_pad) { return sp24_pack_bytes<int8_t>(rows_pad, k_pad); }
+
+extern "C" int drnmi_sp24_pack(const void* dense_bf16, int32_t rows_pad, int32_t k_pad, void* out, int32_t* violations,
+                               void* stream) {
+  return sp24_pack<uint16_t>(dense_bf16, rows_pad, k_pad, out, violations, stream);
+}
+extern "C" int drnmi_sp24_pack_i8(const void* dense_i8, int32_t rows_pad, int32_t k_pad, void* out, int32_t* violations,
+                                  void* stream) {
+  return sp24_pack<int8_t>(dense_i8, rows_pad, k_pad, out, violations, stream);
 }
 
 extern "C" int drnmi_sp24_mma_probe(const void* a, const void* b, const uint32_t* idx, float* d, int32_t abid, void* stream) {
@@ -455,6 +596,14 @@ extern "C" int drnmi_sp24_mma_probe(const void* a, const void* b, const uint32_t
   else
     hipLaunchKernelGGL(sp24_mma_probe_kernel<1>, dim3(1), dim3(64), 0, s, reinterpret_cast<const bf16x8*>(a),
                        reinterpret_cast<const bf16x16*>(b), idx, reinterpret_cast<f32x4*>(d));
+  return static_cast<int>(hipGetLastError());
+}
+
+extern "C" int drnmi_sp24_mma_probe_i8(const void* a, const void* b, const uint32_t* idx, int32_t* d, void* stream) {
+  if (a == nullptr || b == nullptr || idx == nullptr || d == nullptr) return DRNMI_EINVAL;
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  hipLaunchKernelGGL(sp24_mma_probe_i8_kernel, dim3(1), dim3(64), 0, s, reinterpret_cast<const i32x4*>(a),
+                     reinterpret_cast<const i32x8*>(b), idx, reinterpret_cast<i32x4*>(d));
   return static_cast<int>(hipGetLastError());
 }
 

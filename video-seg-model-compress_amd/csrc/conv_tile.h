@@ -1,5 +1,5 @@
 // Tile machinery shared by the LDS-DMA implicit-GEMM conv kernels (conv_big_body.h for conv_big.hip,
-// conv_sp24.hip, conv_stag.hip, conv_w1.hip): swizzles, element traits, the XCD remap, epilogues, the strip
+// conv_sp24.hip for both sparse element types, conv_stag.hip, conv_w1.hip): swizzles, element traits, the XCD remap, epilogues, the strip
 // geometry and the strip rows' DMA source.
 // Internal header (anonymous namespace: each translation unit gets its own copies).
 #pragma once
@@ -127,8 +127,8 @@ __device__ __forceinline__ void glds4(const void* src, char* lds_wave_base) {
   __builtin_amdgcn_global_load_lds((g_void_t*)src, (lds_void_t*)lds_wave_base, 4, 0, 0);
 }
 
-// --- One copy for conv_big_body (conv_big_body.h) and conv_sp24_body (conv_sp24.hip), whose main
-// loops are written out separately
+// --- One copy for conv_big_body (conv_big_body.h) and conv_sp24_body (conv_sp24.hip, bf16 and int8), whose
+// main loops are written out separately
 // STRIP: DMA source of row R, slot lslot, of the strip of group g = K steps 3g..3g+2 (channel block
 // g / 3, tap row kh = g % 3) of the tile at image s_n, output row s_oh, first column s_ow0: strip row
 // R = input pixel (oh - pad + kh dil, ow0 - pad + R), 16-B chunk c at slot c ^ (R & 7) (conflict-free

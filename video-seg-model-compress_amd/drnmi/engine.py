@@ -421,15 +421,20 @@ class PackedNet:
             return
         lib = _lib.load()
         cnt = torch.zeros(1, dtype=torch.int32, device=self.device)
+
+        def pack(nd, pack_bytes, pack_fn, what):
+            # allocate the blob, pack (the library zeroes the count), read the violations back: once per
+            # (re)pack, never in the launch loop
+            rows, kp = nd.wpk.shape
+            blob = torch.empty(int(pack_bytes(rows, kp)), dtype=torch.uint8, device=self.device)
+            _lib.check(pack_fn(nd.wpk.data_ptr(), rows, kp, blob.data_ptr(), cnt.data_ptr(),
+                               ctypes.c_void_p(_lib.stream_ptr(self.device))), f"{what} {nd.name}")
+            if int(cnt.item()) == 0:
+                nd.wsp = blob
+
         if self.precision == "int8":
             for i in self.sp24_i8_candidates():
-                nd = self.graph.nodes[i]
-                rows, kp = nd.wpk.shape
-                blob = torch.empty(int(lib.drnmi_sp24_pack_i8_bytes(rows, kp)), dtype=torch.uint8, device=self.device)
-                _lib.check(lib.drnmi_sp24_pack_i8(nd.wpk.data_ptr(), rows, kp, blob.data_ptr(), cnt.data_ptr(),
-                                                  ctypes.c_void_p(_lib.stream_ptr(self.device))), f"sp24_pack_i8 {nd.name}")
-                if int(cnt.item()) == 0:
-                    nd.wsp = blob
+                pack(self.graph.nodes[i], lib.drnmi_sp24_pack_i8_bytes, lib.drnmi_sp24_pack_i8, "sp24_pack_i8")
             return
         in_block = {j for pairs in self.block_pairs.values() for i in pairs for j in (i, i + 1)}
         for i, nd in enumerate(self.graph.nodes):
@@ -442,12 +447,7 @@ class PackedNet:
                 a.out_dtype, a.y_sp, a.y_sc = _lib.DRNMI_F32, 1, a.ho * a.wo
             if lib.drnmi_conv_kernel_name(ctypes.byref(a)) is None:
                 continue
-            rows, kp = nd.wpk.shape
-            blob = torch.empty(int(lib.drnmi_sp24_pack_bytes(rows, kp)), dtype=torch.uint8, device=self.device)
-            _lib.check(lib.drnmi_sp24_pack(nd.wpk.data_ptr(), rows, kp, blob.data_ptr(), cnt.data_ptr(),
-                                           ctypes.c_void_p(_lib.stream_ptr(self.device))), f"sp24_pack {nd.name}")
-            if int(cnt.item()) == 0:            # read back once per (re)pack, never in the launch loop
-                nd.wsp = blob
+            pack(nd, lib.drnmi_sp24_pack_bytes, lib.drnmi_sp24_pack, "sp24_pack")
 
     def sp24_i8_candidates(self) -> list:
         """Indices of the int8 nodes a 2:4 pack is tried on (host decisions only): int8 launches with
