@@ -66,6 +66,11 @@ def parse(argv=None):
                     help="quantisation-aware fine-tuning: calibrate int8 activation scales on synthetic frames, then "
                          "time the step with set_qat('int8') and, in the same process, with QAT off")
     ap.add_argument("--qat-rounds", type=int, default=3, help="alternating QAT-on / QAT-off timing rounds of --qat")
+    ap.add_argument("--freeze-bn", action="store_true",
+                    help="fine-tune on frozen BatchNorm statistics: time the step with freeze_bn() and, in the same "
+                         "process, without it; reports both step times and peak allocated memory")
+    ap.add_argument("--freeze-bn-rounds", type=int, default=3,
+                    help="alternating frozen / batch-statistics timing rounds of --freeze-bn")
     ap.add_argument("--cpu-seconds", type=float, default=20.0)
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--stub-step", action="store_true",
@@ -253,6 +258,11 @@ def main(argv=None):
         m.eval()
         m.calibrate_int8(torch.from_numpy(synth_frames(3000 + rank, 1, H, W)).to(dev))
         m.train().set_qat("int8")
+    if args.freeze_bn:
+        if args.qat:
+            raise SystemExit("--freeze-bn and --qat each time one switch against the plain step: give one of them")
+        m.freeze_bn()
+        torch.cuda.reset_peak_memory_stats(dev)
     g = torch.Generator(device=dev).manual_seed(2000 + rank)
     x = torch.randn(B, 3, H, W, device=dev, generator=g)
     t = torch.randint(0, 19, (B, H, W), device=dev, generator=g)
@@ -304,6 +314,38 @@ def main(argv=None):
                "convs": len(layers), "values": len(values),
                "note": "alternating rounds in one process; calibrated (absmax) on one synthetic frame"}
         el = med(ms["int8"]) * args.steps / 1e3
+    frozen = None
+    if args.freeze_bn:
+        # frozen / batch statistics in alternating rounds of this process, like --qat: one untimed step after
+        # each switch (the weight-pack table follows the scale pointers), then --steps timed steps; peak
+        # allocated memory per mode from the allocator's high-water mark of its rounds
+        mib = lambda: round(torch.cuda.max_memory_allocated(dev) / 2 ** 20, 1)
+        ms, peak_mib = {True: [el / args.steps * 1e3], False: []}, {True: [mib()], False: []}
+        for on in [False] + [v for _ in range(args.freeze_bn_rounds - 1) for v in (True, False)]:
+            m.freeze_bn(on)
+            torch.cuda.synchronize()
+            torch.cuda.reset_peak_memory_stats(dev)
+            step()
+            torch.cuda.synchronize()
+            if world > 1:
+                dist.barrier()
+            t1 = time.perf_counter()
+            for _ in range(args.steps):
+                loss = step()
+            torch.cuda.synchronize()
+            ms[on].append(max_over_ranks(time.perf_counter() - t1, device=dev) / args.steps * 1e3)
+            peak_mib[on].append(mib())
+        m.freeze_bn(True)
+        med = lambda v: sorted(v)[len(v) // 2]
+        frozen = {"ms_per_step_frozen": [round(v, 3) for v in ms[True]],
+                  "ms_per_step_batch_stats": [round(v, 3) for v in ms[False]],
+                  "median_frozen": round(med(ms[True]), 3), "median_batch_stats": round(med(ms[False]), 3),
+                  "frozen_over_batch_stats": round(med(ms[True]) / med(ms[False]), 4),
+                  "peak_allocated_mib_frozen": max(peak_mib[True]),
+                  "peak_allocated_mib_batch_stats": max(peak_mib[False]),
+                  "note": "alternating rounds in one process; peak = torch.cuda.max_memory_allocated over the "
+                          "mode's rounds (weights, gradients, momentum, workspaces and saved activations)"}
+        el = med(ms[True]) * args.steps / 1e3
     fl = train_flops(m, B, H, W)
     ach = fl * args.steps / el / 1e12
     peak = MFMA_PEAK["fp32"] / 1e12
@@ -345,6 +387,8 @@ def main(argv=None):
                           "note": "the teacher's forward and the CE + KL criterion run inside the timed step"}
     if qat is not None:
         out["qat"] = qat
+    if frozen is not None:
+        out["freeze_bn"] = frozen
     if rank == 0 and world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(args, args.cpu_seconds)
     if rank == 0:

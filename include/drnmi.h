@@ -624,7 +624,8 @@ int drnmi_confusion_matrix(const void* pred, int32_t pred_dtype, const void* lab
  * mode 0 (forward):  row = co, k = (kh*ks + kw)*kin_stride + ci, value w[co][ci][kh][kw] *
  *                    row_scale[co] (row_scale may be NULL = 1; folds an eval BN scale).
  * mode 1 (dgrad):    row = ci, k = (kh*ks + kw)*kin_stride + co, value
- *                    w[co][ci][ks-1-kh][ks-1-kw] (transposed, spatially flipped).
+ *                    w[co][ci][ks-1-kh][ks-1-kw] * row_scale[co] (transposed, spatially flipped;
+ *                    the scale stays on the output channel of the forward conv).
  * Replaces the host-side permute/pad of the conv weights (lmodels/drn.py:27-29 layout). */
 int drnmi_pack_conv_weight(const float* w, int32_t cout, int32_t cin, int32_t ks, int32_t kin_stride,
                            int32_t rows_pad, int32_t k_pad, int32_t mode, const float* row_scale,
@@ -636,8 +637,9 @@ int drnmi_pack_conv_weight(const float* w, int32_t cout, int32_t cin, int32_t ks
  * table: DEVICE memory, n entries of DRNMI_PACK_ENTRY_WORDS int64 each:
  *   [0] w (const float*), [1] out (float* [rows_pad][k_pad]), [2] planes (bf16 [3][rows_pad*k_pad]
  *   or 0), [3] cout, [4] cin, [5] ks, [6] kin_stride, [7] rows_pad, [8] k_pad, [9] mode (0 | 1,
- *   as drnmi_pack_conv_weight, no row scale), [10] first element index of the entry (prefix sum
- *   of rows_pad*k_pad over the entries before it), [11] 0.
+ *   as drnmi_pack_conv_weight), [10] first element index of the entry (prefix sum of
+ *   rows_pad*k_pad over the entries before it), [11] row_scale (const float* [cout], both modes
+ *   index it by co) or 0.
  * total = sum of rows_pad*k_pad.  Values are bit-identical to the per-layer calls.
  * Limits: n <= 512, ks <= 7, kin_stride and k_pad multiples of 4, out / planes 16-B aligned.
  * drnmi_pack_table_check validates a HOST copy of the table before it is uploaded. */
@@ -703,6 +705,39 @@ int drnmi_bn_relu_bwd_y_f32(const float* dz, const float* y, const float* mean, 
  * (seg 1x1 + bias, lmodels/drnseg.py:278-284). */
 int drnmi_channel_sum_f32(const float* x, int64_t rows, int32_t C, int32_t cvalid, float* out,
                           int32_t accumulate, void* ws, void* stream);
+
+/* ---- Frozen BatchNorm statistics in the fine-tune step (DRNSeg.freeze_bn) -- csrc/frozen_bn.hip.
+ * A BN node on its running statistics is z = relu?(conv(x, s o w) + t [+ res]) with, per channel,
+ * s = gamma * rsqrt(running_var + eps) and t = beta - running_mean * s: the forward packs the weights
+ * with row_scale = s and gives t, res and relu to drnmi_conv2d_bn_act; y is never stored.
+ * (lmodels/drn.py:49-65, :86-106 with the BN modules in eval mode.) */
+
+/* s, t and rstd = rsqrt(running_var + eps) of every BN node in one launch.  table: DEVICE memory, n
+ * (<= 1024) entries of DRNMI_FROZEN_BN_ENTRY_WORDS int64: [0] gamma (or 0 = 1), [1] beta (or 0 = 0),
+ * [2] running_mean, [3] running_var, [4] s, [5] t, [6] rstd (float* [c_pad] each), [7] C, [8] c_pad
+ * >= C (the channels past C are written as 0), [9] the bits of the fp32 eps.
+ * drnmi_frozen_bn_table_check validates a HOST copy of the table. */
+#define DRNMI_FROZEN_BN_ENTRY_WORDS 10
+int drnmi_frozen_bn_table_check(const int64_t* table_host, int32_t n);
+int drnmi_frozen_bn_prepare_f32(const int64_t* table, int32_t n, void* stream);
+
+/* Backward through relu?(. + t [+ res]) in one pass over NHWC [rows][C] (C a power of two >= 4):
+ * dr = relu ? (z > 0 ? dz : 0) : dz written over dz; dres (NULL-able) = dr or += dr;
+ * sum_rows dr per channel in fp64: dbeta_sum (double [C], NULL-able) = it, dbeta (NULL-able) = or +=
+ * its fp32 value.  ws: drnmi_reduce_workspace_bytes(rows, C).  dz, z, dres 16-byte aligned.  No
+ * atomics: bit-reproducible. */
+int drnmi_frozen_bn_act_bwd_f32(float* dz, const float* z, int32_t relu, int64_t rows, int32_t C, float* dres,
+                                int32_t dres_accumulate, float* dbeta, int32_t dbeta_accumulate,
+                                double* dbeta_sum, void* ws, void* stream);
+
+/* From g = wgrad(dr, x) = dL/d(s o w), OIHW as [cout][K]: dw[c][:] (NULL-able) = or += s[c] * g[c][:]
+ * and dgamma[c] (NULL-able) = or += rstd[c] * (<g[c][:], w[c][:]> - running_mean[c] * dbeta_sum[c]),
+ * the dot product in fp64 in a fixed order.  w: the weights the forward folded (with QAT their
+ * fake-quantised shadow).  Rows are read as 16-byte pieces when K % 4 == 0 and g, w, dw are aligned. */
+int drnmi_frozen_bn_unfold_f32(const float* g, const float* w, const float* s, const float* rstd,
+                               const float* running_mean, const double* dbeta_sum, int32_t cout, int64_t K,
+                               float* dw, int32_t dw_accumulate, float* dgamma, int32_t dgamma_accumulate,
+                               void* stream);
 
 /* Weight gradient of a conv: dw[co][ci][kh][kw] (+)= sum_pixels dy[pix][co] * x[tap(pix)][ci].
  * dy: NHWC [n*ho*wo][dy_stride] (first cout valid), x: NHWC [n][h][w][cin_stride]. */

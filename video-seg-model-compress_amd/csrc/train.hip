@@ -38,7 +38,7 @@ inline bool aligned16(const void* a, const void* b, const void* c) {
 
 // ------------------------------------------------------------------ weight packing
 // mode 0 (forward): out[co][ (kh*ks + kw) * kin_stride + ci ] = w[co][ci][kh][kw] * scale[co]
-// mode 1 (dgrad):   out[ci][ (kh'*ks + kw') * kin_stride + co ] = w[co][ci][ks-1-kh'][ks-1-kw']
+// mode 1 (dgrad):   out[ci][ (kh'*ks + kw') * kin_stride + co ] = w[co][ci][ks-1-kh'][ks-1-kw'] * scale[co]
 // Everything else in [rows_pad][k_pad] is zero.
 template <typename TO>
 __global__ void __launch_bounds__(kThreads)
@@ -61,8 +61,10 @@ pack_weight_kernel(const float* __restrict__ w, int cout, int cin, int ks, int k
         }
       } else {
         // row = ci (dgrad output channel), c = co (dgrad input channel)
-        if (row < cin && c < cout)
+        if (row < cin && c < cout) {
           v = w[((static_cast<int64_t>(c) * cin + row) * ks + (ks - 1 - kh)) * ks + (ks - 1 - kw)];
+          if (scale != nullptr) v *= scale[c];
+        }
       }
     }
     if constexpr (sizeof(TO) == 2) out[i] = f32_to_bf16(v);
@@ -115,6 +117,7 @@ pack_batched_kernel(const int64_t* __restrict__ tab, int n) {
     const int cout = static_cast<int>(q[3]), cin = static_cast<int>(q[4]), ks = static_cast<int>(q[5]);
     const int kst = static_cast<int>(q[6]), rows_pad = static_cast<int>(q[7]), k_pad = static_cast<int>(q[8]);
     const int mode = static_cast<int>(q[9]);
+    const float* __restrict__ sc = reinterpret_cast<const float*>(q[11]);   // per co, or NULL
     const int64_t m = static_cast<int64_t>(rows_pad) * k_pad;
     const int T = ks * ks;
     const int CT = pack_cols(T);
@@ -137,7 +140,10 @@ pack_batched_kernel(const int64_t* __restrict__ tab, int n) {
       const int j = idx - r * rlen;
       const int co = run_co0 + r;
       float v = 0.f;
-      if (co < cout && j < nci * T) v = w[(static_cast<int64_t>(co) * cin + ci0) * T + j];
+      if (co < cout && j < nci * T) {
+        v = w[(static_cast<int64_t>(co) * cin + ci0) * T + j];
+        if (sc != nullptr) v *= sc[co];                      // one rounding, as pack_weight_kernel's
+      }
       L[r * rstr + j] = v;
     }
     __syncthreads();
@@ -1197,7 +1203,7 @@ extern "C" int drnmi_pack_conv_weight(const float* w, int32_t cout, int32_t cin,
   if (mode != 0 && mode != 1) return DRNMI_EINVAL;
   if (k_pad < ks * ks * kin_stride) return DRNMI_EINVAL;
   if (mode == 0 && (rows_pad < cout || kin_stride < cin)) return DRNMI_EINVAL;
-  if (mode == 1 && (rows_pad < cin || kin_stride < cout || row_scale != nullptr)) return DRNMI_EINVAL;
+  if (mode == 1 && (rows_pad < cin || kin_stride < cout)) return DRNMI_EINVAL;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   const int64_t total = static_cast<int64_t>(rows_pad) * k_pad;
   if (out_dtype == DRNMI_F32)
@@ -1223,7 +1229,7 @@ extern "C" int drnmi_pack_table_check(const int64_t* t, int32_t n, int64_t* tota
     if (kst % 4 != 0 || kp % 4 != 0 || ((q[1] | q[2]) & 15) != 0) return DRNMI_EINVAL;   // 4-column stores
     if (mode == 0 && (rows < cout || kst < cin)) return DRNMI_EINVAL;
     if (mode == 1 && (rows < cin || kst < cout)) return DRNMI_EINVAL;
-    if (q[10] != total || q[11] != 0) return DRNMI_EINVAL;
+    if (q[10] != total || (q[11] & 3) != 0) return DRNMI_EINVAL;
     total += rows * kp;
   }
   if (total_out != nullptr) *total_out = total;

@@ -31,7 +31,10 @@ EXTRA = {"front.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"], "block64.hip": ["-
          "conv_s2row.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"],
          # conv_sp24.hip: its dense issue-rate loop next to the sparse ones (v_smfmac, bf16 and int8, writes
          # VGPRs only) without accumulator copies between AGPRs and VGPRs in the loop
-         "conv_sp24.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"]}
+         "conv_sp24.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"],
+         # frozen_bn.hip: one fp32 operation per instruction (no packed fp32 VALU forms) in the
+         # element-wise passes whose results the tests pin bit for bit
+         "frozen_bn.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
 
 
 def sources():

@@ -95,6 +95,7 @@ class DRNSeg(nn.Module):
         self._int8_method = None     # how _act_scales were derived (int8_state)
         self._int8_percentile = None
         self._qat = None             # "int8": quantisation-aware fine-tuning (set_qat)
+        self._bn_frozen = False      # fine-tune on the BN running statistics (freeze_bn)
         self._packed = {}
         self._plans = {}
         self._pack_key = None
@@ -120,6 +121,7 @@ class DRNSeg(nn.Module):
 
     def __setstate__(self, st):
         super().__setstate__(st)
+        self.__dict__.setdefault("_bn_frozen", False)    # a model pickled before freeze_bn existed
         self._handle = torch_ops.register_model(self)
 
     # ----------------------------------------------------------------- reference API
@@ -131,7 +133,8 @@ class DRNSeg(nn.Module):
 
     def forward(self, x: torch.Tensor):
         if self.training:
-            # fine-tune path: batch-stat BN + autograd through the HIP backward kernels
+            # fine-tune path: batch-stat BN (or, after freeze_bn(), the running statistics) + autograd
+            # through the HIP backward kernels
             if x.device.type != "cuda":
                 raise RuntimeError("drnmi.DRNSeg runs on the HIP engine only (no CPU fallback by design)")
             if self.precision not in ("fp32", "fp32x"):
@@ -412,6 +415,25 @@ class DRNSeg(nn.Module):
             self._qat_scales()
         self._qat = mode
         return self
+
+    def freeze_bn(self, on: bool = True) -> "DRNSeg":
+        """Fine-tune on frozen BatchNorm statistics (the usual practice at the two-crop batches of the
+        accuracy-recovery fine-tune): the train-mode forward and backward (precision "fp32" or "fp32x")
+        normalise every BN node with running_mean / running_var,
+            z = relu?((y - running_mean) * rsqrt(running_var + eps) * gamma + beta [+ res]),
+        and train only the affine pair next to the conv weights.  running_mean, running_var and
+        num_batches_tracked are not written.  The step folds the scale into the packed weights and the
+        shift, residual and ReLU into the conv launch, keeps no pre-BN activation and gets dgamma from
+        the weight gradient.  The flag is the model's own: BN modules put into
+        .eval() by hand do not set it, .train() / .eval() do not clear it, and it travels with a copy or
+        a pickle.  It composes with set_qat("int8").  Inference paths are untouched; freeze_bn(False)
+        restores the batch-statistics step launch for launch."""
+        self._bn_frozen = bool(on)
+        return self
+
+    @property
+    def bn_frozen(self) -> bool:
+        return bool(getattr(self, "_bn_frozen", False))
 
     def qat_layers(self):
         """(names of the convs that fine-tune on int8-grid weights and inputs, the graph values that

@@ -30,6 +30,11 @@ Quantisation-aware fine-tuning (model.set_qat("int8")), in eithe
 precision "int8" launches W8A8 read their weights and activations on the int8 grids (csrc/qat.hip,
 fake quantisation in fp32), straight-through in the backward.  Off by default; with it off no launch,
 buffer or record of the step differs.
+Frozen BN statistics (model.freeze_bn()), in either precision and with or without QAT:
+every BN node normalises with its running statistics, which are not written.  The scale is folded into
+the packed weights and the shift, residual and ReLU into the conv launch, so the forward has no BN launch
+and keeps no pre-BN activation; the backward is one pass over dz and z (csrc/frozen_bn.hip) and takes
+dgamma from the weight gradient.  Off by default; with it off no launch of the step differs.
 Activations NHWC with a power-of-two channel stride, like the inference engine.  There is no
 CPU or ATen fallback.
 """
@@ -65,10 +70,12 @@ class _NodeState:
     """Per-node packed weights (forward / dgrad layouts) cached across steps."""
 
     __slots__ = ("wf", "wd", "wfx", "wdx", "k", "k_pad", "cout_pad", "kd", "kd_pad", "rows_d", "shift", "patch",
-                 "dpatch", "dys", "s2_step", "s2_cls", "s2_planes", "wq", "wq_scale", "wsrc")
+                 "dpatch", "dys", "s2_step", "s2_cls", "s2_planes", "wq", "wq_scale", "wsrc", "fs", "ft", "frs")
 
     def __init__(self):
         self.wf = self.wd = self.wfx = self.wdx = self.shift = None
+        # frozen BN (model.freeze_bn): this step's s, t and rsqrt(running_var + eps), [cout_pad] each
+        self.fs = self.ft = self.frs = None
         self.patch = self.dpatch = False
         self.dys = None
         self.s2_step = self.s2_cls = self.s2_planes = None   # stride-2 dgrad parity classes (per step)
@@ -122,6 +129,14 @@ class TrainRunner:
         self._qat_key = None
         self._qat_tab = None
         self._qat_rows = 0
+        # frozen BN statistics (model.freeze_bn): the device table of the one launch that derives every
+        # node's s / t / rstd, the flat buffer they live in, and fp64 [C] sums of dr for dgamma
+        self._fz_key = None
+        self._fz_tab = None
+        self._fz_buf = None
+        self._fz_dbsum = None
+        self._fz_g = None               # weight-sized scratch: wgrad(dr, x) before the unfold
+        self._fz_unit = None           # (zeros, ones) for the unfused epilogue (drnmi_bn_act_f32)
 
     # ------------------------------------------------------------------ helpers
     def _ws(self, attr, nbytes, device):
@@ -239,6 +254,58 @@ class TrainRunner:
             self._rec("fq", v, x=z, y=zq, scale=s, inv_scale=inv)
         return zq
 
+    def _frozen_begin(self, device, stream) -> bool:
+        """Frozen BN statistics on (model.freeze_bn): s = gamma * rsqrt(running_var + eps), t = beta -
+        running_mean * s and rsqrt(running_var + eps) of every BN node from this step's parameters in
+        one launch (drnmi_frozen_bn_prepare_f32), before any pack reads s.  Off: nothing is launched
+        or allocated."""
+        if not getattr(self.model, "_bn_frozen", False):
+            if self._fz_key is not None:
+                for st in self.state:
+                    st.fs = st.ft = st.frs = None
+                self._fz_key = None
+            return False
+        key = []
+        for nd in self.nodes:
+            bn = nd.bn
+            if bn is None:
+                continue
+            if bn.running_mean is None or bn.running_var is None:
+                raise RuntimeError(f"{nd.name}: freeze_bn needs running statistics (track_running_stats)")
+            ts = (bn.weight, bn.bias, bn.running_mean, bn.running_var)
+            for t in ts:
+                if t is not None and not (t.is_contiguous() and t.dtype == torch.float32 and t.device == device):
+                    raise RuntimeError(f"{nd.name}: expected contiguous fp32 BN tensors on {device}")
+            key.append(tuple(0 if t is None else t.data_ptr() for t in ts) + (float(bn.eps),))
+        key = tuple(key)
+        lib = _lib.load()
+        if key != self._fz_key:
+            bns = [(nd, st) for nd, st in zip(self.nodes, self.state) if nd.bn is not None]
+            pads = [_round_up(nd.conv.out_channels, COUT_ALIGN) for nd, _ in bns]
+            total = sum(pads)
+            self._fz_buf = torch.empty(3, total, dtype=torch.float32, device=device)
+            self._fz_dbsum = torch.empty(max(pads), dtype=torch.float64, device=device)
+            self._fz_unit = (torch.zeros(max(pads), dtype=torch.float32, device=device),
+                             torch.ones(max(pads), dtype=torch.float32, device=device))
+            rows, off = [], 0
+            for (nd, st), cp, k in zip(bns, pads, key):
+                st.fs, st.ft, st.frs = (self._fz_buf[j, off:off + cp] for j in range(3))
+                off += cp
+                eps_bits = int(torch.tensor(k[4], dtype=torch.float32).view(torch.int32).item())
+                rows.append(list(k[:4]) + [st.fs.data_ptr(), st.ft.data_ptr(), st.frs.data_ptr(),
+                                           nd.conv.out_channels, cp, eps_bits])
+            tab = torch.tensor(rows, dtype=torch.int64)
+            _lib.check(lib.drnmi_frozen_bn_table_check(ctypes.c_void_p(tab.data_ptr()), len(rows)), "frozen BN table")
+            self._fz_tab, self._fz_key = tab.to(device), key
+        _lib.check(lib.drnmi_frozen_bn_prepare_f32(_vp(self._fz_tab), self._fz_tab.shape[0], stream),
+                   "frozen BN prepare")
+        if self.record is not None:
+            for nd, st in zip(self.nodes, self.state):
+                if nd.bn is not None:
+                    self._rec("frozen_prepare", nd.name, s=self._snap(st.fs), t=self._snap(st.ft),
+                              rstd=self._snap(st.frs))
+        return True
+
     def _pack(self, nd, st, device, stream):
         lib = _lib.load()
         conv = nd.conv
@@ -254,7 +321,8 @@ class TrainRunner:
         if not (w.is_contiguous() and w.dtype == torch.float32):
             raise RuntimeError(f"{nd.name}: expected a contiguous fp32 weight")
         if not self._packed_now:
-            _lib.check(lib.drnmi_pack_conv_weight(_vp(w), cout, cin, ks, cs, st.cout_pad, st.k_pad, 0, None, F32,
+            # frozen BN: s folded per output channel (st.fs is None otherwise)
+            _lib.check(lib.drnmi_pack_conv_weight(_vp(w), cout, cin, ks, cs, st.cout_pad, st.k_pad, 0, _vp(st.fs), F32,
                                                   _vp(st.wf), stream), f"pack {nd.name}")
             # fp32x: the full-resolution small-channel convs (stem, layer1, layer2 shapes) run on
             # the split-bf16 patch kernels, as in the inference engine (engine.X6_PATCH_SHAPES)
@@ -277,7 +345,7 @@ class TrainRunner:
         if self._packed_now:                      # packed with the forward weights (batched launch)
             return dys
         _lib.check(lib.drnmi_pack_conv_weight(_vp(self._weight(nd, st)), cout, cin, ks, dys, st.rows_d,
-                                              st.kd_pad, 1, None, F32, _vp(st.wd), stream), f"pack dgrad {nd.name}")
+                                              st.kd_pad, 1, _vp(st.fs), F32, _vp(st.wd), stream), f"pack dgrad {nd.name}")
         # fp32x: a data gradient whose (stride-1) conv is a patch-kernel shape (layer1's 16 -> 16
         # at full resolution) runs split-bf16 on the patch kernel, not on the f32 igemm
         st.dpatch = self.model.precision == "fp32x" and \
@@ -343,7 +411,8 @@ class TrainRunner:
                 return False
             key.append((self._weight(nd, st).data_ptr(), st.wf.data_ptr(), st.wfx.data_ptr() if st.wfx is not None else 0,
                         st.wd.data_ptr() if st.wd is not None else 0,
-                        st.wdx.data_ptr() if st.wdx is not None else 0))
+                        st.wdx.data_ptr() if st.wdx is not None else 0,
+                        st.fs.data_ptr() if st.fs is not None else 0))
         key = tuple(key)
         if key != self._pack_key:
             rows = []
@@ -358,7 +427,8 @@ class TrainRunner:
                     ents.append((st.wd, st.wdx, st.dys, st.rows_d, st.kd_pad, 1))
                 for out, planes, kst, rows_pad, k_pad, mode in ents:
                     rows.append([w.data_ptr(), out.data_ptr(), planes.data_ptr() if planes is not None else 0,
-                                 cout, cin, ks, kst, rows_pad, k_pad, mode, total, 0])
+                                 cout, cin, ks, kst, rows_pad, k_pad, mode, total,
+                                 st.fs.data_ptr() if st.fs is not None else 0])
                     total += rows_pad * k_pad
             tab = torch.tensor(rows, dtype=torch.int64)
             tot = ctypes.c_int64(0)
@@ -387,7 +457,7 @@ class TrainRunner:
 
     def _conv(self, x, cin_stride, h, w, wpk, k, k_pad, cout_pad, cout, ks, stride, pad, dil, y, y_strides,
               shift, res, n, ho, wo, stream, what, wx=None, algo=_lib.ALGO_IGEMM, want_stats=False, y_sr=0,
-              split=True):
+              split=True, relu=0):
         """One drnmi_conv2d_bn_act launch.  want_stats: let a conv_x6 launch write the BN statistics
         partials of its output (self._st_ws); returns their row count, 0 when it cannot."""
         a = _lib.ConvArgs()
@@ -400,7 +470,7 @@ class TrainRunner:
         a.ho, a.wo, a.cout, a.cout_pad = ho, wo, cout, cout_pad
         a.ks, a.stride, a.pad, a.dil = ks, stride, pad, dil
         a.k, a.k_pad = k, k_pad
-        a.relu = 0
+        a.relu = relu
         a.dtype = a.out_dtype = F32
         if wx is not None:
             a.dtype = _lib.DRNMI_F32X3           # fp32x: conv_x6 (fp32 in/out, bf16 weight planes)
@@ -444,6 +514,7 @@ class TrainRunner:
         vals["input"] = xin
         self._packed_now = False
         self._qat_begin(dev, ctypes.c_void_p(stream))
+        frozen = self._frozen_begin(dev, ctypes.c_void_p(stream))
         self._packed_now = self._batched_pack(dev, stream)
         per_node = []
         logits = None
@@ -472,6 +543,35 @@ class TrainRunner:
             if cs != cout:
                 raise NotImplementedError("train path: channel count must be a power of two")
             rows = n * oh * ow
+            if frozen:
+                # frozen statistics: s is in the packed weights; t, the residual and the ReLU are the
+                # launch's epilogue, and only z exists.  The patch kernels take no residual: there the
+                # conv writes y and drnmi_bn_act_f32 with mean 0, invstd 1, no gamma and beta = t
+                # finishes it ((y - 0) * 1 * 1 + t exactly)
+                res = rd[nd.res] if nd.res else None
+                z = torch.empty(rows, cs, dtype=torch.float32, device=dev)
+                algo = _lib.ALGO_PATCH if st.patch else _lib.ALGO_IGEMM
+                fused = not (st.patch and res is not None)
+                y = z if fused else torch.empty(rows, cs, dtype=torch.float32, device=dev)
+                self._conv(rd[nd.src], cs_in, ih, iw, st.wf, st.k, st.k_pad, st.cout_pad, cout, ks, s, p, d, y,
+                           (oh * ow * cs, cs, 1), st.ft if fused else st.shift, res if fused else None, n, oh, ow,
+                           stream, nd.name, st.wfx, algo, relu=1 if fused and nd.relu else 0)
+                if self.record is not None:
+                    self._rec("conv", nd.name, x=rd[nd.src], y=y, shift=st.ft if fused else None,
+                              res=res if fused else None, relu=bool(fused and nd.relu), **self._last_conv)
+                if not fused:
+                    zeros, ones = self._fz_unit
+                    _lib.check(lib.drnmi_bn_act_f32(_vp(y), _vp(zeros), _vp(ones), None, _vp(st.ft), _vp(res),
+                                                    1 if nd.relu else 0, rows, cs, _vp(z), ctypes.c_void_p(stream)),
+                               f"frozen bn_act {nd.name}")
+                    if self.record is not None:
+                        self._rec("bn_act", nd.name, y=y, mean=zeros, invstd=ones, res=res, z=z)
+                    del y
+                vals[nd.dst] = z
+                per_node.append(None)
+                if nd.dst in self._qat_sc:
+                    qvals[nd.dst] = self._fake_quant(nd.dst, z, ctypes.c_void_p(stream))
+                continue
             y = torch.empty(rows, cs, dtype=torch.float32, device=dev)
             bn = nd.bn
             if bn.momentum is None or not bn.track_running_stats:
@@ -531,7 +631,7 @@ class TrainRunner:
         saved = None
         if save:
             saved = {"vals": vals, "shapes": shapes, "nodes": per_node, "n": n, "up": up,
-                     "qat": (self._qat_E, qvals, dict(self._qat_sc))}
+                     "qat": (self._qat_E, qvals, dict(self._qat_sc)), "frozen": frozen}
         return logprobs, logits, saved
 
     # ------------------------------------------------------------------ backward
@@ -566,6 +666,7 @@ class TrainRunner:
         # gradients collect in qgrads[v] = d fq(v), folded into grads[v] straight-through (where the
         # level was not clamped) before v's producer consumes it
         q_e, qvals, q_sc = saved["qat"]
+        frozen = saved.get("frozen", False)
         qgrads = {}
         for idx in range(len(self.nodes) - 1, -1, -1):
             nd, st = self.nodes[idx], self.state[idx]
@@ -578,6 +679,7 @@ class TrainRunner:
             oh, ow = shapes[nd.dst]
             rows = n * oh * ow
             done = []
+            fz = False
             if nd.out_fp32_nchw:
                 dys = _pow2_at_least(cout)
                 dy = torch.empty(rows, dys, dtype=torch.float32, device=dev)
@@ -612,7 +714,6 @@ class TrainRunner:
                 dz = grads.pop(nd.dst, None)
                 if dz is None:
                     raise RuntimeError(f"no gradient reached {nd.name}")
-                y, mean, invstd = saved["nodes"][idx]
                 z = vals[nd.dst]
                 bn = nd.bn
                 dres = None
@@ -625,42 +726,68 @@ class TrainRunner:
                     else:
                         dres_acc = 1
                 gw, gb = bn.weight, bn.bias
-                ws = self._ws("_red_ws", lib.drnmi_reduce_workspace_bytes(rows, dys), dev)
-                gacc = 1 if (gw.requires_grad and acc[id(gw)]) else 0
-                if self.record is not None:
-                    bn0 = dict(dz=self._snap(dz), dres_before=self._snap(dres) if dres_acc else None,
-                               dgamma_before=self._snap(gw.grad) if gacc else None,
-                               dbeta_before=self._snap(gb.grad) if gacc and gb.requires_grad else None)
-                if nd.relu and not nd.res:
-                    # residual-free BN + ReLU: the mask is recomputed from y (z is not read)
-                    _lib.check(lib.drnmi_bn_relu_bwd_y_f32(
-                        _vp(dz), _vp(y), _vp(mean), _vp(invstd), _vp(gw.detach()), _vp(gb.detach()), rows, dys,
-                        _vp(dz), _vp(gw.grad) if gw.requires_grad else None,
-                        _vp(gb.grad) if gb.requires_grad else None, gacc, _vp(ws), sp), f"bn_bwd {nd.name}")
+                fz = frozen
+                if fz:
+                    # frozen statistics: dr over dz, dres and dbeta in one pass over dz and z; dgamma and
+                    # the weight gradient follow from wgrad(dr, x) below
+                    ws = self._ws("_red_ws", lib.drnmi_reduce_workspace_bytes(rows, dys), dev)
+                    bacc = 1 if (gb.requires_grad and acc[id(gb)]) else 0
+                    if self.record is not None:
+                        bn0 = dict(dz=self._snap(dz), dres_before=self._snap(dres) if dres_acc else None,
+                                   dbeta_before=self._snap(gb.grad) if bacc else None)
+                    _lib.check(lib.drnmi_frozen_bn_act_bwd_f32(
+                        _vp(dz), _vp(z) if nd.relu else None, 1 if nd.relu else 0, rows, dys, _vp(dres), dres_acc,
+                        _vp(gb.grad) if gb.requires_grad else None, bacc, _vp(self._fz_dbsum), _vp(ws), sp),
+                        f"frozen_bn_act_bwd {nd.name}")
+                    if gb.requires_grad:
+                        done.append(gb)
+                    dy = dz
+                    if self.record is not None:
+                        dy_rec = self._snap(dy)
+                        self._rec("frozen_act_bwd", nd.name, z=z, relu=bool(nd.relu), dr=dy_rec, dres=self._snap(dres),
+                                  dbeta=self._snap(gb.grad) if gb.requires_grad else None,
+                                  dbeta_sum=self._snap(self._fz_dbsum[:dys]), **bn0)
                 else:
-                    _lib.check(lib.drnmi_bn_act_bwd_f32(
-                        _vp(dz), _vp(z), _vp(y), _vp(mean), _vp(invstd), _vp(gw.detach()), 1 if nd.relu else 0,
-                        rows, dys, _vp(dz), _vp(dres), dres_acc,
-                        _vp(gw.grad) if gw.requires_grad else None, _vp(gb.grad) if gb.requires_grad else None,
-                        gacc, _vp(ws), sp), f"bn_bwd {nd.name}")
-                if gw.requires_grad and gb.requires_grad and acc[id(gw)] != acc[id(gb)]:
-                    raise RuntimeError("BN weight/bias grads must be both set or both None")
-                done += [q for q in (gw, gb) if q.requires_grad]
-                dy = dz
-                if self.record is not None:
-                    dy_rec = self._snap(dy)
-                    self._rec("bn_bwd", nd.name, z=z, y=y, mean=mean, invstd=invstd, dy=dy_rec, dres=self._snap(dres),
-                              dgamma=self._snap(gw.grad) if gw.requires_grad else None,
-                              dbeta=self._snap(gb.grad) if gb.requires_grad else None,
-                              from_y=bool(nd.relu and not nd.res), **bn0)
-            # weight gradient
-            if c.weight.requires_grad:
+                    y, mean, invstd = saved["nodes"][idx]
+                    ws = self._ws("_red_ws", lib.drnmi_reduce_workspace_bytes(rows, dys), dev)
+                    gacc = 1 if (gw.requires_grad and acc[id(gw)]) else 0
+                    if self.record is not None:
+                        bn0 = dict(dz=self._snap(dz), dres_before=self._snap(dres) if dres_acc else None,
+                                   dgamma_before=self._snap(gw.grad) if gacc else None,
+                                   dbeta_before=self._snap(gb.grad) if gacc and gb.requires_grad else None)
+                    if nd.relu and not nd.res:
+                        # residual-free BN + ReLU: the mask is recomputed from y (z is not read)
+                        _lib.check(lib.drnmi_bn_relu_bwd_y_f32(
+                            _vp(dz), _vp(y), _vp(mean), _vp(invstd), _vp(gw.detach()), _vp(gb.detach()), rows, dys,
+                            _vp(dz), _vp(gw.grad) if gw.requires_grad else None,
+                            _vp(gb.grad) if gb.requires_grad else None, gacc, _vp(ws), sp), f"bn_bwd {nd.name}")
+                    else:
+                        _lib.check(lib.drnmi_bn_act_bwd_f32(
+                            _vp(dz), _vp(z), _vp(y), _vp(mean), _vp(invstd), _vp(gw.detach()), 1 if nd.relu else 0,
+                            rows, dys, _vp(dz), _vp(dres), dres_acc,
+                            _vp(gw.grad) if gw.requires_grad else None, _vp(gb.grad) if gb.requires_grad else None,
+                            gacc, _vp(ws), sp), f"bn_bwd {nd.name}")
+                    if gw.requires_grad and gb.requires_grad and acc[id(gw)] != acc[id(gb)]:
+                        raise RuntimeError("BN weight/bias grads must be both set or both None")
+                    done += [q for q in (gw, gb) if q.requires_grad]
+                    dy = dz
+                    if self.record is not None:
+                        dy_rec = self._snap(dy)
+                        self._rec("bn_bwd", nd.name, z=z, y=y, mean=mean, invstd=invstd, dy=dy_rec, dres=self._snap(dres),
+                                  dgamma=self._snap(gw.grad) if gw.requires_grad else None,
+                                  dbeta=self._snap(gb.grad) if gb.requires_grad else None,
+                                  from_y=bool(nd.relu and not nd.res), **bn0)
+            # weight gradient.  Frozen BN: it is g = dL/d(s o w), written to a scratch; dw = s o g and dgamma
+            # (which needs it even where the weight itself is not trained) come from drnmi_frozen_bn_unfold_f32
+            fz_gamma = fz and nd.bn.weight.requires_grad
+            if c.weight.requires_grad or fz_gamma:
                 wa = _lib.WgradArgs()
-                wa.dy, wa.x, wa.dw = dy.data_ptr(), rd[nd.src].data_ptr(), c.weight.grad.data_ptr()
+                gbuf = self._ws("_fz_g", c.weight.numel() * 4, dev) if fz else None
+                wa.dy, wa.x, wa.dw = dy.data_ptr(), rd[nd.src].data_ptr(), (gbuf if fz else c.weight.grad).data_ptr()
                 wa.n, wa.h, wa.w, wa.cin, wa.cin_stride = n, ih, iw, cin, self.cstride[nd.src]
                 wa.ho, wa.wo, wa.cout, wa.dy_stride = oh, ow, cout, dys
                 wa.ks, wa.stride, wa.pad, wa.dil = ks, s, p, d
-                wa.accumulate = 1 if acc[id(c.weight)] else 0
+                wa.accumulate = 1 if (not fz and acc[id(c.weight)]) else 0
                 # fp32x: every weight gradient is split-bf16 (the forward's small-channel layers
                 # run split on the patch kernels as well); fp32 sizes only its own partials
                 x3 = self.model.precision == "fp32x"
@@ -673,10 +800,32 @@ class TrainRunner:
                 wg = lib.drnmi_conv_wgrad_f32x3 if x3 else lib.drnmi_conv_wgrad_f32
                 before = self._snap(c.weight.grad) if self.record is not None and wa.accumulate else None
                 _lib.check(wg(ctypes.byref(wa), sp), f"wgrad {nd.name}")
-                done.append(c.weight)
                 if self.record is not None:
-                    self._rec("wgrad", nd.name, dy=dy_rec, x=rd[nd.src], before=before,
-                              after=self._snap(c.weight.grad), x3=x3, plan=_lib.wgrad_plan(wa, x3))
+                    after = self._snap(gbuf[:c.weight.numel() * 4].view(torch.float32).view_as(c.weight)) if fz \
+                        else self._snap(c.weight.grad)
+                    self._rec("wgrad", nd.name, dy=dy_rec, x=rd[nd.src], before=before, after=after, x3=x3,
+                              plan=_lib.wgrad_plan(wa, x3))
+                if fz:
+                    gw = nd.bn.weight
+                    w_acc = 1 if (c.weight.requires_grad and acc[id(c.weight)]) else 0
+                    g_acc = 1 if (fz_gamma and acc[id(gw)]) else 0
+                    if self.record is not None:
+                        uf0 = dict(dw_before=self._snap(c.weight.grad) if w_acc else None,
+                                   dgamma_before=self._snap(gw.grad) if g_acc else None)
+                    _lib.check(lib.drnmi_frozen_bn_unfold_f32(
+                        _vp(gbuf), _vp(self._weight(nd, st)), _vp(st.fs), _vp(st.frs), _vp(nd.bn.running_mean),
+                        _vp(self._fz_dbsum), cout, c.weight[0].numel(),
+                        _vp(c.weight.grad) if c.weight.requires_grad else None, w_acc,
+                        _vp(gw.grad) if fz_gamma else None, g_acc, sp), f"frozen_bn_unfold {nd.name}")
+                    if fz_gamma:
+                        done.append(gw)
+                    if self.record is not None:
+                        self._rec("frozen_unfold", nd.name, g=after, w=self._snap(self._weight(nd, st)),
+                                  s=self._snap(st.fs), rstd=self._snap(st.frs),
+                                  dw=self._snap(c.weight.grad) if c.weight.requires_grad else None,
+                                  dgamma=self._snap(gw.grad) if fz_gamma else None, **uf0)
+                if c.weight.requires_grad:
+                    done.append(c.weight)
             if self.grad_ready is not None and done:
                 self.grad_ready(done)
             # data gradient (not needed for the network input)
