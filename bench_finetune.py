@@ -54,9 +54,13 @@ def parse(argv=None):
     ap.add_argument("--height", type=int, default=1024)
     ap.add_argument("--width", type=int, default=768)
     ap.add_argument("--no-prune", action="store_true")
-    ap.add_argument("--precision", default="fp32", choices=["fp32", "fp32x"],
+    ap.add_argument("--precision", default="fp32", choices=["fp32", "fp32x", "fp32x2"],
                     help="fp32x: the convs (forward, data and weight gradients) on the fp32-accurate "
-                         "split-bf16 kernels (conv_x6, X6 patch kernels, wgrad_f32x3); BN and the head stay exact fp32")
+                         "split-bf16 kernels (conv_x6, X6 patch kernels, wgrad_f32x3); BN and the head stay exact fp32.  "
+                         "fp32x2: fp32x with the conv_x6 launches on the three-product conv_x3")
+    ap.add_argument("--ab-rounds", type=int, default=0,
+                    help="with --precision fp32x2: time the step at fp32x2 and, in the same process, at fp32x, in this "
+                         "many alternating rounds")
     ap.add_argument("--distill", action="store_true",
                     help="knowledge distillation: a frozen dense teacher of --arch (synthetic weights, another seed) "
                          "runs inside the timed step and the criterion is DistillationLoss (CE + KL to the teacher)")
@@ -123,7 +127,7 @@ def step_t_star(model, n, h, w, precision):
     from drnmi.roofline import MFMA_PEAK  # noqa: F401
     shapes = {"input": (h, w)}
     t = 0.0
-    f32, x6 = MFMA_PEAK["fp32"], MFMA_PEAK["fp32x"]
+    f32, x6, x3 = MFMA_PEAK["fp32"], MFMA_PEAK["fp32x"], MFMA_PEAK["fp32x2"]
     for nd in model._graph.nodes:
         c = nd.conv
         ih, iw = shapes[nd.src]
@@ -133,12 +137,13 @@ def step_t_star(model, n, h, w, precision):
         fl = 2.0 * n * oh * ow * c.out_channels * c.in_channels * c.kernel_size[0] * c.kernel_size[1]
         cs = 8 if nd.src == "input" else _pow2_at_least(c.in_channels)
         patch = (cs, c.out_channels, c.kernel_size[0], c.stride[0], c.dilation[0]) in X6_PATCH_SHAPES
-        fx = precision == "fp32x"
-        t += fl / (x6 if fx and (c.in_channels >= 32 or patch) else f32)                 # forward
+        fx = precision in ("fp32x", "fp32x2")
+        ig = x3 if precision == "fp32x2" else x6        # fp32x2: the implicit-GEMM launches at the three-product peak
+        t += fl / ((x6 if patch else ig) if fx and (c.in_channels >= 32 or patch) else f32)   # forward
         if nd.src != "input":
             dpatch = (_pow2_at_least(c.out_channels), c.in_channels, c.kernel_size[0], 1,
                       c.dilation[0]) in X6_PATCH_SHAPES
-            t += fl / (x6 if fx and (c.out_channels >= 32 or dpatch) else f32)            # dgrad
+            t += fl / ((x6 if dpatch else ig) if fx and (c.out_channels >= 32 or dpatch) else f32)   # dgrad
         t += fl / (x6 if fx else f32)                                                     # wgrad
     return t
 
@@ -314,6 +319,32 @@ def main(argv=None):
                "convs": len(layers), "values": len(values),
                "note": "alternating rounds in one process; calibrated (absmax) on one synthetic frame"}
         el = med(ms["int8"]) * args.steps / 1e3
+    ab = None
+    if args.ab_rounds > 0:
+        # fp32x2 / fp32x in alternating rounds of this process, like --qat: one untimed step after each switch
+        # (a per-layer pack sets the mode's buffers), then --steps timed steps
+        if args.precision != "fp32x2" or args.qat or args.freeze_bn:
+            raise SystemExit("--ab-rounds times --precision fp32x2 against fp32x, without --qat / --freeze-bn")
+        ms = {"fp32x2": [el / args.steps * 1e3], "fp32x": []}
+        for prec in ["fp32x"] + [v for _ in range(args.ab_rounds - 1) for v in ("fp32x2", "fp32x")]:
+            m.set_precision(prec)
+            step()
+            step()
+            torch.cuda.synchronize()
+            if world > 1:
+                dist.barrier()
+            t1 = time.perf_counter()
+            for _ in range(args.steps):
+                loss = step()
+            torch.cuda.synchronize()
+            ms[prec].append(max_over_ranks(time.perf_counter() - t1, device=dev) / args.steps * 1e3)
+        m.set_precision("fp32x2")
+        med = lambda v: sorted(v)[len(v) // 2]
+        ab = {"ms_per_step_fp32x2": [round(v, 3) for v in ms["fp32x2"]], "ms_per_step_fp32x": [round(v, 3) for v in ms["fp32x"]],
+              "median_fp32x2": round(med(ms["fp32x2"]), 3), "median_fp32x": round(med(ms["fp32x"]), 3),
+              "fp32x2_over_fp32x": round(med(ms["fp32x2"]) / med(ms["fp32x"]), 4),
+              "note": "alternating rounds in one process"}
+        el = med(ms["fp32x2"]) * args.steps / 1e3
     frozen = None
     if args.freeze_bn:
         # frozen / batch statistics in alternating rounds of this process, like --qat: one untimed step after
@@ -389,6 +420,8 @@ def main(argv=None):
         out["qat"] = qat
     if frozen is not None:
         out["freeze_bn"] = frozen
+    if ab is not None:
+        out["fp32x2_vs_fp32x"] = ab
     if rank == 0 and world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(args, args.cpu_seconds)
     if rank == 0:

@@ -35,13 +35,25 @@ int32_t drnmi_abi_version(void);
 int64_t drnmi_conv_args_size(void);
 
 enum drnmi_dtype { DRNMI_F32 = 0, DRNMI_BF16 = 1, DRNMI_U8 = 2, DRNMI_I64 = 3, DRNMI_I8 = 4, DRNMI_F32X3 = 5,
-                   DRNMI_F8 = 6, DRNMI_BF16_SP24 = 7, DRNMI_I8_SP24 = 8 };
+                   DRNMI_F8 = 6, DRNMI_BF16_SP24 = 7, DRNMI_I8_SP24 = 8, DRNMI_F32X2 = 9 };
 /* DRNMI_F32X3 (conv dtype only, the "fp32x" precision mode): x, res and y are fp32 NHWC as in
  * DRNMI_F32, wgt is three bf16 planes [3][cout_pad][k_pad] with w = w1 + w2 + w3 (an exact split
  * of the fp32 weight), and the conv runs fp32-accurate arithmetic on the bf16 MFMA pipe: each
  * fp32 activation is split the same way in registers and the six products above 2^-24 are
  * accumulated in fp32 (csrc/conv_x6.hip).  Requires cin >= 32 (power of two), ks 1 or 3,
  * out_dtype DRNMI_F32. */
+/* DRNMI_F32X2 (conv dtype only, the "fp32x2" fine-tune precision): DRNMI_F32X3's launch contract --
+ * shapes, epilogue, ws / stats / y_sr, drnmi_conv_workspace_bytes and drnmi_conv_stats_rows -- on two
+ * bf16 weight planes [2][cout_pad][k_pad], w1 = bf16(w), w2 = bf16(w - w1) (the leading two planes of
+ * a DRNMI_F32X3 buffer are exactly these, at the same plane stride).  Each fp32 activation is split
+ * the same way in registers and three products are kept, x1 w2 + x2 w1 + x1 w1, smallest first, in
+ * fp32 accumulators (csrc/conv_x3.hip): each product is within 2^-15 |x||w| of x * w (bf16 keeps 8 bits:
+ * the split remainders are <= 2^-17 each, the dropped x2 w2 <= 2^-16) -- about 16 significant bits -- at
+ * half the MFMA work of DRNMI_F32X3.  tile >= 0 is read in
+ * conv_x3's own encoding: tile % 3 is the variant (0: 128 x 128 tile on 64-channel ring steps, one
+ * workgroup per CU; 1: the same tile on 32-channel steps, two per CU; 2: 64 x 128, two per CU) and,
+ * when tile >= 3, tile / 3 the split-K count (only with a workspace).  All variants are bit-identical.
+ * DRNMI_ALGO_PATCH has no two-plane form: DRNMI_ENOTSUP. */
 /* DRNMI_F8 (the "fp8" precision mode; version 6): OCP e4m3fn bytes (maximum 448, no infinities,
  * round to nearest even).  The arithmetic, stated once for the kernels and for tests/fp8_ref.py:
  *   element    e4m3(v) = the e4m3fn value nearest to clamp(v, -448, 448), ties to even; the clamp is
@@ -758,6 +770,11 @@ int drnmi_conv_wgrad_f32(const drnmi_wgrad_args* args, void* stream);
  * bf16 split of dy and x, the six products above 2^-24 on the bf16 MFMA, fp32 accumulation);
  * same arguments, workspace and errors.  semantic_seg.py:166-230 backward. */
 int drnmi_conv_wgrad_f32x3(const drnmi_wgrad_args* args, void* stream);
+/* The fp32x2 form (the DRNMI_F32X2 arithmetic: two-term bf16 splits of dy and x, three products, smallest
+ * first): same arguments, workspace (drnmi_conv_wgrad_workspace_bytes) and plan as drnmi_conv_wgrad_f32x3.
+ * The pre pipeline (128-tile geometries with K >= 1024, DRNMI_WGRAD_PRE in drnmi_conv_wgrad_plan) runs on two
+ * dy planes and three products (csrc/wgrad_x3.hip); the LDS tiles and the direct kernel keep their six. */
+int drnmi_conv_wgrad_f32x2(const drnmi_wgrad_args* args, void* stream);
 /* Host-only: the launch drnmi_conv_wgrad_f32 (x6 = 0) or drnmi_conv_wgrad_f32x3 (x6 = 1) makes for
  * these arguments, from the launcher's own decision (no pointer is read, nothing runs).  kernel:
  * DRNMI_WGRAD_*; splits: the pixel splits whose partials the reduce sums (wave splits for the direct

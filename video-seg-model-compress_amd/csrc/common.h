@@ -63,6 +63,28 @@ __device__ __forceinline__ void mfma_x6(f32x4& c, const bf16x8 (&a)[3], const bf
   c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[0], b[0], c, 0, 0, 0);
 }
 
+// Two-way split of 8 fp32 values, x = x1 + x2 + r: the leading two terms of split3 (the same
+// roundings), |r| <= 2^-17 |x|: the fp32x2 arithmetic (include/drnmi.h DRNMI_F32X2).
+__device__ __forceinline__ void split2(const float4& lo4, const float4& hi4, bf16x8& b1, bf16x8& b2) {
+  const f32x2_t x[4] = {f32x2_t{lo4.x, lo4.y}, f32x2_t{lo4.z, lo4.w}, f32x2_t{hi4.x, hi4.y}, f32x2_t{hi4.z, hi4.w}};
+  uint32_t u1[4], u2[4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    u1[i] = pk_bf16x2(x[i]);
+    u2[i] = pk_bf16x2(x[i] - widen_bf16x2(u1[i]));
+  }
+  b1 = __builtin_bit_cast(bf16x8, make_uint4(u1[0], u1[1], u1[2], u1[3]));
+  b2 = __builtin_bit_cast(bf16x8, make_uint4(u2[0], u2[1], u2[2], u2[3]));
+}
+
+// c += a * b on the split2 planes of both operands (largest first): the three products above 2^-16
+// of the leading one, smallest first.  Every fp32x2 kernel accumulates in this order.
+__device__ __forceinline__ void mfma_x3(f32x4& c, const bf16x8 (&a)[2], const bf16x8 (&b)[2]) {
+  c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[1], b[0], c, 0, 0, 0);
+  c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[0], b[1], c, 0, 0, 0);
+  c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[0], b[0], c, 0, 0, 0);
+}
+
 // 16-B chunk `chunk` of 64-B LDS row `row` (32 bf16): conflict-free for every ds_read_b128 lane
 // group (conv_big.hip swzb<64>)
 __device__ __forceinline__ int swz64(int row, int chunk) { return chunk ^ (((row >> 3) & 1) * 3); }

@@ -234,18 +234,36 @@ int x6_num_cus() {
 // read) and the output (+ residual) stream.  The default (auto variant, S = 1) is kept unless the
 // best plan is >= 5 % faster.  The model is within a few % of the SPLITS sweep (512 -> 512 d4 at
 // 2 x 128 x 96: 631 / 580 us modelled for S = 1 / 4, 627 / 580 measured).
+// conv_x3 (DRNMI_F32X2) plans the same way on its own variants: one plan function, two families.
 struct X6Plan { int v, S; };
+struct XFamily {
+  int num;                                  // variants; a forced tile id is variant tile % num, split tile / num
+  const X6Variant& (*variant)(int);
+  int (*auto_variant)(const drnmi_conv_args&);
+  bool (*supported)(const drnmi_conv_args&);
+  int planes;                               // bf16 weight planes
+};
+// conv_x3's default tiles (scripts/x3_micro.py, profiles/fp32x2/micro_conv.log): the two-per-CU 128 x 128
+// tile on 32-channel steps wherever cout % 128 == 0 -- it beat the one-per-CU 64-channel-step tile on every
+// fine-tune shape, long K included (3x3 512 d4: 349 vs 443 us; 1x1 512 -> 2048: 258 vs 399 us), so that tile
+// stays a forced variant -- and the two-per-CU 64 x 128 tile for everything narrower (3x3 64: 43 vs 55 us)
+int x3_auto_variant(const drnmi_conv_args& p) { return p.cout % 128 == 0 ? 1 : 2; }
+const XFamily kX6Family{kNumX6, &x6_variant, &x6_auto_variant, &x6_conv_supported, 3};
+const XFamily kX3Family{kNumX3, &x3_variant, &x3_auto_variant, &x3_conv_supported, 2};
+const XFamily& x_family(const drnmi_conv_args& p) { return p.dtype == DRNMI_F32X2 ? kX3Family : kX6Family; }
+
 X6Plan x6_plan(const drnmi_conv_args& p, bool split_ok) {
+  const XFamily& f = x_family(p);
   // the partials are [split][m][cout] rows written as float4: only cout % 4 == 0 splits
   if (p.cout % 4 != 0) split_ok = false;
   if (p.tile >= 0) {
-    const int v = p.tile % kNumX6;
-    int S = p.tile / kNumX6;
+    const int v = p.tile % f.num;
+    int S = p.tile / f.num;
     if (!split_ok || S < 1) S = 1;
     if (S > p.k_pad / kX6BK) S = p.k_pad / kX6BK;
     return {v, S};
   }
-  const int v0 = x6_auto_variant(p);
+  const int v0 = f.auto_variant(p);
   if (!split_ok) return {v0, 1};
   const int cus = x6_num_cus();
   const int64_t M = static_cast<int64_t>(p.n) * p.ho * p.wo;
@@ -263,7 +281,7 @@ X6Plan x6_plan(const drnmi_conv_args& p, bool split_ok) {
   // rounds of it) the plan moved 1/3 of the step's conv_x6 launches onto it and the step's conv_x6
   // time did not move (19.52 -> 19.57 ms, profiles/r8_finetune/x6_plan_v4.txt); variant 4 stays a
   // forced tile for A/B runs.
-  const X6Variant& x = x6_variant(v0);
+  const X6Variant& x = f.variant(v0);
   const double c0 = cost(x, 1);
   X6Plan best{v0, 1};
   double bc = c0;
@@ -289,20 +307,22 @@ int64_t x6_workspace_bytes(const drnmi_conv_args& p) {
 
 // rows of BN-statistics partials a launch with these arguments writes (0: it cannot -- split K)
 int64_t x6_stats_rows(const drnmi_conv_args& p) {
-  if (!x6_conv_supported(p)) return 0;
+  if (!x_family(p).supported(p)) return 0;
   const X6Plan pl = x6_plan(p, p.ws != nullptr);
   if (pl.S > 1) return 0;
-  const int bpx = x6_variant(pl.v).bpx;
+  const int bpx = x_family(p).variant(pl.v).bpx;
   const int64_t M = static_cast<int64_t>(p.n) * p.ho * p.wo;
   return (M + bpx - 1) / bpx * (bpx / 64);
 }
 
+// conv_x6 (DRNMI_F32X3) and, as x3_route, conv_x3 (DRNMI_F32X2): the same checks on the family's variants
 ConvRoute x6_route(const drnmi_conv_args& p) {
-  if (!x6_conv_supported(p)) return refuse(DRNMI_ENOTSUP);
+  const XFamily& f = x_family(p);
+  if (!f.supported(p)) return refuse(DRNMI_ENOTSUP);
   const X6Plan pl = x6_plan(p, p.ws != nullptr);
-  const X6Variant& v = x6_variant(pl.v);
+  const X6Variant& v = f.variant(pl.v);
   if (!rows_exist(p, v.bco)) return refuse(DRNMI_EINVAL);      // ... in each plane
-  if (3 * static_cast<int64_t>(p.cout_pad) * p.k_pad >= (int64_t(1) << 31)) return refuse(DRNMI_EINVAL);
+  if (f.planes * static_cast<int64_t>(p.cout_pad) * p.k_pad >= (int64_t(1) << 31)) return refuse(DRNMI_EINVAL);
   const int S = pl.S;
   if (S > 1 && p.stats != nullptr) return refuse(DRNMI_EINVAL);   // statistics only from an unsplit launch
   if (p.stats != nullptr && (reinterpret_cast<uintptr_t>(p.stats) & 7) != 0) return refuse(DRNMI_EINVAL);
@@ -310,14 +330,15 @@ ConvRoute x6_route(const drnmi_conv_args& p) {
   if (S > 1 && (reinterpret_cast<uintptr_t>(p.ws) & 15) != 0) return refuse(DRNMI_EINVAL);
   return take(&v.k[p.ks - 1], S);       // ks 2: the 2x2 parity-class kernels of a stride-2 conv's data gradient
 }
+ConvRoute x3_route(const drnmi_conv_args& p) { return x6_route(p); }
 
 }  // namespace
 
 ConvRoute conv_route(const drnmi_conv_args& p) {
-  // BN-statistics partials and output row strides: conv_x6 only
+  // BN-statistics partials and output row strides: conv_x6 / conv_x3 only
   if (p.stats != nullptr && (p.algo != DRNMI_ALGO_IGEMM || x6_stats_rows(p) <= 0)) return refuse(DRNMI_EINVAL);
-  if (p.y_sr != 0 && (p.algo != DRNMI_ALGO_IGEMM || p.dtype != DRNMI_F32X3 || p.y_sc != 1 || p.y_sr < 0 ||
-                      !x6_conv_supported(p)))
+  if (p.y_sr != 0 && (p.algo != DRNMI_ALGO_IGEMM || (p.dtype != DRNMI_F32X3 && p.dtype != DRNMI_F32X2) || p.y_sc != 1 ||
+                      p.y_sr < 0 || !x_family(p).supported(p)))
     return refuse(DRNMI_EINVAL);
   if (p.algo == DRNMI_ALGO_PATCH) {
     if (p.dtype == DRNMI_BF16_SP24 || p.dtype == DRNMI_I8_SP24) return refuse(DRNMI_EINVAL);
@@ -339,7 +360,7 @@ ConvRoute conv_route(const drnmi_conv_args& p) {
     if (p.out_dtype != p.dtype && p.out_dtype != DRNMI_BF16 && p.out_dtype != DRNMI_F32) return refuse(DRNMI_EINVAL);
   } else if (p.dtype == DRNMI_I8_SP24) {                  // the int8 route's outputs
     if (p.out_dtype != DRNMI_I8 && p.out_dtype != DRNMI_BF16 && p.out_dtype != DRNMI_F32) return refuse(DRNMI_EINVAL);
-  } else if (p.dtype == DRNMI_F32X3) {
+  } else if (p.dtype == DRNMI_F32X3 || p.dtype == DRNMI_F32X2) {
     if (p.out_dtype != DRNMI_F32) return refuse(DRNMI_EINVAL);
   } else if ((p.dtype != DRNMI_BF16 && p.dtype != DRNMI_F32 && p.dtype != DRNMI_BF16_SP24) ||
              (p.out_dtype != DRNMI_BF16 && p.out_dtype != DRNMI_F32)) {
@@ -351,6 +372,7 @@ ConvRoute conv_route(const drnmi_conv_args& p) {
   if (p.y_sr == 0 && !conv_geometry(p)) return refuse(DRNMI_EINVAL);
   if (p.dtype == DRNMI_I8 || p.dtype == DRNMI_F8) return q8_route(p);       // 8-bit: one kernel family
   if (p.dtype == DRNMI_F32X3) return x6_route(p);
+  if (p.dtype == DRNMI_F32X2) return x3_route(p);
   if (p.dtype == DRNMI_BF16_SP24 || p.dtype == DRNMI_I8_SP24) return sp24_route(p);
   if (p.tile >= DRNMI_TILE_DMA128 || (p.tile < 0 && (big_conv_supported(p) || halo_conv_supported(p)))) return big_route(p);
   if (p.x2 != nullptr) return refuse(DRNMI_ENOTSUP);          // fused second input: LDS-DMA kernels only
@@ -415,12 +437,13 @@ extern "C" const char* drnmi_conv_kernel_name(const drnmi_conv_args* a) {
 
 extern "C" int64_t drnmi_conv_workspace_bytes(const drnmi_conv_args* a) {
   if (a == nullptr) return -1;
-  return a->dtype == DRNMI_F32X3 && a->algo == DRNMI_ALGO_IGEMM && x6_conv_supported(*a) ? x6_workspace_bytes(*a) : 0;
+  const bool x = a->dtype == DRNMI_F32X3 || a->dtype == DRNMI_F32X2;
+  return x && a->algo == DRNMI_ALGO_IGEMM && x_family(*a).supported(*a) ? x6_workspace_bytes(*a) : 0;
 }
 
 extern "C" int64_t drnmi_conv_stats_rows(const drnmi_conv_args* a) {
   if (a == nullptr) return -1;
-  return a->dtype == DRNMI_F32X3 && a->algo == DRNMI_ALGO_IGEMM ? x6_stats_rows(*a) : 0;
+  return (a->dtype == DRNMI_F32X3 || a->dtype == DRNMI_F32X2) && a->algo == DRNMI_ALGO_IGEMM ? x6_stats_rows(*a) : 0;
 }
 
 // The labels-only video path's last 3x3 conv (D-22 layer8) with the seg classifier folded into its

@@ -119,6 +119,14 @@ constexpr int kNumX6 = 6;
 const X6Variant& x6_variant(int v);
 bool x6_conv_supported(const drnmi_conv_args& p);
 
+hipError_t x6_splitk_finish(const drnmi_conv_args& p, int splits, hipStream_t s);   // a split-K plan's second launch
+
+// conv_x3.hip: the three-product two-plane form (dtype DRNMI_F32X2), conv_x6's launch contract;
+// step is per 32-channel sub-step
+constexpr int kNumX3 = 3;
+const X6Variant& x3_variant(int v);
+bool x3_conv_supported(const drnmi_conv_args& p);
+
 // patch_conv.hip / patch_f32.hip: the small-channel LDS-patch convs (DRNMI_ALGO_PATCH); the row
 // for these arguments, or nullptr (not supported)
 const ConvKernel* patch_kernel(const drnmi_conv_args& p);

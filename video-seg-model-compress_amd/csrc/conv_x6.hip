@@ -574,14 +574,19 @@ hipError_t launch_x6(const drnmi_conv_args& p, int splits, hipStream_t s) {
   const hipError_t e = launch_lds<&conv_x6_kernel<KS, WCO, WC, PS>>(dim3(static_cast<unsigned>(blocks), splits),
                                                                     dim3(C::THREADS), C::LDS, s, p);
   if (e != hipSuccess || splits == 1) return e;
-  const int64_t total = M * ((p.cout + 3) / 4);
+  return x6_splitk_finish(p, splits, s);
+}
+
+}  // namespace
+
+// the second launch of a split-K plan (conv_x6 and conv_x3 write the same [split][m][cout] partials)
+hipError_t x6_splitk_finish(const drnmi_conv_args& p, int splits, hipStream_t s) {
+  const int64_t total = static_cast<int64_t>(p.n) * p.ho * p.wo * ((p.cout + 3) / 4);
   int64_t g = (total + 255) / 256;
   if (g > 4096) g = 4096;
   hipLaunchKernelGGL(x6_splitk_epilogue_kernel, dim3(static_cast<unsigned>(g)), dim3(256), 0, s, p, splits);
   return hipGetLastError();
 }
-
-}  // namespace
 
 // variants: 0 <K, 128, 2, 4> (256 channels x 256 pixels, 8 waves), 1 <K, 128, 1, 4> (128 x 256, 4
 // waves), 2 <K, 64, 1, 4> (64 x 256, 4 waves), 3 <K, 64, 2, 4> (128 x 256, 8 waves), 4 <K, 64, 2, 2>

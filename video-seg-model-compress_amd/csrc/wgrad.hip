@@ -20,42 +20,12 @@
 // The host side has one routing decision (wgrad_route) on one workspace layout (wgrad_layout) that
 // the size queries, the plan query and the launch read.
 #include "common.h"
+#include "wgrad.h"
 
 namespace drnmi {
 namespace {
 
-constexpr int kThreads = 256;
 
-struct WgradP {
-  const float* dy;
-  const float* x;
-  float* ws;
-  int dys, cout;
-  int n, h, w, cs, ho, wo, ks, stride, pad, dil;
-  int K;                 // ks * ks * cs
-  int64_t M;
-  int64_t pix_per_split;
-};
-
-constexpr int kWM = 32;      // pixels per chunk
-constexpr int kWLD = kWM + 4;
-constexpr int kWT = 64;      // tile rows / cols
-constexpr int kWTBig = 128;  // the large tile's; the dy planes' rows are padded to a multiple of it
-
-// A thread's pixel m = (n, oh, ow) advances by one chunk: the coordinates are stepped, not divided
-// out of m every chunk (an int64 division per chunk and thread).  On the caller's own variables: as
-// a struct copied per load the 128-tile and the pre kernel grew by a dozen instructions.
-__device__ __forceinline__ void wgrad_pix_step(const WgradP& p, int64_t& m, int& n, int& oh, int& ow) {
-  m += kWM;
-  ow += kWM;
-  while (ow >= p.wo) {
-    ow -= p.wo;
-    if (++oh == p.ho) {
-      oh = 0;
-      ++n;
-    }
-  }
-}
 
 // Tile T co x T k per workgroup: 4 waves of T/2 x T/2, F x F fragments each (F = T / 32), K loop
 // over 32-pixel chunks of the block's pixel split.  Operand tiles go to LDS transposed ([row][m]).
@@ -256,26 +226,6 @@ __global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(T
 // accumulator as wgrad_kernel<128, true>, so the partial sums are bit-identical to it.
 __device__ float4 g_wgrad_zero[4];   // zero-initialised: the B source outside the image
 
-// LDS byte address of a __shared__ object
-__device__ __forceinline__ uint32_t lds_addr(const void* p) {
-  return static_cast<uint32_t>(reinterpret_cast<uintptr_t>((const __attribute__((address_space(3))) void*)p));
-}
-// one 16-B-per-lane LDS-DMA (global_load_lds_dwordx4) to the wave-uniform LDS address `lds`
-// (M0 holds the LDS address; its previous value is restored, as M0 is reserved to the compiler)
-__device__ __forceinline__ void dma16(const void* src, uint32_t lds) {
-  uint32_t keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep) : "v"(src), "s"(lds) : "memory");
-}
-// XOR term of the 16-B chunk of a 128-B fp32 B row (the 64-B bf16 A rows take common.h swz64)
-__device__ __forceinline__ int pre_swz_b(int row) { return ((row >> 1) & 1) | (row & 4); }
-// transposed B write of row RR (0..15) of a thread's 16-row group: w[k] holds the lane address for
-// swizzle value k -> (0, 1, 4, 5)
-template <int RR>
-__device__ __forceinline__ void pre_wr(const uint32_t (&w)[4], float v) {
-  constexpr int k = ((RR >> 1) & 1) | (((RR >> 2) & 1) << 1);
-  asm volatile("ds_write_b32 %0, %1 offset:%2" :: "v"(w[k]), "v"(v), "i"(RR * 128) : "memory");
-}
 
 __global__ void __launch_bounds__(kThreads)
 wgrad_dy_split_kernel(const float* __restrict__ dy, int dys, int cout, int64_t M, int64_t Mp, int Cp,
@@ -306,12 +256,6 @@ wgrad_dy_split_kernel(const float* __restrict__ dy, int dys, int cout, int64_t M
   }
 }
 
-struct WgradPreP {
-  WgradP p;
-  const bf16_t* dyt;   // [3][Cp][Mp]
-  int64_t Mp;
-  int Cp;
-};
 
 __global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(2))) wgrad_x6_pre_kernel(const WgradPreP q) {
   const WgradP& p = q.p;
@@ -845,7 +789,9 @@ extern "C" int drnmi_conv_wgrad_plan(const drnmi_wgrad_args* a, int32_t x6, int3
   return DRNMI_OK;
 }
 
-static int wgrad_launch(const drnmi_wgrad_args* a, bool x6, void* stream) {
+// two: drnmi_conv_wgrad_f32x2 -- the pre route on two planes and three products (wgrad_x3_pre_kernel); every
+// other route, and the plan and workspace layout (sized for three planes), as drnmi_conv_wgrad_f32x3
+static int wgrad_launch(const drnmi_wgrad_args* a, bool x6, void* stream, bool two = false) {
   const int rc = wgrad_check(a);
   if (rc != DRNMI_OK) return rc;
   if (a->dy == nullptr || a->x == nullptr || a->dw == nullptr || a->ws == nullptr) return DRNMI_EINVAL;
@@ -883,9 +829,13 @@ static int wgrad_launch(const drnmi_wgrad_args* a, bool x6, void* stream) {
     bf16_t* dyt = reinterpret_cast<bf16_t*>(reinterpret_cast<char*>(a->ws) + l.partials_bytes);
     q.dyt = dyt;
     const int64_t blocks = (q.Mp / 32) * (q.Cp / 64);
-    hipLaunchKernelGGL(wgrad_dy_split_kernel, dim3(static_cast<unsigned>(blocks < 8192 ? blocks : 8192)), dim3(kThreads),
-                       0, s, a->dy, a->dy_stride, a->cout, p.M, q.Mp, q.Cp, dyt);
-    hipLaunchKernelGGL(wgrad_x6_pre_kernel, g2, dim3(kThreads), 0, s, q);
+    const dim3 gs(static_cast<unsigned>(blocks < 8192 ? blocks : 8192));
+    if (two) {
+      launch_wgrad_x3_pre(&q, a->dy, gs, g2, s);
+    } else {
+      hipLaunchKernelGGL(wgrad_dy_split_kernel, gs, dim3(kThreads), 0, s, a->dy, a->dy_stride, a->cout, p.M, q.Mp, q.Cp, dyt);
+      hipLaunchKernelGGL(wgrad_x6_pre_kernel, g2, dim3(kThreads), 0, s, q);
+    }
   } else if (r.kernel == DRNMI_WGRAD_BIG) {
     hipLaunchKernelGGL((wgrad_kernel<kWTBig, true>), g2, dim3(kThreads), 0, s, p);
   } else if (r.kernel == DRNMI_WGRAD_X6) {
@@ -908,3 +858,4 @@ static int wgrad_launch(const drnmi_wgrad_args* a, bool x6, void* stream) {
 
 extern "C" int drnmi_conv_wgrad_f32(const drnmi_wgrad_args* a, void* stream) { return wgrad_launch(a, false, stream); }
 extern "C" int drnmi_conv_wgrad_f32x3(const drnmi_wgrad_args* a, void* stream) { return wgrad_launch(a, true, stream); }
+extern "C" int drnmi_conv_wgrad_f32x2(const drnmi_wgrad_args* a, void* stream) { return wgrad_launch(a, true, stream, true); }

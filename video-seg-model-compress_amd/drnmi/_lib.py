@@ -13,6 +13,7 @@ from .build import LIB_PATH
 DRNMI_F32, DRNMI_BF16, DRNMI_U8, DRNMI_I64, DRNMI_I8, DRNMI_F32X3, DRNMI_F8 = 0, 1, 2, 3, 4, 5, 6
 DRNMI_BF16_SP24 = 7
 DRNMI_I8_SP24 = 8
+DRNMI_F32X2 = 9           # conv dtype: two bf16 weight planes, three products (csrc/conv_x3.hip)
 SP24_GATHER, SP24_STRIP = 0, 1          # include/drnmi.h enum drnmi_sp24_tile
 ALGO_IGEMM, ALGO_PATCH = 0, 1
 # include/drnmi.h enum drnmi_tile: the ids tests and micro-benchmarks force
@@ -129,6 +130,7 @@ SIGNATURES = {
     "drnmi_bn_stats_partials_f32": (ctypes.c_int, [_VP, _I64, _I64, _I32, _F32, _F32, _VP, _VP, _VP, _VP, _VP, _VP]),
     "drnmi_conv_wgrad_f32": (ctypes.c_int, [ctypes.POINTER(WgradArgs), _VP]),
     "drnmi_conv_wgrad_f32x3": (ctypes.c_int, [ctypes.POINTER(WgradArgs), _VP]),
+    "drnmi_conv_wgrad_f32x2": (ctypes.c_int, [ctypes.POINTER(WgradArgs), _VP]),
     "drnmi_conv_wgrad_plan": (ctypes.c_int, [ctypes.POINTER(WgradArgs), _I32, ctypes.POINTER(ctypes.c_int32),
                                              ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int64),
                                              ctypes.POINTER(ctypes.c_int32)]),

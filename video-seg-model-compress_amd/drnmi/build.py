@@ -34,7 +34,10 @@ EXTRA = {"front.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"], "block64.hip": ["-
          "conv_sp24.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"],
          # frozen_bn.hip: one fp32 operation per instruction (no packed fp32 VALU forms) in the
          # element-wise passes whose results the tests pin bit for bit
-         "frozen_bn.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
+         "frozen_bn.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
+         # conv_x3.hip: the operand split as one fp32 operation per instruction as well
+         "conv_x3.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
+         "wgrad_x3.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
 
 
 def sources():

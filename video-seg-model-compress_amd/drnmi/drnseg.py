@@ -18,7 +18,8 @@ Differences by design:
     (lmodels/drnseg.py:285-287: bilinear, align_corners=True, output 8h x 8w) on its own
     fused HIP kernel (drnmi_up8_bilinear_logsoftmax_argmax).
   * precision: "fp32" (default; the reference's arithmetic, parity mode, exact-fp32
-    MFMA), "fp32x" (fp32-accurate arithmetic on the bf16 MFMA pipe: exact 3-way bf16 splits,
+    MFMA), "fp32x2" (fine-tuning: the three-product two-plane form of fp32x's convs, about 16 significant
+    bits, csrc/conv_x3.hip), "fp32x" (fp32-accurate arithmetic on the bf16 MFMA pipe: exact 3-way bf16 splits,
     6 products, for every conv with cin >= 32; parity gates as fp32, ~3x faster), "bf16"
     (perf mode, fp32 accumulation), "fp8" (OCP e4m3 weights and activations on the same convs
     as int8, fp32 accumulation, the int8 calibration's scales; inference only) or "int8" (W8A8 for the cin >= 64 convs,
@@ -137,9 +138,10 @@ class DRNSeg(nn.Module):
             # through the HIP backward kernels
             if x.device.type != "cuda":
                 raise RuntimeError("drnmi.DRNSeg runs on the HIP engine only (no CPU fallback by design)")
-            if self.precision not in ("fp32", "fp32x"):
-                raise NotImplementedError("the fine-tune path runs in fp32 (the reference's arithmetic) or fp32x "
-                                          "(fp32-accurate split-bf16 forward/dgrad convs)")
+            if self.precision not in ("fp32", "fp32x", "fp32x2"):
+                raise NotImplementedError("the fine-tune path runs in fp32 (the reference's arithmetic), fp32x "
+                                          "(fp32-accurate split-bf16 forward/dgrad convs) or fp32x2 (their "
+                                          "three-product form)")
             from .train import train_forward
             return train_forward(self, x)
         if x.dtype != torch.float32 or x.dim() != 4 or x.shape[1] != 3:
@@ -261,8 +263,8 @@ class DRNSeg(nn.Module):
 
     # ----------------------------------------------------------------- configuration
     def set_precision(self, precision: str) -> "DRNSeg":
-        if precision not in ("fp32", "fp32x", "bf16", "int8", "fp8"):
-            raise ValueError("precision must be 'fp32', 'fp32x', 'bf16', 'int8' or 'fp8'")
+        if precision not in ("fp32", "fp32x", "fp32x2", "bf16", "int8", "fp8"):
+            raise ValueError("precision must be 'fp32', 'fp32x', 'fp32x2', 'bf16', 'int8' or 'fp8'")
         if precision in ("int8", "fp8") and self.arch != "D":
             # the int8 launches are pinned bit for bit by an oracle that restates DRN-D only, and fp8
             # follows int8's layout
@@ -396,8 +398,8 @@ class DRNSeg(nn.Module):
         return self
 
     def set_qat(self, mode: str | None) -> "DRNSeg":
-        """Quantisation-aware fine-tuning: with "int8" the train-mode forward (precision "fp32" or
-        "fp32x") reads the int8 engine's grids wherever precision "int8" would launch W8A8 for this
+        """Quantisation-aware fine-tuning: with "int8" the train-mode forward (precision "fp32",
+        "fp32x" or "fp32x2", whose forward convs then keep fp32x's six products) reads the int8 engine's grids wherever precision "int8" would launch W8A8 for this
         model: those convs (qat_layers()[0]) see their weights on the per-output-channel int8 grid and,
         as input and residual, the activations (qat_layers()[1]) on their calibrated per-tensor grid;
         the backward is straight-through.  The scales are the installed ones
@@ -411,14 +413,14 @@ class DRNSeg(nn.Module):
         if mode is not None:
             if self.arch != "D":
                 raise NotImplementedError(f"quantisation-aware fine-tuning covers the DRN-D family only, as precision "
-                                          f"'int8' does; {self.model_name} fine-tunes in 'fp32' or 'fp32x'")
+                                          f"'int8' does; {self.model_name} fine-tunes in 'fp32', 'fp32x' or 'fp32x2'")
             self._qat_scales()
         self._qat = mode
         return self
 
     def freeze_bn(self, on: bool = True) -> "DRNSeg":
         """Fine-tune on frozen BatchNorm statistics (the usual practice at the two-crop batches of the
-        accuracy-recovery fine-tune): the train-mode forward and backward (precision "fp32" or "fp32x")
+        accuracy-recovery fine-tune): the train-mode forward and backward (precision "fp32", "fp32x" or "fp32x2")
         normalise every BN node with running_mean / running_var,
             z = relu?((y - running_mean) * rsqrt(running_var + eps) * gamma + beta [+ res]),
         and train only the affine pair next to the conv weights.  running_mean, running_var and

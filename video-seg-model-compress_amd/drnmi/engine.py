@@ -294,7 +294,10 @@ class PackedNet:
                            stage_outputs=dict(graph.stage_outputs), channels=dict(graph.channels))
         self.block_sparse = block_sparse
         self.sparse24 = sparse24
-        self.precision = precision
+        # fp32x2 (the fine-tune's validate()): the fp32x plan and buffers, its conv_x6 launches issued
+        # as DRNMI_F32X2 on the leading two of the three weight planes
+        self.two_plane = precision == "fp32x2"
+        self.precision = precision = "fp32x" if self.two_plane else precision
         # int8 / fp8 nets run their small-channel layers in bf16: "base" is that precision
         self.qcode = Q8_CODES.get(precision)       # the net's 8-bit value code (None: no 8-bit launches)
         self.base = "bf16" if self.qcode is not None else precision
@@ -911,7 +914,7 @@ class Plan:
         a.y_sn, a.y_sp, a.y_sc = lh * lw * cs, cs, 1
         name = lib.drnmi_conv_kernel_name(ctypes.byref(a))   # (routing does not read a.y)
         if name is None or not name.decode().startswith(("conv_big_kernel", "conv_i8_kernel", "conv_i8_occ2_kernel",
-                                                        "conv_x6_kernel", "conv_f8_kernel", "conv_f8_occ2_kernel",
+                                                        "conv_x6_kernel", "conv_x3_kernel", "conv_f8_kernel", "conv_f8_occ2_kernel",
                                                         "conv_sp24_kernel", "conv_sp24_i8_kernel")):
             return
         if "logits_nhwc" not in self.bufs:      # only plans whose seg conv writes the NHWC rows
@@ -1043,7 +1046,7 @@ class Plan:
         a.ks, a.stride, a.pad, a.dil = c.kernel_size[0], c.stride[0], c.padding[0], c.dilation[0]
         a.k, a.k_pad = nd.k, nd.k_pad
         a.relu = 1 if nd.relu else 0
-        a.dtype = _lib.DRNMI_F32X3 if nd.x6 else pk.value_code(nd.x_val)
+        a.dtype = (_lib.DRNMI_F32X2 if pk.two_plane else _lib.DRNMI_F32X3) if nd.x6 else pk.value_code(nd.x_val)
         a.tile = -1
         a.algo = _lib.ALGO_PATCH if _uses_patch(nd, nd.cin_stride, pk.base) else _lib.ALGO_IGEMM
         a.res_scale, a.out_scale = nd.res_scale, nd.out_scale

@@ -14,7 +14,7 @@ HBM_PEAK_BPS = 8.0e12
 # int8: dense i8 MFMA = 2x bf16 (fp8 launches, nd.i8 too, run e4m3 on the K-128 f8f6f4 MFMA at the same
 # peak and one byte per element); fp32x: fp32-accurate split-bf16 arithmetic, 6 bf16 MFMAs per fp32
 # product (csrc/conv_x6.hip) = 2.5 PF / 6
-MFMA_PEAK = {"bf16": 2.5e15, "fp32": 157.3e12, "int8": 5.0e15, "fp32x": 2.5e15 / 6}
+MFMA_PEAK = {"bf16": 2.5e15, "fp32": 157.3e12, "int8": 5.0e15, "fp32x": 2.5e15 / 6, "fp32x2": 2.5e15 / 3}
 
 
 def kernel_peak(kernel_name: str, base: str) -> float:
@@ -24,6 +24,8 @@ def kernel_peak(kernel_name: str, base: str) -> float:
     # conv_i8_*, conv_w1_i8_*, conv_w1h_i8_*; conv_f8_*: e4m3 on the K-128 f8f6f4 MFMA runs at the same 8-bit peak
     if kernel_name.startswith(("conv_i8", "conv_f8")) or "_i8_" in kernel_name:
         return MFMA_PEAK["int8"]
+    if kernel_name.startswith("conv_x3"):        # three bf16 MFMAs per product (csrc/conv_x3.hip)
+        return MFMA_PEAK["fp32x2"]
     if kernel_name.startswith("conv_x6"):
         return MFMA_PEAK["fp32x"]
     if kernel_name.startswith("conv_sp24"):       # 2:4 sparse bf16: dense-equivalent FLOPs against AMD's 2x sparse peak

@@ -26,6 +26,11 @@ split-bf16 kernel (csrc/conv_x6.hip: exact 3-way bf16 split of weights and activ
 products above 2^-24, fp32 accumulation, 2.5 PF / 6 peak) instead of the exact-f32 MFMA
 (157 TF), and so do their weight gradients (drnmi_conv_wgrad_f32x3, the same split on dy and x);
 BN, the head and the small-channel convs stay exact fp32.
+"fp32x2" is "fp32x" with those implicit-GEMM convs on the three-product two-plane kernel
+(csrc/conv_x3.hip, DRNMI_F32X2: half the MFMA work, about 16 significant bits per product, DESIGN.md
+3.3a), which reads the leading two of the three packed planes; the weight gradients' pre
+pipeline (K >= 1024) runs on two dy planes and three products (drnmi_conv_wgrad_f32x2); the patch-kernel shapes
+(HBM-bound), the other weight-gradient routes and, under set_qat, the forward pass keep their six products.
 Quantisation-aware fine-tuning (model.set_qat("int8")), in either precision: the convs
 precision "int8" launches W8A8 read their weights and activations on the int8 grids (csrc/qat.hip,
 fake quantisation in fp32), straight-through in the backward.  Off by default; with it off no launch,
@@ -60,6 +65,7 @@ S2_CLASS_DGRAD = True
 # conv_x6 training launches may split K where their tiles leave CUs idle (tests switch it off for
 # bit-for-bit comparisons of launch forms: a split sums the same products in another association)
 X6_SPLIT_K = True
+SPLIT_PRECISIONS = ("fp32x", "fp32x2")      # the split-bf16 fine-tune precisions
 
 
 def _vp(t):
@@ -326,7 +332,7 @@ class TrainRunner:
                                                   _vp(st.wf), stream), f"pack {nd.name}")
             # fp32x: the full-resolution small-channel convs (stem, layer1, layer2 shapes) run on
             # the split-bf16 patch kernels, as in the inference engine (engine.X6_PATCH_SHAPES)
-            st.patch = self.model.precision == "fp32x" and not nd.out_fp32_nchw and \
+            st.patch = self.model.precision in SPLIT_PRECISIONS and not nd.out_fp32_nchw and \
                 (cs, cout, ks, conv.stride[0], conv.dilation[0]) in X6_PATCH_SHAPES
             st.wfx = self._split(st.wf, cs, st.k, st.k_pad, patch=st.patch, out=st.wfx)
         if conv.bias is not None:
@@ -348,7 +354,7 @@ class TrainRunner:
                                               st.kd_pad, 1, _vp(st.fs), F32, _vp(st.wd), stream), f"pack dgrad {nd.name}")
         # fp32x: a data gradient whose (stride-1) conv is a patch-kernel shape (layer1's 16 -> 16
         # at full resolution) runs split-bf16 on the patch kernel, not on the f32 igemm
-        st.dpatch = self.model.precision == "fp32x" and \
+        st.dpatch = self.model.precision in SPLIT_PRECISIONS and \
             (dys, cin, ks, 1, nd.conv.dilation[0]) in X6_PATCH_SHAPES
         st.wdx = self._split(st.wd, dys, st.kd, st.kd_pad, patch=st.dpatch, out=st.wdx)
         return dys
@@ -446,7 +452,7 @@ class TrainRunner:
         """fp32x: the three bf16 planes of a packed fp32 weight, for the convs conv_x6 takes
         (>= 32 input channels, k == k_pad) or the split-bf16 patch kernels take (`patch`); None
         keeps the launch on the exact-f32 kernel.  `out`: the previous step's planes (reused)."""
-        if self.model.precision != "fp32x" or (not patch and (cin_stride < 32 or k != k_pad)):
+        if self.model.precision not in SPLIT_PRECISIONS or (not patch and (cin_stride < 32 or k != k_pad)):
             return None
         # one HIP pass (drnmi_split3_bf16), bit-identical to engine.split3_bf16
         if out is None or out.shape != (3,) + tuple(wpk.shape):
@@ -457,8 +463,9 @@ class TrainRunner:
 
     def _conv(self, x, cin_stride, h, w, wpk, k, k_pad, cout_pad, cout, ks, stride, pad, dil, y, y_strides,
               shift, res, n, ho, wo, stream, what, wx=None, algo=_lib.ALGO_IGEMM, want_stats=False, y_sr=0,
-              split=True, relu=0):
-        """One drnmi_conv2d_bn_act launch.  want_stats: let a conv_x6 launch write the BN statistics
+              split=True, relu=0, six=False):
+        """One drnmi_conv2d_bn_act launch.  six: keep an fp32x2 launch on six products.
+        want_stats: let a conv_x6 launch write the BN statistics
         partials of its output (self._st_ws); returns their row count, 0 when it cannot."""
         a = _lib.ConvArgs()
         a.x, a.wgt, a.scale, a.shift = x.data_ptr(), (wx if wx is not None else wpk).data_ptr(), None, shift.data_ptr()
@@ -474,6 +481,16 @@ class TrainRunner:
         a.dtype = a.out_dtype = F32
         if wx is not None:
             a.dtype = _lib.DRNMI_F32X3           # fp32x: conv_x6 (fp32 in/out, bf16 weight planes)
+            # fp32x2: conv_x3 on the leading two planes; the patch kernels keep six products, and so does the
+            # whole forward pass under set_qat (the data gradients still take three).  Measured on the D-22 QAT
+            # step against the float64 restatement, gradient rel-L2: three products in the convs that read
+            # fake-quantised values put every parameter at ~1e-3 (x and w on 127-level grids make the split
+            # remainders a function of the level, so they add up over K instead of averaging out); in the
+            # other forward convs (layer3, layer4.0) they moved one ReLU of layer.4.0 (1.5e-2 at its bn1.bias,
+            # 3e-3 upstream) -- QAT's gates pin such discrete forward events; in the data gradients alone
+            # 1.8e-5 (six everywhere: 1.9e-6)
+            if self.model.precision == "fp32x2" and algo == _lib.ALGO_IGEMM and not six:
+                a.dtype = _lib.DRNMI_F32X2
         a.tile, a.algo = -1, algo
         lib = _lib.load()
         nb = 0
@@ -523,6 +540,7 @@ class TrainRunner:
             c = nd.conv
             # a conv the int8 engine runs W8A8 reads fq(src) / fq(res); every other conv the values
             rd = qvals if self._qat_E is not None and idx in self._qat_E else vals
+            six = self._qat_E is not None    # fp32x2 under QAT: the forward pass keeps six products (_conv)
             ih, iw = shapes[nd.src]
             ks, s, p, d = c.kernel_size[0], c.stride[0], c.padding[0], c.dilation[0]
             oh, ow = _conv_out(ih, ks, s, p, d), _conv_out(iw, ks, s, p, d)
@@ -533,7 +551,8 @@ class TrainRunner:
             if nd.out_fp32_nchw:        # seg 1x1 + bias -> fp32 NCHW logits
                 logits = torch.empty(n, cout, oh, ow, dtype=torch.float32, device=dev)
                 self._conv(rd[nd.src], cs_in, ih, iw, st.wf, st.k, st.k_pad, st.cout_pad, cout, ks, s, p, d,
-                           logits, (cout * oh * ow, 1, oh * ow), st.shift, None, n, oh, ow, stream, nd.name, st.wfx)
+                           logits, (cout * oh * ow, 1, oh * ow), st.shift, None, n, oh, ow, stream, nd.name, st.wfx,
+                           six=six)
                 vals[nd.dst] = logits
                 per_node.append(None)
                 if self.record is not None:
@@ -555,7 +574,7 @@ class TrainRunner:
                 y = z if fused else torch.empty(rows, cs, dtype=torch.float32, device=dev)
                 self._conv(rd[nd.src], cs_in, ih, iw, st.wf, st.k, st.k_pad, st.cout_pad, cout, ks, s, p, d, y,
                            (oh * ow * cs, cs, 1), st.ft if fused else st.shift, res if fused else None, n, oh, ow,
-                           stream, nd.name, st.wfx, algo, relu=1 if fused and nd.relu else 0)
+                           stream, nd.name, st.wfx, algo, relu=1 if fused and nd.relu else 0, six=six)
                 if self.record is not None:
                     self._rec("conv", nd.name, x=rd[nd.src], y=y, shift=st.ft if fused else None,
                               res=res if fused else None, relu=bool(fused and nd.relu), **self._last_conv)
@@ -579,7 +598,8 @@ class TrainRunner:
             # conv_x6 launches write the BN statistics partials in their epilogue (no pass over y)
             g_rows = self._conv(rd[nd.src], cs_in, ih, iw, st.wf, st.k, st.k_pad, st.cout_pad, cout, ks, s, p,
                                 d, y, (oh * ow * cs, cs, 1), st.shift, None, n, oh, ow, stream, nd.name, st.wfx,
-                                _lib.ALGO_PATCH if st.patch else _lib.ALGO_IGEMM, want_stats=FUSED_BN_STATS)
+                                _lib.ALGO_PATCH if st.patch else _lib.ALGO_IGEMM, want_stats=FUSED_BN_STATS,
+                                six=six)
             mean = torch.empty(cs, dtype=torch.float32, device=dev)
             invstd = torch.empty(cs, dtype=torch.float32, device=dev)
             if self.record is not None:
@@ -790,14 +810,15 @@ class TrainRunner:
                 wa.accumulate = 1 if (not fz and acc[id(c.weight)]) else 0
                 # fp32x: every weight gradient is split-bf16 (the forward's small-channel layers
                 # run split on the patch kernels as well); fp32 sizes only its own partials
-                x3 = self.model.precision == "fp32x"
+                x3 = self.model.precision in SPLIT_PRECISIONS
                 nb = (lib.drnmi_conv_wgrad_workspace_bytes if x3 else lib.drnmi_conv_wgrad_f32_workspace_bytes)(
                     ctypes.byref(wa))
                 if nb < 0:
                     raise RuntimeError(f"wgrad {nd.name}: bad geometry")
                 ws = self._ws("_wg_ws", nb, dev)
                 wa.ws, wa.ws_bytes = ws.data_ptr(), ws.numel()
-                wg = lib.drnmi_conv_wgrad_f32x3 if x3 else lib.drnmi_conv_wgrad_f32
+                wg = lib.drnmi_conv_wgrad_f32 if not x3 else lib.drnmi_conv_wgrad_f32x2 \
+                    if self.model.precision == "fp32x2" else lib.drnmi_conv_wgrad_f32x3
                 before = self._snap(c.weight.grad) if self.record is not None and wa.accumulate else None
                 _lib.check(wg(ctypes.byref(wa), sp), f"wgrad {nd.name}")
                 if self.record is not None:
