@@ -287,6 +287,50 @@ int64_t drnmi_conv_stats_rows(const drnmi_conv_args* args);
  * every step. */
 int64_t drnmi_conv_workspace_bytes(const drnmi_conv_args* args);
 
+/* Split-K form of a DRNMI_BF16 implicit-GEMM launch, for grids that leave most CUs idle (one small
+ * frame per call: a 512 -> 512 3x3 conv of a 300 x 300 frame is 12 workgroups on the 256 x 256 tile;
+ * DRNSeg.set_low_latency routes such launches here).  New entry points under ABI version 7:
+ * drnmi_conv_args, enum drnmi_tile and every existing symbol are unchanged, and args->tile is not read.
+ * csrc/conv_sk.hip: tiles of 128 output channels x 64 pixels over M = n ho wo flattened; the K range,
+ * in steps of one tap x 64 channels in the packed order k = (kh ks + kw) cin + ci, is cut into
+ * `splits` contiguous near-equal parts (the remainder steps go to the first parts), one workgroup
+ * per (tile, part), ONE launch: each workgroup stores its fp32 partial tile to the workspace,
+ * publishes it at device scope and draws the tile's ticket; the workgroup that draws the last one
+ * adds the partials in part order 0 .. splits - 1 (never in arrival order), applies the epilogue of
+ * drnmi_conv2d_bn_act (acc * scale + shift, residual, ReLU; bf16 or fp32 at the output strides of a
+ * DRNMI_BF16 launch) and sets the ticket back to 0.  No workgroup waits for another.  The result is
+ * a function of the arguments and `splits` alone: two launches give the same bytes.  splits == 1
+ * touches no workspace.
+ *   splits   0 = auto: floor(2 CUs / tiles) (CUs read from the device; 256 without one), at most
+ *            K steps / 4 and DRNMI_SPLITK_MAX, at least 1: so 1, or tiles x splits <= 2 CUs
+ *            (drnmi_conv_splitk_auto returns it).  Else 1 .. min(DRNMI_SPLITK_MAX, K steps),
+ *            K steps = ks * ks * cin / 64.
+ *   shapes   dtype DRNMI_BF16, cin a power of two >= 64, ks 1 or 3 at any stride / dilation (a tap
+ *            wholly in the padding reads zeros), any M, cout_pad % 128 == 0 with the rows of every
+ *            128-channel tile present, k_pad == k, scale NULL or not, optional bf16 residual,
+ *            out_dtype DRNMI_BF16 (NHWC rows, y_sc 1, y_sp cout) or DRNMI_F32 (any strides).
+ *   refused  DRNMI_ENOTSUP: x2, unit_mask, another dtype, cin < 64, DRNMI_ALGO_PATCH;
+ *            DRNMI_EINVAL: whatever drnmi_conv2d_bn_act refuses with it, splits outside the range
+ *            above, and, for more than one part, ws NULL, not 16-byte aligned or ws_bytes below
+ *            drnmi_conv_splitk_workspace_bytes.
+ *   ws       args->ws / ws_bytes: one int32 ticket per tile (padded to 256 B), then the partials
+ *            [splits][M][cout_pad] fp32.  The tickets must be ZERO before the first launch: whoever
+ *            allocates the workspace zeroes it once (all of it is simplest); every launch
+ *            leaves them zero, so launches that follow each other on a stream -- other shapes and
+ *            split counts too -- and replays of a captured graph share it without a memset.  Two
+ *            launches that may run at the same time need a workspace each.
+ * drnmi_conv_splitk_status: the status the launch would return (no launch; x, wgt, shift, y are not
+ * looked at).  drnmi_conv_splitk_kernel_name: "conv_sk_kernel<1>" / "conv_sk_kernel<3>" (by ks), NULL
+ * exactly when that status is not 0.  drnmi_conv_splitk_auto / drnmi_conv_splitk_workspace_bytes:
+ * the part count splits = 0 picks / the bytes `splits` parts need (0 for one part), judged as if a
+ * large enough workspace were given; the negative status / -1 for arguments the launch refuses. */
+#define DRNMI_SPLITK_MAX 16
+int drnmi_conv_splitk(const drnmi_conv_args* args, int splits, void* stream);
+int drnmi_conv_splitk_status(const drnmi_conv_args* args, int splits);
+int drnmi_conv_splitk_auto(const drnmi_conv_args* args);
+int64_t drnmi_conv_splitk_workspace_bytes(const drnmi_conv_args* args, int splits);
+const char* drnmi_conv_splitk_kernel_name(const drnmi_conv_args* args, int splits);
+
 /* Fused stem + layer1 (bf16, csrc/patch_conv.hip stem_l1_kernel): replaces the two launches
  *   drnmi_conv2d_bn_act(stem); drnmi_conv2d_bn_act(next)
  * of lmodels/drn.py:132-137 (layer0 7x7 3->16 + BN + ReLU on the uint8 frame) and :201-211

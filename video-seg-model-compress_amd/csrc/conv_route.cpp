@@ -383,6 +383,37 @@ ConvRoute conv_route(const drnmi_conv_args& p) {
   return take(igemm_kernel(p.dtype, tile, p.ks));
 }
 
+// --- conv_sk (drnmi_conv_splitk): its own entry points, no tile id.  The auto count fills the part:
+// S = floor(2 CUs / tiles) -- tiles x S workgroups are at most one full round of the kernel's two
+// workgroups per CU -- capped so that every part keeps at least 4 K steps (a part pays the ring's
+// fill and a partial tile's round trip) and at DRNMI_SPLITK_MAX.  So S = 1, or tiles x S <= 2 CUs.
+int sk_auto_splits(const drnmi_conv_args& p) {
+  const int64_t tiles = sk_tiles(p);
+  const int nsteps = p.k / kSkBK;
+  int64_t S = 2 * static_cast<int64_t>(x6_num_cus()) / tiles;
+  if (S > nsteps / 4) S = nsteps / 4;
+  if (S > kSkMaxSplits) S = kSkMaxSplits;
+  return S < 1 ? 1 : static_cast<int>(S);
+}
+int64_t sk_workspace_bytes(const drnmi_conv_args& p, int S) {
+  return S > 1 ? sk_ticket_bytes(p) + static_cast<int64_t>(S) * p.n * p.ho * p.wo * p.cout_pad * 4 : 0;
+}
+
+ConvRoute sk_route(const drnmi_conv_args& p, int splits) {
+  // whatever every launch is refused for (shapes, strides, dtype / out_dtype codes), asked of the default route
+  drnmi_conv_args q = p;
+  q.tile = DRNMI_TILE_AUTO;
+  if (conv_route(q).status == DRNMI_EINVAL || splits < 0 || splits > kSkMaxSplits) return refuse(DRNMI_EINVAL);
+  // no fused second input, no unit skipping, bf16 only, cin >= 64
+  if (p.x2 != nullptr || p.unit_mask != nullptr || p.algo != DRNMI_ALGO_IGEMM || !sk_conv_supported(p)) return refuse(DRNMI_ENOTSUP);
+  if (!rows_exist(p, kSkBCO)) return refuse(DRNMI_EINVAL);
+  const int S = splits == 0 ? sk_auto_splits(p) : splits;
+  if (S > p.k / kSkBK) return refuse(DRNMI_EINVAL);                  // every part has a K step
+  if (S > 1 && (p.ws == nullptr || (reinterpret_cast<uintptr_t>(p.ws) & 15) != 0 || p.ws_bytes < sk_workspace_bytes(p, S)))
+    return refuse(DRNMI_EINVAL);
+  return take(sk_kernel(p.ks), S);
+}
+
 namespace {
 
 struct SegRoute {
@@ -444,6 +475,42 @@ extern "C" int64_t drnmi_conv_workspace_bytes(const drnmi_conv_args* a) {
 extern "C" int64_t drnmi_conv_stats_rows(const drnmi_conv_args* a) {
   if (a == nullptr) return -1;
   return (a->dtype == DRNMI_F32X3 || a->dtype == DRNMI_F32X2) && a->algo == DRNMI_ALGO_IGEMM ? x6_stats_rows(*a) : 0;
+}
+
+// conv_sk: the launch and its four queries, all answered by sk_route
+extern "C" int drnmi_conv_splitk(const drnmi_conv_args* a, int splits, void* stream) {
+  if (a == nullptr || a->x == nullptr || a->wgt == nullptr || a->shift == nullptr || a->y == nullptr) return DRNMI_EINVAL;
+  const ConvRoute r = sk_route(*a, splits);
+  if (r.status != 0) return r.status;
+  return launch_status(r.k->launch(*a, r.splits, reinterpret_cast<hipStream_t>(stream)));
+}
+
+extern "C" int drnmi_conv_splitk_status(const drnmi_conv_args* a, int splits) {
+  return a == nullptr ? DRNMI_EINVAL : sk_route(*a, splits).status;
+}
+
+extern "C" const char* drnmi_conv_splitk_kernel_name(const drnmi_conv_args* a, int splits) {
+  return a == nullptr ? nullptr : sk_route(*a, splits).name();
+}
+
+// the route of these arguments given a workspace that is large enough
+static ConvRoute sk_route_sized(const drnmi_conv_args& a, int splits) {
+  drnmi_conv_args q = a;
+  q.ws = reinterpret_cast<void*>(uintptr_t(256));
+  q.ws_bytes = INT64_MAX;
+  return sk_route(q, splits);
+}
+
+extern "C" int drnmi_conv_splitk_auto(const drnmi_conv_args* a) {
+  if (a == nullptr) return DRNMI_EINVAL;
+  const ConvRoute r = sk_route_sized(*a, 0);
+  return r.status != 0 ? r.status : r.splits;
+}
+
+extern "C" int64_t drnmi_conv_splitk_workspace_bytes(const drnmi_conv_args* a, int splits) {
+  if (a == nullptr) return -1;
+  const ConvRoute r = sk_route_sized(*a, splits);
+  return r.status != 0 ? -1 : sk_workspace_bytes(*a, r.splits);
 }
 
 // The labels-only video path's last 3x3 conv (D-22 layer8) with the seg classifier folded into its

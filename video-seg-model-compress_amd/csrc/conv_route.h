@@ -127,6 +127,17 @@ constexpr int kNumX3 = 3;
 const X6Variant& x3_variant(int v);
 bool x3_conv_supported(const drnmi_conv_args& p);
 
+// conv_sk.hip: split-K bf16 implicit GEMM for grids that leave most CUs idle (drnmi_conv_splitk): 128
+// channels x 64 pixels per tile, K steps of one tap x 64 channels cut into `splits` parts; rows by ks
+constexpr int kSkBCO = 128, kSkBPX = 64, kSkBK = 64;
+constexpr int kSkMaxSplits = DRNMI_SPLITK_MAX;
+bool sk_conv_supported(const drnmi_conv_args& p);
+int64_t sk_tiles(const drnmi_conv_args& p);
+int64_t sk_ticket_bytes(const drnmi_conv_args& p);
+const ConvKernel* sk_kernel(int ks);
+// the route of drnmi_conv_splitk and its queries (splits 0: the auto count)
+ConvRoute sk_route(const drnmi_conv_args& p, int splits);
+
 // patch_conv.hip / patch_f32.hip: the small-channel LDS-patch convs (DRNMI_ALGO_PATCH); the row
 // for these arguments, or nullptr (not supported)
 const ConvKernel* patch_kernel(const drnmi_conv_args& p);

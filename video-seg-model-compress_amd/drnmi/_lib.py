@@ -125,6 +125,11 @@ SIGNATURES = {
     "drnmi_conv_wgrad_workspace_bytes": (ctypes.c_int64, [ctypes.POINTER(WgradArgs)]),
     "drnmi_conv_workspace_bytes": (ctypes.c_int64, [ctypes.POINTER(ConvArgs)]),
     "drnmi_conv_stats_rows": (ctypes.c_int64, [ctypes.POINTER(ConvArgs)]),
+    "drnmi_conv_splitk": (ctypes.c_int, [ctypes.POINTER(ConvArgs), ctypes.c_int, _VP]),
+    "drnmi_conv_splitk_status": (ctypes.c_int, [ctypes.POINTER(ConvArgs), ctypes.c_int]),
+    "drnmi_conv_splitk_auto": (ctypes.c_int, [ctypes.POINTER(ConvArgs)]),
+    "drnmi_conv_splitk_workspace_bytes": (ctypes.c_int64, [ctypes.POINTER(ConvArgs), ctypes.c_int]),
+    "drnmi_conv_splitk_kernel_name": (ctypes.c_char_p, [ctypes.POINTER(ConvArgs), ctypes.c_int]),
     "drnmi_dgrad_s2_class_planes": (ctypes.c_int, [_VP, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _VP, _I32,
                                                    _VP]),
     "drnmi_bn_stats_partials_f32": (ctypes.c_int, [_VP, _I64, _I64, _I32, _F32, _F32, _VP, _VP, _VP, _VP, _VP, _VP]),

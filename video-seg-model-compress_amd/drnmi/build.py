@@ -37,7 +37,9 @@ EXTRA = {"front.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"], "block64.hip": ["-
          "frozen_bn.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
          # conv_x3.hip: the operand split as one fp32 operation per instruction as well
          "conv_x3.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
-         "wgrad_x3.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
+         "wgrad_x3.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
+         # conv_sk.hip: the partial sums added one fp32 operation per instruction
+         "conv_sk.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
 
 
 def sources():

@@ -90,6 +90,7 @@ class DRNSeg(nn.Module):
         self.precision = "fp32"
         self.block_sparse = False    # opt-in: measured slower than dense below ~60 % zero units
         self.sparse24 = False        # opt-in: 2:4-pruned bf16 layers on the sparse MFMA (set_sparse24)
+        self.low_latency = False     # opt-in: small grids on the split-K bf16 conv (set_low_latency)
         self._graph = lower_drnseg(self.layer, self.seg)
         self._act_scales = None      # int8: per-value activation scales (calibrate_int8)
         self._int8_hists = None      # value -> |x| histogram of the last histogram calibration
@@ -270,6 +271,8 @@ class DRNSeg(nn.Module):
             # follows int8's layout
             raise NotImplementedError(f"precision '{precision}' covers the DRN-D family only; {self.model_name} "
                                       "runs in 'fp32', 'fp32x' or 'bf16'")
+        if precision != "bf16" and getattr(self, "low_latency", False):
+            raise ValueError("the low-latency mode covers precision 'bf16' only: set_low_latency(False) first")
         self.precision = precision
         return self
 
@@ -490,6 +493,30 @@ class DRNSeg(nn.Module):
         device = torch.device(device or next(self.parameters()).device)
         return self._packed_net(device).sparse24_layers()
 
+    def set_low_latency(self, enabled: bool) -> "DRNSeg":
+        """bf16 inference on one small frame per call (the seg_video loop: model(img) per 300 x 300
+        frame): conv launches whose default tiles would leave most CUs idle run on the split-K kernel
+        (include/drnmi.h drnmi_conv_splitk, csrc/conv_sk.hip), which spreads a launch's K range over
+        the idle CUs and finishes in the same launch; blocks whose 1x1 downsample is folded into
+        their last conv run unfolded where that conv is routed.  The rule is Plan._route_low_latency
+        (DESIGN.md 3.10); launches it leaves alone, the front, the seg conv and the head keep their
+        kernels, so a large batch runs as without the mode.  Sums are added in another order than on
+        the default tiles: outputs agree to bf16 rounding, not bit for bit.  Opt-in, off by default;
+        precision "bf16" only (ValueError otherwise).  Drops the launch plans built so far."""
+        if enabled and self.precision != "bf16":
+            raise ValueError(f"the low-latency mode covers precision 'bf16' only, not '{self.precision}'")
+        self.low_latency = bool(enabled)
+        self._plans = {}
+        return self
+
+    def low_latency_layers(self, n, h, w, device=None) -> list:
+        """Names of the conv nodes the low-latency plan of n x h x w frames launches on the split-K
+        kernel ([] with the mode off)."""
+        if not self.low_latency:
+            return []
+        plan = self.plan(n, h, w, device)
+        return [plan.packed.graph.nodes[i].name for i in sorted(plan.sk)]
+
     def plan(self, n, h, w, device=None, keep_all=False) -> Plan:
         device = device or next(self.parameters()).device
         plan, _ = self._prepare(n, h, w, torch.device(device), keep_all=keep_all)
@@ -533,7 +560,7 @@ class DRNSeg(nn.Module):
         pkey = (self.precision, n, h, w, keep_all)
         plan = self._plans.get(pkey)
         if plan is None:
-            plan = Plan(pk, n, h, w, keep_all=keep_all)
+            plan = Plan(pk, n, h, w, keep_all=keep_all, low_latency=getattr(self, "low_latency", False))
             self._plans[pkey] = plan
         return plan, _lib.stream_ptr(device)
 

@@ -725,6 +725,11 @@ def _conv_out(h, k, s, p, d):
     return (h + 2 * p - d * (k - 1) - 1) // s + 1
 
 
+# The low-latency mode's routing rule (Plan._route_low_latency), set from scripts/low_latency_micro.py
+# on an MI355X (profiles/low_latency/README.txt)
+LOW_LATENCY_MAX_WG_FRAC = 0.5     # default-route workgroups, as a fraction of the CU count, below which a conv is routed
+LOW_LATENCY_MIN_KSTEPS_3X3 = 36   # K steps of 64 channels a routed 3x3 has at least (cin >= 256); 1x1s: unsplit only
+
 # segment(): NHWC logits rows for the labels head, and the seg classifier folded into the last conv
 # (drnmi_conv_stag_seg); tests switch these module flags off to compare with the unfused path
 LABELS_NHWC = True
@@ -732,7 +737,9 @@ SEG_FUSE = True
 
 # launch kind -> (C entry point, how many drnmi_conv_args lead its arguments, the library's name
 # query over those structs or, without one, the kernel's fixed name)
+# (conv_sk: the split count follows the struct in both the launch and the name query)
 LAUNCH_KINDS = {"conv": ("drnmi_conv2d_bn_act", 1, "drnmi_conv_kernel_name"),
+                "conv_sk": ("drnmi_conv_splitk", 2, "drnmi_conv_splitk_kernel_name"),
                 "stem_layer1": ("drnmi_stem_layer1", 2, "drnmi_stem_layer1_kernel_name"),
                 "conv_seg": ("drnmi_conv_stag_seg", 1, "drnmi_conv_stag_seg_kernel_name"),
                 "front": ("drnmi_video_front_u8", 0, "front3_kernel"),
@@ -769,9 +776,10 @@ class Launch:
 class Plan:
     """Launch plan for one (batch, H, W, precision): shapes, buffers, C-ABI arg structs."""
 
-    def __init__(self, packed: PackedNet, n: int, h: int, w: int, keep_all: bool = False):
+    def __init__(self, packed: PackedNet, n: int, h: int, w: int, keep_all: bool = False, low_latency: bool = False):
         self.packed = packed
         self.n, self.h, self.w = n, h, w
+        self.low_latency = bool(low_latency)
         dev = packed.device
         g = packed.graph
         self.shapes = {"input": (h, w)}
@@ -790,12 +798,13 @@ class Plan:
         for nd in g.nodes:
             if not nd.x_val:
                 nd.x_val, nd.r_val = nd.src, nd.res
-        self.skip = {i for i, nd in enumerate(g.nodes) if self.fuse and nd.fused_into >= 0}
+        self.sk, self.unfold = self._route_low_latency() if self.low_latency else ({}, set())
+        self.skip = self._folded_away()
         reads_of = {}
         for i, nd in enumerate(g.nodes):
             if i in self.skip:
                 reads_of[i] = set()
-            elif self.fuse and nd.fused:
+            elif self._fused(i):
                 reads_of[i] = {nd.x_val, nd.fused["x2_val"]}
             else:
                 reads_of[i] = {nd.x_val, nd.r_val} - {None}
@@ -841,6 +850,7 @@ class Plan:
                     if last_use.get(v) == i and v in self.bufs and v != nd.dst:
                         t = self.bufs[v]
                         pool.setdefault((t.numel(), t.dtype), []).append(t)
+        self.sk_ws = None
         self.args = self._all_args()
         self.stem_u8 = self._stem_u8_args()
         self.front_pack_t = None
@@ -857,8 +867,76 @@ class Plan:
     def _all_args(self) -> list:
         """Index-aligned with the nodes; None for a folded downsample and for conv1 of a fused
         16-channel block (conv2 keeps its args: they name the block's row)."""
-        return [None if i in self.skip or i in self.block16 else self._conv_args(nd)
+        args = [None if i in self.skip or i in self.block16 else self._conv_args(nd, i)
                 for i, nd in enumerate(self.packed.graph.nodes)]
+        if self.sk:
+            # one workspace for every conv_sk launch of the plan (they follow each other on one stream),
+            # zeroed once: every launch leaves its tickets zero (include/drnmi.h drnmi_conv_splitk)
+            lib = _lib.load()
+            need = max(int(lib.drnmi_conv_splitk_workspace_bytes(ctypes.byref(args[i]), S)) for i, S in self.sk.items())
+            if need > 0 and (self.sk_ws is None or self.sk_ws.numel() < need):
+                self.sk_ws = torch.zeros(need, dtype=torch.uint8, device=self.packed.device)
+            for i in self.sk:
+                if self.sk_ws is not None:
+                    args[i].ws, args[i].ws_bytes = self.sk_ws.data_ptr(), self.sk_ws.numel()
+                if lib.drnmi_conv_splitk_status(ctypes.byref(args[i]), self.sk[i]) != 0:
+                    raise RuntimeError(f"low latency: conv_sk refuses {self.packed.graph.nodes[i].name}")
+        return args
+
+    def _fused(self, i: int):
+        """The folded-downsample form of node i's launch in this plan, or None."""
+        return self.packed.graph.nodes[i].fused if self.fuse and i not in self.unfold else None
+
+    def _folded_away(self) -> set:
+        """The downsample nodes this plan computes inside their block's last conv."""
+        return {i for i, nd in enumerate(self.packed.graph.nodes)
+                if self.fuse and nd.fused_into >= 0 and nd.fused_into not in self.unfold}
+
+    def _route_low_latency(self):
+        """The low-latency mode's routing rule (DRNSeg.set_low_latency): a bf16 conv goes
+        to the split-K kernel (include/drnmi.h drnmi_conv_splitk, auto split count) when that kernel's
+        contract admits it, it is a 3x3 of at least LOW_LATENCY_MIN_KSTEPS_3X3 K steps of 64 channels or
+        a 1x1 the auto count leaves unsplit (and that neither has a folded downsample nor is one), and
+        its default route would start fewer than LOW_LATENCY_MAX_WG_FRAC x CUs workgroups (the
+        LDS-DMA tiles' 256 pixels x 256 / 128 / 64 channels).  A conv with a folded 1x1 downsample
+        is judged, and then launched, unfolded (the split-K kernel has no second input): the
+        downsample becomes a launch of its own, judged like any other.  The front, the fused
+        blocks, the seg conv and every 2:4 / unit-masked launch keep their kernels.
+        Returns ({node index: split count}, {indices of the convs launched unfolded})."""
+        pk, lib = self.packed, _lib.load()
+        if pk.precision != "bf16":
+            raise ValueError(f"the low-latency mode covers precision 'bf16' only, not '{pk.precision}'")
+        nodes = pk.graph.nodes
+        cus = torch.cuda.get_device_properties(pk.device).multi_processor_count
+        in_block = {j for pairs in pk.block_pairs.values() for i in pairs for j in (i, i + 1)} if self.fuse else set()
+        sk, unfold = {}, set()
+        for i, nd in enumerate(nodes):
+            c = nd.conv
+            if nd.i8 or nd.x6 or nd.wsp is not None or nd.unit_mask is not None or nd.out_fp32_nchw or i in in_block or \
+                    _uses_patch(nd, nd.cin_stride, pk.base):
+                continue
+            oh, ow = self.shapes[nd.dst]
+            m, cout = self.n * oh * ow, c.out_channels
+            bco = 64 if (nd.cin_stride <= 64 and cout % 256) else 256 if cout % 256 == 0 else 128 if cout % 128 == 0 else 64
+            if -(-m // 256) * -(-cout // bco) >= LOW_LATENCY_MAX_WG_FRAC * cus:
+                continue
+            a = _probe_args(nd, nd.cin_stride, nd.k, nd.k_pad)
+            a.n, (a.h, a.w), (a.ho, a.wo) = self.n, self.shapes[nd.src], (oh, ow)
+            S = lib.drnmi_conv_splitk_auto(ctypes.byref(a))
+            # measured (profiles/low_latency/README.txt): a split launch pays one L2 write-back per workgroup,
+            # which a 3x3 with fewer K steps and a split 1x1 do not earn back; an unsplit 1x1 gains from the
+            # small tile alone, but not where it would unfold a block (or is the unfolded downsample)
+            if c.kernel_size[0] == 3 and nd.k // 64 < LOW_LATENCY_MIN_KSTEPS_3X3:
+                continue
+            if c.kernel_size[0] == 1 and (S != 1 or nd.fused or nd.fused_into >= 0):
+                continue
+            if S >= 1:
+                sk[i] = S
+                if nd.fused:
+                    unfold.add(i)
+        # (a downsample that stays folded into a conv the rule left alone has no launch to route)
+        sk = {i: S for i, S in sk.items() if not (self.fuse and 0 <= nodes[i].fused_into and nodes[i].fused_into not in unfold)}
+        return sk, unfold
 
     def _decide_front(self):
         """How the uint8-frame path starts.  front_fused: layer0..layer2 as one drnmi_video_front_u8
@@ -934,7 +1012,7 @@ class Plan:
             return
         j = prod[0].row
         a = self.args[j]
-        if pk.quant_after.get(j) or not self._only_reader(j, i):
+        if pk.quant_after.get(j) or not self._only_reader(j, i) or j in self.sk:
             return
         i8 = seg.i8 and nodes[j].i8
         if i8 != (seg.i8 or nodes[j].i8) or (not i8 and not seg.scale_folded):
@@ -993,7 +1071,7 @@ class Plan:
         for i, nd in enumerate(nodes):
             if i in done:
                 continue                          # folded into another launch
-            fused = nd.fused if self.fuse else None
+            fused = self._fused(i)
             reads = () if u8 and i == 0 else (nd.x_val, fused["x2_val"] if fused else nd.r_val)
             c = 64 if i in self.block64 else 16 if i in self.block16 else 0
             if u8 and i == 0 and self.front_fused:
@@ -1010,12 +1088,14 @@ class Plan:
                     (ref(self.args[i]), segf["seg_w"], segf["seg_k_pad"], segf["seg_rows"], ptr("seg_part")))
             elif nhwc and i == self.seg_idx:
                 add(i, "conv", (i,), reads, ("logits_nhwc",), (ref(self.seg_nhwc_args),))
+            elif i in self.sk:
+                add(i, "conv_sk", (i,), reads, (nd.dst,), (ref(self.args[i]), self.sk[i]))
             else:
                 add(i, "conv", (fused["ds"], i) if fused else (i,), reads, (nd.dst,),
                     (ref(self.stem_u8 if u8 and i == 0 else self.args[i]),))
         return out
 
-    def _conv_args(self, nd: ConvNode) -> _lib.ConvArgs:
+    def _conv_args(self, nd: ConvNode, i: int) -> _lib.ConvArgs:
         pk = self.packed
         c = nd.conv
         ih, iw = self.shapes[nd.src]
@@ -1026,7 +1106,7 @@ class Plan:
         a.wgt = nd.wpk.data_ptr()
         a.scale = None if nd.scale_folded else nd.scale.data_ptr()
         a.shift = nd.shift.data_ptr()
-        fused = nd.fused if self.fuse else None
+        fused = self._fused(i)
         a.res = self.bufs[nd.r_val].data_ptr() if (nd.r_val and not fused) else None
         a.y = self.bufs[nd.dst].data_ptr()
         cout = c.out_channels
@@ -1078,8 +1158,7 @@ class Plan:
 
     def refresh_weight_ptrs(self):
         nodes = self.packed.graph.nodes
-        skip = {i for i, nd in enumerate(nodes) if self.fuse and nd.fused_into >= 0}
-        if skip != self.skip:
+        if self._folded_away() != self.skip:
             raise RuntimeError("repack changed the downsample fusion of a live plan")
         self.args = self._all_args()
         self.front_pack_t = None
