@@ -11,6 +11,9 @@ runs 32+ splits, the grouped reduce and conv_x6 with split-K 1, 2 and 4.  Here
     and a 4-ulp error each fail;
   * a CPU test walks D-22 and D-54 at the benchmark shape through the library's host-only plan
     queries and asserts that the kernel-level GPU cases below reach every route class found.
+The fp32x2 and frozen-BN steps (DRNSeg.set_precision("fp32x2"), DRNSeg.freeze_bn) are audited the same
+way: three-product launches under b2 (train_audit.py), the frozen records by checks of their own, the
+launch inventory of a frozen step asserted; their host-only controls are tests/test_train_audit_controls.py.
 """
 from __future__ import annotations
 
@@ -65,15 +68,22 @@ def test_train_launches_match_reference(cfg, group):
 @pytest.mark.gpu
 @pytest.mark.parametrize("cfg", list(A.CONFIGS))
 def test_train_launches_all_audited(cfg):
-    """Every record is of exactly one checked kind in one audited group; every node has its forward,
-    BN, wgrad and (input node excepted) dgrad records in every pass; the parity-class launches of
+    """Every record is of exactly one checked kind in one audited group (a kind without a check fails
+    here, by name); every node has its forward,
+    BN (live: statistics, bn_act, backward; frozen: frozen_prepare, frozen_act_bwd, frozen_unfold and no
+    statistics launch, the running statistics bit-identical across the step), wgrad and (input node
+    excepted) dgrad records in every pass; the parity-class launches of
     a node cover its whole destination; and the routes the runner took are the ones the host-only
     walk (train_audit.step_routes, which the class-coverage test relies on) predicts."""
     cap = A.capture(cfg)
-    arch, precision, shape, passes = A.CONFIGS[cfg]
+    arch, precision, shape, passes, opts = A.CONFIGS[cfg]
+    frozen = bool(opts.get("frozen"))
     assert [r.index for r in cap.recs] == list(range(len(cap.recs)))
     assert sum(len(A.launches(cfg, g)) for g in A.GROUPS) == len(cap.recs)
     assert {r.group for r in cap.recs} == set(A.GROUPS)
+    assert set(A.CHECKS) == set(A.NODE_KINDS) and set(A.HEAD_CHECKS) == set(A.HEAD_KINDS)
+    unaudited = [(r.index, r.kind) for r in cap.recs if r.kind not in A.CHECKS and r.kind not in A.HEAD_CHECKS]
+    assert not unaudited, f"records of a kind without a check: {unaudited}"
     for r in cap.recs:
         assert (r.kind in A.CHECKS) != (r.kind in A.HEAD_CHECKS), r.kind
         assert (r.name is None) == (r.kind in A.HEAD_CHECKS), (r.kind, r.name)
@@ -88,6 +98,19 @@ def test_train_launches_all_audited(cfg):
             m = cap.meta[name]
             have = [r.kind for r in kinds[name]]
             want = ["conv", "seg_nhwc", "bias_grad", "wgrad"] if m.seg else ["conv", "bn_stats", "bn_act", "bn_bwd", "wgrad"]
+            if frozen and not m.seg:
+                # frozen statistics: no bn_stats and no bn_bwd; one frozen_prepare and one frozen_act_bwd per BN
+                # node; wgrad(dr, x) and one frozen_unfold per conv whose weight or gamma is trained (here every
+                # gamma is: the conv of opts["no_weight_grad"] keeps both launches, for dgamma alone); bn_act only
+                # as the unfused end of a patch kernel with a residual
+                conv = [r for r in kinds[name] if r.kind == "conv"][0]
+                want = ["conv", "frozen_prepare", "frozen_act_bwd", "wgrad", "frozen_unfold"]
+                if conv.data["shift"] is None:
+                    assert conv.data["kernel"].startswith("patch_conv_kernel") and m.res is not None, name
+                    want.append("bn_act")
+                uf = [r for r in kinds[name] if r.kind == "frozen_unfold"][0]
+                assert (uf.data["dw"] is None) == (name in opts.get("no_weight_grad", ())), name
+                assert uf.data["dgamma"] is not None, name
             for k in want:
                 assert have.count(k) == 1, (name, k, have)
             dg = [r for r in kinds[name] if r.kind == "dgrad"]
@@ -102,10 +125,45 @@ def test_train_launches_all_audited(cfg):
                 assert cls[0].data["fill"] != "empty" or bool(owned.all()), name
             else:
                 assert len(dg) <= 1, name
-        assert A.recorded_routes(cap, step) == A.step_routes(arch, precision, shape[0], shape[2], shape[3])
+        assert A.recorded_routes(cap, step) == A.step_routes(arch, precision, shape[0], shape[2], shape[3],
+                                                             freeze_bn=frozen)
     names = sorted({A.launch_label(r).split(" x")[0].split(" split-K")[0] for r in cap.recs})
-    print(f"{cfg}: {len(cap.recs)} records, kernels {names}")
-    if precision == "fp32x":
+    print(f"{cfg}: {len(cap.recs)} records, 0 unaudited, kernels {names}")
+    if precision == "fp32x2":
+        # six or three products per launch, from the record: the patch kernels and the LDS-tile / direct weight
+        # gradients of an fp32x2 step keep six and take b, conv_x3 and the two-plane pre route take b2; no
+        # three-product launch sums more products than the controls of test_train_audit_controls.py do
+        n3 = {k: [r for r in cap.recs if r.kind == k and A.products(k, r.data) == 3] for k in ("conv", "dgrad", "wgrad")}
+        n6 = {k: [r for r in cap.recs if r.kind == k and A.products(k, r.data) == 6] for k in ("conv", "dgrad", "wgrad")}
+        assert all(n3.values()) and n6["conv"] and n6["wgrad"], ({k: len(v) for k, v in n3.items()}, n6.keys())
+        assert all(r.data["kernel"].startswith("patch_conv_kernel") for k in ("conv", "dgrad") for r in n6[k])
+        assert all(r.data["plan"][0] != "wgrad_x6_pre_kernel" for r in n6["wgrad"])
+        for k, rs in n3.items():
+            ks = [cap.meta[r.name].n * cap.meta[r.name].oh * cap.meta[r.name].ow if k == "wgrad" else r.data["k"]
+                  for r in rs]
+            assert max(ks) <= A.MAX_K3[k], (k, max(ks))
+            print(f"{cfg}: {len(rs)} three-product {k} launches, K {min(ks)} .. {max(ks)}, "
+                  f"{sum(v < A.B2_MIN_K for v in ks)} below K = {A.B2_MIN_K} (gated with 2^-15 S)")
+        for (k, summed), (ratio, label, node, kk) in sorted(A.three_product_ratios(cap).items()):
+            print(f"{cfg}: three-product {k}, K {'>=' if summed else '<'} {A.B2_MIN_K}: largest (|got - ref| - a - "
+                  f"2^-22 |ref|) / S = {ratio:.3e} of {A.B2_SUMMED if summed else A.B2_ONE:.3e} ({node}, {label}, K {kk})")
+    if frozen:
+        assert not any(r.kind in ("bn_stats", "bn_bwd") for r in cap.recs)
+        assert cap.stats[0].keys() == cap.stats[1].keys() and any("running_var" in k for k in cap.stats[0])
+        for k, v in cap.stats[0].items():        # running_mean, running_var, num_batches_tracked: not written
+            assert v.dtype == cap.stats[1][k].dtype and torch.equal(v, cap.stats[1][k]), k
+        # as in the live-BN step (below) the backward finds dres unset in these graphs: the store is audited
+        # here, the accumulating form by test_frozen_act_bwd_dres_accumulates
+        fb = [r for r in cap.recs if r.kind == "frozen_act_bwd"]
+        assert any(r.data["dres"] is not None for r in fb) and not any(r.data["dres_before"] is not None for r in fb)
+        assert {r.data["relu"] for r in fb} == {True, False}          # a block's last BN, its downsample's
+        uf = [r for r in cap.recs if r.kind == "frozen_unfold"]
+        acc = {(r.data["dw_before"] is not None, r.data["dgamma_before"] is not None) for r in uf if r.data["dw"] is not None}
+        assert acc == ({(False, False), (True, True)} if passes > 1 else {(False, False)}), acc
+        assert any(r.data["dbeta_before"] is not None for r in fb) == (passes > 1)
+        assert any(r.kind == "dgrad" and r.data["fill"] == "prev" for r in cap.recs)
+        return
+    if precision in ("fp32x", "fp32x2"):
         forms = {r.data["form"] for r in cap.recs if r.kind == "dgrad"}
         assert "class" in forms and "s1" in forms, forms
         if arch == "drn_d_54":       # 1x1 stride-2 downsamples: classes no tap reaches stay zero-filled
@@ -227,6 +285,16 @@ X6_PLAN_CASES = [
     (1, 17, 19, 64, 64, 3, 1, 1, False, "conv_x6_kernel<3, 32, 2, 2>", 1),
     (1, 17, 19, 256, 64, 1, 0, 1, False, "conv_x6_kernel<1, 32, 2, 2>", 1),
 ]
+# the same for conv_x3 (fp32x2; tile id v + 3 S, S = 1: the default route without a workspace): the classes of
+# the benchmark's plan that no audit configuration reaches (at 1/8 resolution of a 96 x 64 crop every 128-wide
+# 3x3 launch splits K), and one per tile width beside them; gate of train_audit.py with b2
+X3_PLAN_CASES = [
+    (2, 11, 13, 128, 128, 3, 1, 1, True, "conv_x3_kernel<3, 64, 2, 2, 1>", 1),
+    (2, 11, 13, 128, 128, 3, 2, 2, False, "conv_x3_kernel<3, 64, 2, 2, 1>", 2),
+    (1, 17, 19, 64, 128, 1, 0, 1, True, "conv_x3_kernel<1, 64, 2, 2, 1>", 1),
+    (1, 17, 19, 64, 64, 3, 1, 1, False, "conv_x3_kernel<3, 32, 2, 2, 1>", 1),
+    (1, 17, 19, 256, 64, 1, 0, 1, False, "conv_x3_kernel<1, 32, 2, 2, 1>", 1),
+]
 # (n, ih, iw, cin, cout, ks, pad): stride-2 convs whose fp32x data gradient runs as parity-class
 # launches (ks 2 / 1 kernels, y_sr row stride, asymmetric padding); odd sizes, both tile widths
 S2_CLASS_CASES = [
@@ -265,6 +333,28 @@ def _x6_case_tile(case):
         if name is not None and name.decode() == case[9]:
             return v + 6 * case[10]
     raise AssertionError(f"no conv_x6 variant gives {case[9]} for {case}")
+
+
+def _x3_case_args(case, tile=-1):
+    from drnmi import _lib
+    a = _x6_case_args(case, tile)
+    a.dtype = _lib.DRNMI_F32X2
+    if case[10] == 1:
+        a.ws, a.ws_bytes = None, 0
+    return a
+
+
+def _x3_case_tile(case):
+    """The tile id whose launch is the case's kernel at its split count: -1 (the launcher's own choice, one
+    split) or a forced v + 3 S."""
+    from drnmi import _lib
+    lib = _lib.load()
+    for tile in ([-1] if case[10] == 1 else [v + 3 * case[10] for v in range(3)]):
+        a = _x3_case_args(case, tile)
+        name = lib.drnmi_conv_kernel_name(ctypes.byref(a))
+        if name is not None and name.decode() == case[9]:
+            return tile
+    raise AssertionError(f"no conv_x3 variant gives {case[9]} for {case}")
 
 
 def _s2_class_plan(ks, pad):
@@ -322,11 +412,12 @@ def test_wgrad_plan_query():
 def test_gpu_cases_reach_every_workload_route_class():
     """D-22 and D-54 at the benchmark shape, fp32 and fp32x: every class of weight-gradient launch
     (kernel, splits 1 / 2..31 / >= 32, reduce kernel, ragged last split, M % 32 != 0) and of conv_x6
-    forward / data-gradient launch (kernel, split-K count) is reached by a kernel-level GPU case."""
+    forward / data-gradient launch (kernel, split-K count) is reached by a kernel-level GPU case; fp32x2:
+    every conv_x3 class (kernel, split-K count) by an audited fp32x2 step or a kernel-level case."""
     wg, cx = set(), set()
     for arch in ("drn_d_22", "drn_d_54"):
         for precision in ("fp32", "fp32x"):
-            w_, c_ = A.route_classes(A.step_routes(arch, precision, *BENCH_SHAPE))
+            w_, c_, _ = A.route_classes(A.step_routes(arch, precision, *BENCH_SHAPE))
             wg |= w_
             cx |= c_
     assert len(wg) >= 12 and len(cx) >= 12, (sorted(wg), sorted(cx))
@@ -345,6 +436,27 @@ def test_gpu_cases_reach_every_workload_route_class():
     for c in wg:
         if c[3] and c[0] in ("wgrad_kernel<64, false>", "wgrad_x6_pre_kernel") and c[1] == "2..31":
             assert c[:4] + (True,) in got_wg, c
+    # fp32x2: the conv_x3 classes of the same plan, reached by the audit's fp32x2 configurations (their recorded
+    # routes equal step_routes: test_train_launches_all_audited) or by X3_PLAN_CASES; its weight-gradient plans
+    # are fp32x's (one plan function), the two-plane pre route among them
+    c3 = set()
+    for arch in ("drn_d_22", "drn_d_54"):
+        w3, c6, c_ = A.route_classes(A.step_routes(arch, "fp32x2", *BENCH_SHAPE))
+        assert not c6 and w3 <= wg, (sorted(c6), sorted(w3 - wg))
+        c3 |= c_
+    got_c3 = set()
+    for arch, precision, shape, _, opts in A.CONFIGS.values():
+        if precision == "fp32x2":
+            got_c3 |= A.route_classes(A.step_routes(arch, precision, shape[0], shape[2], shape[3],
+                                                    freeze_bn=bool(opts.get("frozen"))))[2]
+    by_cfg = len(got_c3 & c3)
+    for c in X3_PLAN_CASES:
+        _x3_case_tile(c)
+        got_c3.add((c[9], c[10]))
+    print(f"workload: {len(c3)} conv_x3 classes {sorted(c3)}; the audit configurations reach {by_cfg}, "
+          f"with X3_PLAN_CASES {len(got_c3 & c3)}")
+    assert len(c3) >= 7 and not c3 - got_c3, sorted(c3 - got_c3)
+    assert any(c[0] == "wgrad_x6_pre_kernel" for c in wg)
 
 
 def _wgrad_node(case):
@@ -410,6 +522,68 @@ def test_conv_x6_plan_classes_match_float64(case):
          for dt in (F64, torch.float32)]
     b = A.B_REL * A._nhwc(A._conv(A._nchw(x, n, h, w, cin, F64).abs(), wt.to(F64).abs(), None, m))
     assert not _report(f"{kernel} split-K {S}", [A.gate("y", y.cpu(), v[0], v[1], b)])
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("case", X3_PLAN_CASES, ids=lambda c: f"{c[9]}-S{c[10]}".replace(" ", ""))
+def test_conv_x3_plan_classes_match_float64(case):
+    """conv_x3 as the fp32x2 fine-tune launches it (two of the three packed planes, no scale, fp32 NHWC out,
+    residual = the accumulating data-gradient destination) at the tile and split-K classes of the benchmark
+    that the audit's small crops do not reach, against float64 under the audit's gate with b2."""
+    from drnmi import _lib, ops
+    from drnmi.engine import split3_bf16
+    n, h, w, cin, cout, ks, pad, dil, res, kernel, S = case
+    g = torch.Generator().manual_seed(cin + cout + ks + S)
+    x = torch.relu(torch.randn(n, h, w, cin, generator=g))
+    wt = torch.randn(cout, cin, ks, ks, generator=g) * (2.0 / (cin * ks * ks)) ** 0.5
+    a = _x3_case_args(case, _x3_case_tile(case))
+    r = torch.randn(n, a.ho, a.wo, cout, generator=g) if res else None
+    wpk, k = ops.pack_conv_weight(wt.to(DEV), cin, torch.float32)
+    assert k == a.k and wpk.shape == (a.cout_pad, a.k_pad)
+    planes = split3_bf16(wpk)
+    xd = x.to(DEV)
+    y = r.to(DEV).clone() if res else torch.empty(n, a.ho, a.wo, cout, device=DEV)
+    shift = torch.zeros(a.cout_pad, device=DEV)
+    ws = torch.empty(max(a.ws_bytes, 256), dtype=torch.uint8, device=DEV)
+    a.x, a.wgt, a.shift, a.y = xd.data_ptr(), planes.data_ptr(), shift.data_ptr(), y.data_ptr()
+    if S > 1:
+        a.ws = ws.data_ptr()
+    a.res = y.data_ptr() if res else None
+    assert _lib.load().drnmi_conv_kernel_name(ctypes.byref(a)).decode() == kernel
+    _lib.check(_lib.load().drnmi_conv2d_bn_act(ctypes.byref(a), ctypes.c_void_p(_lib.stream_ptr())), "conv_x3")
+    torch.cuda.synchronize()
+    m = A.NodeMeta("case", "x", "y", None, False, False, n, cin, cout, ks, 1, pad, dil, h, w, a.ho, a.wo, weight=wt)
+    v = [A._nhwc(A._conv(A._nchw(x, n, h, w, cin, dt), wt.to(dt), None, m)) + (r.to(dt) if res else 0)
+         for dt in (F64, torch.float32)]
+    Sabs = A._nhwc(A._conv(A._nchw(x, n, h, w, cin, F64).abs(), wt.to(F64).abs(), None, m))
+    b2, Sabs = A.split_term("conv", {"x3": True, "kernel": kernel}, Sabs, k)
+    assert k >= A.B2_MIN_K or float(b2.max()) == A.B2_ONE * float(Sabs.max())
+    assert not _report(f"{kernel} split-K {S} K {k}", [A.gate("y", y.cpu(), v[0], v[1], b2, S=Sabs)])
+
+
+@pytest.mark.gpu
+def test_frozen_act_bwd_dres_accumulates():
+    """drnmi_frozen_bn_act_bwd_f32 with dres_accumulate = 1 and dbeta_accumulate = 1 (a residual value that
+    already holds a gradient; the fine-tune graphs never present one) through the audit's check."""
+    from drnmi import _lib
+    lib = _lib.load()
+    sp = ctypes.c_void_p(_lib.stream_ptr())
+    vp = lambda t: ctypes.c_void_p(t.data_ptr())
+    rows, C = 2 * 9 * 5, 64
+    m, g = _node(rows + C, 2, C, C, 1, 1, 0, 1, 9, 5, relu=True, res="r")
+    z = torch.relu(torch.randn(rows, C, generator=g))
+    dz, dres0, db0 = torch.randn(rows, C, generator=g), torch.randn(rows, C, generator=g), torch.randn(C, generator=g)
+    dzd, zd, dresd, dbd = (t.to(DEV).contiguous() for t in (dz, z, dres0, db0))
+    dsum = torch.zeros(C, dtype=torch.float64, device=DEV)
+    ws = torch.empty(lib.drnmi_reduce_workspace_bytes(rows, C), dtype=torch.uint8, device=DEV)
+    _lib.check(lib.drnmi_frozen_bn_act_bwd_f32(vp(dzd), vp(zd), 1, rows, C, vp(dresd), 1, vp(dbd), 1, vp(dsum), vp(ws),
+                                               sp), "frozen_act_bwd")
+    torch.cuda.synchronize()
+    rec = {"dz": dz, "z": z, "relu": True, "dr": dzd.cpu(), "dres": dresd.cpu(), "dres_before": dres0,
+           "dbeta": dbd.cpu(), "dbeta_before": db0, "dbeta_sum": dsum.cpu()}
+    figs = A.check_frozen_act_bwd(m, rec)
+    assert {f.what for f in figs} >= {"dres (accumulated)", "dbeta (accumulated)"}
+    assert not _report(f"frozen_act_bwd {rows} x {C}", figs)
 
 
 @pytest.mark.gpu

@@ -21,6 +21,22 @@ margin.  2^-22 |ref| is two fp32 ulps of the result (the final rounding and one 
 bf16 launches only (conv_x6, the X6 patch kernels, drnmi_conv_wgrad_f32x3): the three-way bf16
 split is exact, the products dropped are x2 w3, x3 w2 and x3 w3, bounded by (2^-27 + 2^-27 + 2^-36)
 |x| |w|; b = 2^-25 (|x| conv |w|) in float64 is that bound with a factor of two.
+b2 replaces b for a three-product launch (a conv or data gradient whose recorded kernel is conv_x3_kernel*,
+a weight gradient of an fp32x2 step whose plan is the two-plane pre route): with S = |x| conv |w| (or
+|dy|, |x| / |w|, |dy|) and K the number of products the launch sums per output (the launch's own k =
+ks^2 x channel stride -- a parity-class launch has its own ks -- and the pixel count M of a weight
+gradient), b2 = 3 x 2^-18 S from K = 288 on and 2^-15 S below: include/drnmi.h's bound of a summed launch
+and its worst case of one product (tests/test_fp32x2.py, tests/test_gpu_fp32x2.py).  Six or three is
+decided per launch from the record: in an fp32x2 step the patch kernels and the LDS-tile and direct
+weight gradients keep six products and are gated with b.
+
+Frozen BN statistics (DRNSeg.freeze_bn; csrc/frozen_bn.hip, include/drnmi.h), per channel, in fp32 as
+the kernels round it:  rstd = 1 / sqrt(running_var + eps),  s = gamma * rstd,  t = beta - running_mean * s
+(pad channels: 0);  z = relu?(conv(x, s o w) + t [+ res]);  dr = relu ? (z > 0 ? dz : 0) : dz;
+dres = dr or += dr;  dbeta = sum_rows dr (fp64, then fp32);  G = wgrad(dr, x);  dw = s o G;
+dgamma = rstd * (<G[c], w[c]> - running_mean * sum_rows dr), the bracket in fp64.  The forward and the data
+gradient read the folded weight s o w (TrainRunner._pack / _pack_dgrad give s to the pack); the
+weight gradient reads dr and x only.
 """
 from __future__ import annotations
 
@@ -34,24 +50,43 @@ from plan_audit import GROUPS, group_of
 
 SEED = 13
 IGNORE = 255
-# name -> (arch, precision, input shape, passes): passes forward + backward runs without zero_grad
+# name -> (arch, precision, input shape, passes, options): passes forward + backward runs without
+# zero_grad.  options: frozen = freeze_bn() before the first forward; no_weight_grad = nodes whose conv
+# weight is not trained while their BN's gamma is (the frozen step still needs wgrad(dr, x) there)
 CONFIGS = {
-    "d22_fp32_1x72x40": ("drn_d_22", "fp32", (1, 3, 72, 40), 1),
-    "d22_fp32x_1x72x40": ("drn_d_22", "fp32x", (1, 3, 72, 40), 1),
-    "d54_fp32_2x96x64": ("drn_d_54", "fp32", (2, 3, 96, 64), 1),
-    "d54_fp32x_2x96x64": ("drn_d_54", "fp32x", (2, 3, 96, 64), 1),
-    "d22_fp32x_2x64x64_acc": ("drn_d_22", "fp32x", (2, 3, 64, 64), 2),
+    "d22_fp32_1x72x40": ("drn_d_22", "fp32", (1, 3, 72, 40), 1, {}),
+    "d22_fp32x_1x72x40": ("drn_d_22", "fp32x", (1, 3, 72, 40), 1, {}),
+    "d54_fp32_2x96x64": ("drn_d_54", "fp32", (2, 3, 96, 64), 1, {}),
+    "d54_fp32x_2x96x64": ("drn_d_54", "fp32x", (2, 3, 96, 64), 1, {}),
+    "d22_fp32x_2x64x64_acc": ("drn_d_22", "fp32x", (2, 3, 64, 64), 2, {}),
     # two conv+BN+ReLU units in layer7 and layer8 (BasicBlock and Bottleneck trunks)
-    "d24_fp32_1x72x40": ("drn_d_24", "fp32", (1, 3, 72, 40), 1),
-    "d24_fp32x_1x72x40": ("drn_d_24", "fp32x", (1, 3, 72, 40), 1),
-    "d56_fp32x_1x64x64": ("drn_d_56", "fp32x", (1, 3, 64, 64), 1),
+    "d24_fp32_1x72x40": ("drn_d_24", "fp32", (1, 3, 72, 40), 1, {}),
+    "d24_fp32x_1x72x40": ("drn_d_24", "fp32x", (1, 3, 72, 40), 1, {}),
+    "d56_fp32x_1x64x64": ("drn_d_56", "fp32x", (1, 3, 64, 64), 1, {}),
+    # three-product launches (conv_x3, the two-plane pre weight gradient): the shapes of the fp32x rows
+    "d22_fp32x2_1x72x40": ("drn_d_22", "fp32x2", (1, 3, 72, 40), 1, {}),
+    "d54_fp32x2_2x96x64": ("drn_d_54", "fp32x2", (2, 3, 96, 64), 1, {}),
+    "d22_fp32x2_2x64x64_acc": ("drn_d_22", "fp32x2", (2, 3, 64, 64), 2, {}),
+    # frozen BN statistics: the exact-fp32 igemm, conv_x6 and conv_x3 with the fused epilogue
+    "d22_fp32_frozen_1x72x40": ("drn_d_22", "fp32", (1, 3, 72, 40), 1,
+                                {"frozen": True, "no_weight_grad": ("layer.3.1.conv1", "layer.6.0.conv2")}),
+    "d22_fp32x_frozen_2x64x64_acc": ("drn_d_22", "fp32x", (2, 3, 64, 64), 2, {"frozen": True}),
+    "d54_fp32x2_frozen_2x96x64": ("drn_d_54", "fp32x2", (2, 3, 96, 64), 1, {"frozen": True}),
 }
 # every kind a record may have; each has exactly one check below
-NODE_KINDS = ("conv", "bn_stats", "bn_act", "seg_nhwc", "bias_grad", "bn_bwd", "wgrad", "dgrad")
+NODE_KINDS = ("conv", "bn_stats", "bn_act", "seg_nhwc", "bias_grad", "bn_bwd", "wgrad", "dgrad", "frozen_prepare",
+              "frozen_act_bwd", "frozen_unfold")
 HEAD_KINDS = ("head", "ce", "head_bwd")
 F64 = torch.float64
 EPS_REL = 2.0 ** -22
 B_REL = 2.0 ** -25
+# three-product launches: include/drnmi.h's bounds for DRNMI_F32X2 (tests/test_fp32x2.py derives both)
+B2_SUMMED = 3 * 2.0 ** -18       # a sum of K >= 288 products of either sign
+B2_ONE = 2.0 ** -15              # the worst case of one product: holds for any K
+B2_MIN_K = 288
+# the longest sums the three-product launches of CONFIGS make (asserted by the GPU audit): the host-only
+# controls of tests/test_train_audit_controls.py drop a cross product at these lengths
+MAX_K3 = {"conv": 18432, "dgrad": 4608, "wgrad": 192}
 
 
 # ----------------------------------------------------------------------------- records
@@ -82,6 +117,9 @@ class NodeMeta:
     eps: float = 1e-5
     momentum: float = 0.1
     keys: dict = field(default_factory=dict)    # weight / bias / gamma / beta -> parameter name
+    rmean: torch.Tensor | None = None           # running statistics before the captured step
+    rvar: torch.Tensor | None = None
+    frozen: bool = False                        # the step ran on them (freeze_bn)
 
 
 @dataclass
@@ -101,6 +139,7 @@ class Capture:
     meta: dict                # node name -> NodeMeta
     order: list               # node names in graph order
     params: dict              # parameter name -> final .grad (host)
+    stats: tuple = ()         # ({buffer name: tensor} before the first pass, the same after the last)
 
 
 @dataclass
@@ -114,15 +153,18 @@ class Figure:
     got: float
     ref: float
     n: int
+    ratio: float | None = None     # three-product launches: max (|got - ref| - a - 2^-22 |ref|) / S
 
     def __str__(self):
+        r = "" if self.ratio is None else f", three products: error over a / S {self.ratio:.2e}"
         return (f"{self.what}: a {self.a:.2e} b {self.b:.2e} worst excess {self.excess:.2e} at {self.where} "
-                f"(got {self.got:.9g}, ref {self.ref:.9g}, {self.n} elements)")
+                f"(got {self.got:.9g}, ref {self.ref:.9g}, {self.n} elements{r})")
 
 
 def gate(what: str, got: torch.Tensor, ref: torch.Tensor, v32: torch.Tensor | None, b: torch.Tensor | None = None,
-         a: float | None = None) -> Figure:
-    """|got - ref| <= 2^-22 |ref| + a (+ b) over every element; a from v32 unless given."""
+         a: float | None = None, S: torch.Tensor | None = None) -> Figure:
+    """|got - ref| <= 2^-22 |ref| + a (+ b) over every element; a from v32 unless given.  S (three-product
+    launches): also report max (|got - ref| - a - 2^-22 |ref|) / S, a measurement and no part of the gate."""
     ref = ref.to(F64)
     got64 = got.to(F64)
     assert got64.shape == ref.shape, (what, tuple(got64.shape), tuple(ref.shape))
@@ -137,8 +179,32 @@ def gate(what: str, got: torch.Tensor, ref: torch.Tensor, v32: torch.Tensor | No
     over = torch.where(torch.isfinite(got64), over, torch.full_like(over, float("inf")))
     k = int(torch.argmax(over.reshape(-1)))
     where = tuple(int(i) for i in torch.unravel_index(torch.tensor(k), over.shape)) if over.dim() else ()
+    ratio = None
+    if S is not None:
+        ok = S > 0
+        ratio = float((((got64 - ref).abs() - EPS_REL * ref.abs() - a)[ok] / S[ok]).max()) if bool(ok.any()) else 0.0
     return Figure(what, a, float(b.max()) if b is not None else 0.0, float(over.reshape(-1)[k]), where,
-                  float(got64.reshape(-1)[k]), float(ref.reshape(-1)[k]), ref.numel())
+                  float(got64.reshape(-1)[k]), float(ref.reshape(-1)[k]), ref.numel(), ratio)
+
+
+def products(kind: str, d: dict) -> int:
+    """Products per (x, w) pair of a recorded conv / dgrad / wgrad launch: 0 exact fp32, 6 or 3 split bf16."""
+    if not d["x3"]:
+        return 0
+    if kind == "wgrad":
+        return 3 if d.get("two") and d["plan"][0] == "wgrad_x6_pre_kernel" else 6
+    return 3 if (d.get("kernel") or "").startswith("conv_x3_kernel") else 6
+
+
+def split_term(kind: str, d: dict, S: torch.Tensor, k: int):
+    """(b or b2 or None, S or None) of a launch: the gate's split-bf16 term from S = |x| conv |w| in float64
+    and the number k of products summed per output, and S again where the launch keeps three products."""
+    n = products(kind, d)
+    if n == 0:
+        return None, None
+    if n == 6:
+        return B_REL * S, None
+    return (B2_SUMMED if k >= B2_MIN_K else B2_ONE) * S, S
 
 
 def exact(what: str, got: torch.Tensor, ref: torch.Tensor) -> Figure:
@@ -177,16 +243,61 @@ def _dgrad(w, dy, m: NodeMeta):
                                       dilation=m.dil)
 
 
+def frozen_affine(m: NodeMeta, dt):
+    """(s, t, rstd) [cout] of a BN node on its running statistics, in dtype dt: this file's own
+    restatement of drnmi_frozen_bn_prepare_f32 (eps is the fp32 value the kernel reads)."""
+    eps = float(torch.tensor(m.eps, dtype=torch.float32))
+    rstd = 1.0 / torch.sqrt(m.rvar.to(dt) + eps)
+    s = m.gamma.to(dt) * rstd
+    return s, m.beta.to(dt) - m.rmean.to(dt) * s, rstd
+
+
+def folded_weight(m: NodeMeta, dt) -> torch.Tensor:
+    """The weight a launch reads: s o w in a frozen step's BN nodes (s restated here, not taken from the
+    frozen_prepare record, which is the launch before this one in the chain), w everywhere else."""
+    w = m.weight.to(dt)
+    if m.frozen and m.gamma is not None:
+        w = w * frozen_affine(m, dt)[0].reshape(-1, 1, 1, 1)
+    return w
+
+
+def check_frozen_prepare(m: NodeMeta, d: dict) -> list:
+    """s, t and rstd of one BN node from gamma, beta and the running statistics; the channels from cout
+    up to cout_pad are written as 0 (a zero weight row, a zero shift), compared exactly."""
+    r64, r32 = frozen_affine(m, F64), frozen_affine(m, torch.float32)
+    figs = []
+    for i, key in enumerate(("s", "t", "rstd")):
+        assert d[key].dim() == 1 and d[key].numel() >= m.cout, (m.name, key, d[key].shape)
+        figs.append(gate(key, d[key][:m.cout], r64[i], r32[i]))
+        figs.append(exact(f"{key} padding channels", d[key][m.cout:], torch.zeros_like(d[key][m.cout:])))
+    return figs
+
+
 def check_conv(m: NodeMeta, d: dict) -> list:
+    """Forward conv.  In a frozen step a BN node's launch reads s o w and, in its fused form, carries the
+    recorded shift (= t), residual and ReLU: relu?(conv(x, w) * s + t + res); the unfused form (a patch
+    kernel with a residual) has none of the three and drnmi_bn_act_f32 follows (check_bn_act)."""
+    fz = m.frozen and m.gamma is not None
+    assert fz == ("shift" in d), m.name
     outs = {}
     for dt in (F64, torch.float32):
         x = _nchw(d["x"], m.n, m.ih, m.iw, m.cin, dt)
-        outs[dt] = _conv(x, m.weight.to(dt), m.bias.to(dt) if m.bias is not None else None, m)
-    b = None
+        y = _conv(x, folded_weight(m, dt), m.bias.to(dt) if m.bias is not None else None, m)
+        if fz:
+            assert (d["shift"] is None) <= (d["res"] is None and not d["relu"]), m.name
+            if d["shift"] is not None:
+                y = y + d["shift"][:m.cout].to(dt).reshape(1, -1, 1, 1)
+            if d["res"] is not None:
+                y = y + _nchw(d["res"], m.n, m.oh, m.ow, m.cout, dt)
+            if d["relu"]:
+                y = torch.relu(y)
+        outs[dt] = y
+    b, S = None, None
     if d["x3"]:
-        b = B_REL * _conv(_nchw(d["x"], m.n, m.ih, m.iw, m.cin, F64).abs(), m.weight.to(F64).abs(), None, m)
+        S = _conv(_nchw(d["x"], m.n, m.ih, m.iw, m.cin, F64).abs(), folded_weight(m, F64).abs(), None, m)
+        b, S = split_term("conv", d, S, d.get("k", m.ks * m.ks * m.cin))
     got = d["y"] if m.seg else _nchw(d["y"], m.n, m.oh, m.ow, m.cout, torch.float32)
-    figs = [gate("y", got, outs[F64], outs[torch.float32], b)]
+    figs = [gate("y", got, outs[F64], outs[torch.float32], b, S=S)]
     if not m.seg and d["y"].reshape(m.n * m.oh * m.ow, -1).shape[1] != m.cout:
         pad = d["y"].reshape(m.n * m.oh * m.ow, -1)[:, m.cout:]
         figs.append(exact("y padding channels", pad, torch.zeros_like(pad)))
@@ -236,8 +347,17 @@ def check_bn_act(m: NodeMeta, d: dict) -> list:
     y = d["y"].reshape(rows, -1)
     res = d["res"].reshape(rows, -1) if d["res"] is not None else None
     assert (res is not None) == (m.res is not None), m.name
-    r = [bn_act_ref(y, d["mean"], d["invstd"], m.gamma, m.beta, res, m.relu, dt) for dt in (F64, torch.float32)]
-    return [gate("z", d["z"].reshape(rows, -1), r[0], r[1])]
+    gamma, beta, figs = m.gamma, m.beta, []
+    assert m.frozen == ("beta" in d), m.name
+    if m.frozen:
+        # the unfused end of a frozen conv (a patch kernel with a residual): y = conv(x, s o w), and this
+        # launch runs with mean 0, invstd 1, no gamma and beta = t, the recorded shift
+        cs = y.shape[1]
+        figs = [exact("unit mean", d["mean"][:cs], torch.zeros(cs)), exact("unit invstd", d["invstd"][:cs], torch.ones(cs))]
+        gamma, beta = torch.ones(cs), d["beta"][:cs]
+    r = [bn_act_ref(y, d["mean"][:y.shape[1]], d["invstd"][:y.shape[1]], gamma, beta, res, m.relu, dt)
+         for dt in (F64, torch.float32)]
+    return figs + [gate("z", d["z"].reshape(rows, -1), r[0], r[1])]
 
 
 def _up_weight(up: torch.Tensor, c: int, dt) -> torch.Tensor:
@@ -333,38 +453,106 @@ def check_bn_bwd(m: NodeMeta, d: dict) -> list:
     return figs
 
 
+def frozen_act_bwd_ref(dz, z, relu, dt):
+    """dr = relu ? (z > 0 ? dz : 0) : dz, the mask taken from the GPU's own z, and its per-channel sum."""
+    dr = dz.to(dt)
+    if relu:
+        dr = torch.where(z > 0, dr, torch.zeros_like(dr))
+    return dr, dr.sum(0)
+
+
+def check_frozen_act_bwd(m: NodeMeta, d: dict) -> list:
+    """Backward through relu?(. + t [+ res]).  dr and a fresh dres are stores with no arithmetic: exact."""
+    rows = m.n * m.oh * m.ow
+    sh = lambda t: t.reshape(rows, -1)
+    assert d["relu"] == m.relu and (d["dres"] is not None) == (m.res is not None), m.name
+    r = [frozen_act_bwd_ref(sh(d["dz"]), sh(d["z"]), m.relu, dt) for dt in (F64, torch.float32)]
+    figs = [exact("dr", sh(d["dr"]), r[1][0])]
+    if d["dres"] is not None:
+        if d["dres_before"] is None:
+            figs.append(exact("dres", sh(d["dres"]), r[1][0]))
+        else:
+            figs.append(gate("dres (accumulated)", sh(d["dres"]), r[0][0] + sh(d["dres_before"]).to(F64),
+                             r[1][0] + sh(d["dres_before"])))
+    figs.append(gate("dbeta_sum", d["dbeta_sum"][:m.cout], r[0][1], r[1][1]))
+    if d["dbeta"] is not None:
+        v64, v32 = r[0][1], r[1][1]
+        if d["dbeta_before"] is not None:
+            v64, v32 = v64 + d["dbeta_before"].to(F64), v32 + d["dbeta_before"]
+        figs.append(gate("dbeta (accumulated)" if d["dbeta_before"] is not None else "dbeta", d["dbeta"], v64, v32))
+    return figs
+
+
+def frozen_unfold_ref(g, w, s, rstd, rmean, dbeta_sum, dt):
+    """(dw, dgamma) = (s o G, rstd * (<G[c], w[c]> - running_mean * sum_rows dr)) in dtype dt."""
+    g = g.to(dt)
+    dw = s.to(dt).reshape(-1, 1, 1, 1) * g
+    dot = (g * w.to(dt)).flatten(1).sum(1)
+    return dw, rstd.to(dt) * (dot - rmean.to(dt) * dbeta_sum.to(dt))
+
+
+def check_frozen_unfold(m: NodeMeta, d: dict) -> list:
+    """dw = s o G onto weight.grad and dgamma onto gamma.grad, stored or accumulated, from the launch's own
+    G, w, s, rstd and dbeta_sum; running_mean is the captured model's.  dw is None where the conv weight is
+    not trained (the launch then runs for dgamma alone)."""
+    c = m.cout
+    assert torch.equal(d["w"], m.weight), m.name
+    r = [frozen_unfold_ref(d["g"], d["w"], d["s"][:c], d["rstd"][:c], m.rmean, d["dbeta_sum"][:c], dt)
+         for dt in (F64, torch.float32)]
+    figs = []
+    assert d["dw"] is not None or d["dgamma"] is not None, m.name
+    for i, key in ((0, "dw"), (1, "dgamma")):
+        if d[key] is None:
+            assert d[key + "_before"] is None, (m.name, key)
+            continue
+        v64, v32 = r[0][i], r[1][i]
+        before = d[key + "_before"]
+        if before is not None:
+            v64, v32 = v64 + before.to(F64), v32 + before
+        figs.append(gate(key + (" (accumulated)" if before is not None else ""), d[key], v64, v32))
+    return figs
+
+
 def wgrad_terms(m: NodeMeta, d: dict):
-    """(float64 contribution, fp32 contribution, b or None) of one wgrad launch."""
+    """(float64 contribution, fp32 contribution, b / b2 or None) of one wgrad launch."""
+    return wgrad_terms_s(m, d)[:3]
+
+
+def wgrad_terms_s(m: NodeMeta, d: dict):
+    """wgrad_terms and S (three-product launches, else None).  The launch reads dy and x only, so a frozen
+    step's (dy = dr, the result G = dL/d(s o w)) is checked as any other."""
     rows = m.n * m.oh * m.ow
     dys = d["dy"].reshape(rows, -1)
     v = []
     for dt in (F64, torch.float32):
         v.append(_wgrad(_nchw(d["x"], m.n, m.ih, m.iw, m.cin, dt), _nchw(dys, m.n, m.oh, m.ow, m.cout, dt), m))
-    b = None
+    b, S = None, None
     if d["x3"]:
-        b = B_REL * _wgrad(_nchw(d["x"], m.n, m.ih, m.iw, m.cin, F64).abs(),
-                           _nchw(dys, m.n, m.oh, m.ow, m.cout, F64).abs(), m)
-    return v[0], v[1], b
+        S = _wgrad(_nchw(d["x"], m.n, m.ih, m.iw, m.cin, F64).abs(), _nchw(dys, m.n, m.oh, m.ow, m.cout, F64).abs(), m)
+        b, S = split_term("wgrad", d, S, rows)
+    return v[0], v[1], b, S
 
 
 def check_wgrad(m: NodeMeta, d: dict) -> list:
-    v64, v32, b = wgrad_terms(m, d)
+    v64, v32, b, S = wgrad_terms_s(m, d)
     if d["before"] is not None:
         v64, v32 = v64 + d["before"].to(F64), v32 + d["before"]
-    return [gate("weight.grad", d["after"], v64, v32, b)]
+    return [gate("weight.grad", d["after"], v64, v32, b, S=S)]
 
 
 def check_dgrad(m: NodeMeta, d: dict) -> list:
     """One data-gradient launch: this launch's contribution added to the `before` snapshot of its
     destination.  A parity-class launch (cls = (a, b)) owns the pixels (a::2, b::2); every other
     pixel must keep its `before` bits, wherever `before` is defined: a destination the step
-    allocated uninitialised (fill == "empty") is defined on the classes already written."""
+    allocated uninitialised (fill == "empty") is defined on the classes already written.  In a frozen step
+    the launch reads the folded weight s o w (TrainRunner._pack_dgrad packs with st.fs), as the forward does."""
     rows = m.n * m.oh * m.ow
     dys = d["dy"].reshape(rows, -1)
-    c = [_nhwc(_dgrad(m.weight.to(dt), _nchw(dys, m.n, m.oh, m.ow, m.cout, dt), m)) for dt in (F64, torch.float32)]
-    b = None
+    c = [_nhwc(_dgrad(folded_weight(m, dt), _nchw(dys, m.n, m.oh, m.ow, m.cout, dt), m)) for dt in (F64, torch.float32)]
+    b, S = None, None
     if d["x3"]:
-        b = B_REL * _nhwc(_dgrad(m.weight.to(F64).abs(), _nchw(dys, m.n, m.oh, m.ow, m.cout, F64).abs(), m))
+        S = _nhwc(_dgrad(folded_weight(m, F64).abs(), _nchw(dys, m.n, m.oh, m.ow, m.cout, F64).abs(), m))
+        b, S = split_term("dgrad", d, S, d.get("k", m.ks * m.ks * m.cout))
     after = d["after"].reshape(m.n, m.ih, m.iw, -1)
     assert after.shape[3] == m.cin, (m.name, after.shape)
     before = d["before"].reshape(after.shape) if d["before"] is not None else None
@@ -373,7 +561,7 @@ def check_dgrad(m: NodeMeta, d: dict) -> list:
     if d["form"] != "class":
         if d["fill"] == "prev":
             c = [c[0] + before.to(F64), c[1] + before]
-        return [gate(f"d {m.src} ({d['form']})", after, c[0], c[1], b)]
+        return [gate(f"d {m.src} ({d['form']})", after, c[0], c[1], b, S=S)]
     a_, b_ = d["cls"]
     own = torch.zeros(m.ih, m.iw, dtype=torch.bool)
     own[a_::2, b_::2] = True
@@ -388,22 +576,48 @@ def check_dgrad(m: NodeMeta, d: dict) -> list:
     if d["fill"] != "empty":
         c = [c[0] + before.to(F64), c[1] + before]
     sel = lambda t: t[:, a_::2, b_::2]
-    figs.append(gate(f"d {m.src} class {a_}{b_}", sel(after), sel(c[0]), sel(c[1]), sel(b) if b is not None else None))
+    figs.append(gate(f"d {m.src} class {a_}{b_}", sel(after), sel(c[0]), sel(c[1]), sel(b) if b is not None else None,
+                     S=sel(S) if S is not None else None))
     keep = defined & ~own
     figs.append(exact(f"d {m.src} outside class {a_}{b_}", after[:, keep], before[:, keep]))
     return figs
 
 
 CHECKS = {"conv": check_conv, "bn_stats": check_bn_stats, "bn_act": check_bn_act, "seg_nhwc": check_seg_nhwc,
-          "bias_grad": check_bias_grad, "bn_bwd": check_bn_bwd, "wgrad": check_wgrad, "dgrad": check_dgrad}
+          "bias_grad": check_bias_grad, "bn_bwd": check_bn_bwd, "wgrad": check_wgrad, "dgrad": check_dgrad,
+          "frozen_prepare": check_frozen_prepare, "frozen_act_bwd": check_frozen_act_bwd,
+          "frozen_unfold": check_frozen_unfold}
 HEAD_CHECKS = {"head": check_head, "ce": check_ce, "head_bwd": check_head_bwd}
 
 
+_FIGS: dict = {}
+
+
 def check(cap: Capture, rec: Rec) -> list:
-    """The Figures of one record (every compared output); raises on a malformed record only."""
-    if rec.kind in HEAD_CHECKS:
-        return HEAD_CHECKS[rec.kind](rec.data)
-    return CHECKS[rec.kind](cap.meta[rec.name], rec.data)
+    """The Figures of one record (every compared output), computed once per captured record; raises on a
+    malformed record only."""
+    key = (id(cap), rec.index)
+    if key not in _FIGS:
+        _FIGS[key] = HEAD_CHECKS[rec.kind](rec.data) if rec.kind in HEAD_CHECKS else \
+            CHECKS[rec.kind](cap.meta[rec.name], rec.data)
+    return _FIGS[key]
+
+
+def three_product_ratios(cap: Capture) -> dict:
+    """{(kind, K >= 288?): (largest (|got - ref| - a - 2^-22 |ref|) / S, launch label, node, K)} over the
+    three-product launches of a capture: what the code under test measures against b2's constants, not
+    their source."""
+    out = {}
+    for rec in cap.recs:
+        if rec.kind not in ("conv", "dgrad", "wgrad") or products(rec.kind, rec.data) != 3:
+            continue
+        m = cap.meta[rec.name]
+        k = m.n * m.oh * m.ow if rec.kind == "wgrad" else rec.data["k"]
+        for f in check(cap, rec):
+            key = (rec.kind, k >= B2_MIN_K)
+            if f.ratio is not None and (key not in out or f.ratio > out[key][0]):
+                out[key] = (f.ratio, launch_label(rec), rec.name, k)
+    return out
 
 
 def failures(figs: list) -> list:
@@ -414,7 +628,8 @@ def launch_label(rec: Rec) -> str:
     d = rec.data
     if rec.kind == "wgrad":
         k, s, per, red = d["plan"]
-        return f"{k} x{s} per {per} + {red}"
+        two = " (two planes)" if products("wgrad", d) == 3 else ""
+        return f"{k}{two} x{s} per {per} + {red}"
     if "kernel" in d:
         return f"{d['kernel']} split-K {d['split_k']}"
     if rec.kind == "bn_stats":
@@ -456,6 +671,8 @@ def node_meta(model, shape) -> tuple:
         ps = {"weight": c.weight, "bias": c.bias, "gamma": nd.bn.weight if nd.bn is not None else None,
               "beta": nd.bn.bias if nd.bn is not None else None}
         meta[nd.name].keys = {k: ids[id(q)] for k, q in ps.items() if q is not None}
+        if nd.bn is not None:
+            meta[nd.name].rmean, meta[nd.name].rvar = t(nd.bn.running_mean), t(nd.bn.running_var)
         order.append(nd.name)
     return meta, order
 
@@ -478,12 +695,23 @@ def capture(cfg: str) -> Capture:
     from drnmi.drnseg import DRNSeg
     from drnmi.train import CrossEntropyLoss, TrainRunner
     from drnmi.weights import synth_state_dict
-    arch, precision, shape, passes = CONFIGS[cfg]
+    arch, precision, shape, passes, opts = CONFIGS[cfg]
     m = DRNSeg(arch, 19, pretrained=False)
+    # synth_state_dict draws running_mean in +-0.1 and running_var in 0.5 .. 1.5 (weights.synth_tensor): a
+    # frozen step's s differs from gamma and its t from beta, so a check can tell them apart
     m.load_state_dict(synth_state_dict(m, SEED))
     m.set_precision(precision)
     m = m.to("cuda").train()
+    if opts.get("frozen"):
+        m.freeze_bn()
     meta, order = node_meta(m, shape)
+    for nd in m._graph.nodes:
+        meta[nd.name].frozen = bool(opts.get("frozen"))
+        if nd.name in opts.get("no_weight_grad", ()):
+            nd.conv.weight.requires_grad_(False)
+    assert set(opts.get("no_weight_grad", ())) <= set(order), order
+    buffers = lambda: {k: b.detach().cpu().clone() for k, b in m.named_buffers()}
+    stats0 = buffers()
     x, t = make_inputs(shape)
     recs: list = []
     step = [0]
@@ -514,7 +742,7 @@ def capture(cfg: str) -> Capture:
             r.data["written"] = list(done)
             done.append(tuple(r.data["cls"]))
     params = {k: p.grad.detach().cpu() for k, p in m.named_parameters() if p.grad is not None}
-    cap = Capture(cfg, recs, meta, order, params)
+    cap = Capture(cfg, recs, meta, order, params, (stats0, buffers()))
     _CACHE[cfg] = cap
     return cap
 
@@ -549,7 +777,8 @@ def wgrad_args(n, cin, cs, cout, dys, ks, stride, pad, dil, h, w):
 
 
 def conv_args(x3, algo, n, h, w, cin, ho, wo, cout, cout_pad, ks, stride, pad, dil, k, k_pad, y_strides, res=False,
-              y_sr=0, tile=-1):
+              y_sr=0, tile=-1, two=False, relu=0):
+    """two: DRNMI_F32X2 where TrainRunner._conv takes it (a split-bf16 implicit-GEMM launch of an fp32x2 step)."""
     from drnmi import _lib
     a = _lib.ConvArgs()
     a.x = a.wgt = a.shift = a.y = PTR
@@ -560,8 +789,10 @@ def conv_args(x3, algo, n, h, w, cin, ho, wo, cout, cout_pad, ks, stride, pad, d
     a.ho, a.wo, a.cout, a.cout_pad = ho, wo, cout, cout_pad
     a.ks, a.stride, a.pad, a.dil = ks, stride, pad, dil
     a.k, a.k_pad = k, k_pad
-    a.relu = 0
+    a.relu = relu
     a.dtype = _lib.DRNMI_F32X3 if x3 else _lib.DRNMI_F32
+    if x3 and two and algo == _lib.ALGO_IGEMM:
+        a.dtype = _lib.DRNMI_F32X2
     a.out_dtype = _lib.DRNMI_F32
     a.tile, a.algo = tile, algo
     return a
@@ -572,7 +803,7 @@ def conv_route(a, split=True, want_stats=False) -> tuple:
     from drnmi import _lib
     lib = _lib.load()
     sk = 1
-    x3 = a.dtype == _lib.DRNMI_F32X3
+    x3 = a.dtype in (_lib.DRNMI_F32X3, _lib.DRNMI_F32X2)
     if x3 and a.algo == _lib.ALGO_IGEMM and split:
         nb = lib.drnmi_conv_workspace_bytes(ctypes.byref(a))
         if nb > 0:
@@ -585,17 +816,20 @@ def conv_route(a, split=True, want_stats=False) -> tuple:
     return (name.decode() if name else None, sk)
 
 
-def step_routes(arch: str, precision: str, n: int, h: int, w: int) -> list:
+def step_routes(arch: str, precision: str, n: int, h: int, w: int, freeze_bn: bool = False) -> list:
     """Every conv, wgrad and dgrad launch of one fine-tune step at [n, 3, h, w], with the route the
     library's host-only queries give it: [(what, node name, route)], what in fwd / wgrad / dgrad;
     route = (kernel, split-K) or the drnmi_conv_wgrad_plan tuple plus the pixel count.  It follows
     TrainRunner.forward / backward with the module switches at their defaults; the GPU audit checks
-    it against the launches the runner really made."""
+    it against the launches the runner really made.  fp32x2: the implicit-GEMM launches of fp32x as
+    DRNMI_F32X2.  freeze_bn: no launch is asked for BN statistics, and a BN node's launch carries the
+    residual and the ReLU unless it is a patch kernel with a residual."""
     from drnmi import _lib
     from drnmi.drnseg import DRNSeg
     from drnmi.engine import COUT_ALIGN, K_ALIGN, X6_PATCH_SHAPES, _conv_out, _pow2_at_least, _round_up
     g = DRNSeg(arch, 19, pretrained=False)._graph
-    x3 = precision == "fp32x"
+    x3 = precision in ("fp32x", "fp32x2")
+    two = precision == "fp32x2"
     cstride = {"input": 8}
     for v, c in g.channels.items():
         if v != "input":
@@ -614,9 +848,11 @@ def step_routes(arch: str, precision: str, n: int, h: int, w: int) -> list:
         patch = x3 and not nd.out_fp32_nchw and (cs, cout, ks, s, d) in X6_PATCH_SHAPES
         split = x3 and (patch or (cs >= 32 and k == k_pad))
         ys = (cout * oh * ow, 1, oh * ow) if nd.out_fp32_nchw else (oh * ow * cstride[nd.dst], cstride[nd.dst], 1)
+        fused = freeze_bn and not nd.out_fp32_nchw and not (patch and nd.res)
         a = conv_args(split, _lib.ALGO_PATCH if patch else _lib.ALGO_IGEMM, n, ih, iw, cs, oh, ow, cout,
-                      _round_up(cout, COUT_ALIGN), ks, s, p, d, k, k_pad, ys)
-        out.append(("fwd", nd.name, conv_route(a, want_stats=not nd.out_fp32_nchw)))
+                      _round_up(cout, COUT_ALIGN), ks, s, p, d, k, k_pad, ys, two=two, res=bool(fused and nd.res),
+                      relu=1 if fused and nd.relu else 0)
+        out.append(("fwd", nd.name, conv_route(a, want_stats=not nd.out_fp32_nchw and not freeze_bn)))
     have = set()
     for nd in reversed(g.nodes):
         c = nd.conv
@@ -659,14 +895,14 @@ def step_routes(arch: str, precision: str, n: int, h: int, w: int) -> list:
                     continue
                 a = conv_args(True, _lib.ALGO_IGEMM, n, oh, ow, dys, ho_c, wo_c, cin, rows_d, ksc, 1, 0, 1,
                               ksc * ksc * dys, ksc * ksc * dys, (ih * iw * cs_src, 2 * cs_src, 1), res=prev,
-                              y_sr=2 * iw * cs_src)
+                              y_sr=2 * iw * cs_src, two=two)
                 out.append(("dgrad", nd.name, conv_route(a, split=False)))
         else:
             hu, wu = (oh, ow) if s == 1 else (ih + 2 * p - d * (ks - 1), iw + 2 * p - d * (ks - 1))
             use_patch = dpatch and not prev
             a = conv_args(bool(wdx and (use_patch or not dpatch)), _lib.ALGO_PATCH if use_patch else _lib.ALGO_IGEMM, n,
                           hu, wu, dys, ih, iw, cin, rows_d, ks, 1, pad_d, d, kd, kd_pad, (ih * iw * cs_src, cs_src, 1),
-                          res=prev)
+                          res=prev, two=two)
             out.append(("dgrad", nd.name, conv_route(a)))
         have.add(nd.src)
     return out
@@ -689,7 +925,8 @@ def recorded_routes(cap: Capture, step: int = 0) -> list:
 
 
 def route_classes(routes: list) -> tuple:
-    """(wgrad classes, conv_x6 classes) of a list of routes."""
+    """(wgrad classes, conv_x6 classes, conv_x3 classes) of a list of routes."""
     wg = {wgrad_class(r[:4], r[4]) for what, _, r in routes if what == "wgrad"}
     cx = {r for what, _, r in routes if what != "wgrad" and r[0] and r[0].startswith("conv_x6_kernel")}
-    return wg, cx
+    c3 = {r for what, _, r in routes if what != "wgrad" and r[0] and r[0].startswith("conv_x3_kernel")}
+    return wg, cx, c3

@@ -512,7 +512,7 @@ class TrainRunner:
         _lib.check(lib.drnmi_conv2d_bn_act(ctypes.byref(a), ctypes.c_void_p(stream)), what)
         if self.record is not None:
             kn = lib.drnmi_conv_kernel_name(ctypes.byref(a))
-            self._last_conv = {"kernel": kn.decode() if kn else None, "x3": wx is not None,
+            self._last_conv = {"kernel": kn.decode() if kn else None, "x3": wx is not None, "k": k,
                                "split_k": max(1, nb // (4 * n * ho * wo * cout)) if nb > 0 else 1}
         return max(rows, 0)
 
@@ -584,7 +584,7 @@ class TrainRunner:
                                                     1 if nd.relu else 0, rows, cs, _vp(z), ctypes.c_void_p(stream)),
                                f"frozen bn_act {nd.name}")
                     if self.record is not None:
-                        self._rec("bn_act", nd.name, y=y, mean=zeros, invstd=ones, res=res, z=z)
+                        self._rec("bn_act", nd.name, y=y, mean=zeros, invstd=ones, res=res, z=z, beta=st.ft)
                     del y
                 vals[nd.dst] = z
                 per_node.append(None)
@@ -825,7 +825,7 @@ class TrainRunner:
                     after = self._snap(gbuf[:c.weight.numel() * 4].view(torch.float32).view_as(c.weight)) if fz \
                         else self._snap(c.weight.grad)
                     self._rec("wgrad", nd.name, dy=dy_rec, x=rd[nd.src], before=before, after=after, x3=x3,
-                              plan=_lib.wgrad_plan(wa, x3))
+                              two=self.model.precision == "fp32x2", plan=_lib.wgrad_plan(wa, x3))
                 if fz:
                     gw = nd.bn.weight
                     w_acc = 1 if (c.weight.requires_grad and acc[id(c.weight)]) else 0
@@ -843,6 +843,7 @@ class TrainRunner:
                     if self.record is not None:
                         self._rec("frozen_unfold", nd.name, g=after, w=self._snap(self._weight(nd, st)),
                                   s=self._snap(st.fs), rstd=self._snap(st.frs),
+                                  dbeta_sum=self._snap(self._fz_dbsum[:cout]),
                                   dw=self._snap(c.weight.grad) if c.weight.requires_grad else None,
                                   dgamma=self._snap(gw.grad) if fz_gamma else None, **uf0)
                 if c.weight.requires_grad:
