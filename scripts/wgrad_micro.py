@@ -1,7 +1,7 @@
 """Diagnostic: the weight-gradient kernels on fine-tune shapes of the benchmark (2 crops of 1024 x 768),
 timed with HIP events; run under rocprofv3 --pmc for counters.
 
-    python scripts/wgrad_micro.py [--precision fp32|fp32x|both] [--repeats N]
+    python scripts/wgrad_micro.py [--precision fp32|fp32x|fp32x2|both] [--repeats N]
 
 The 1/8-resolution D-54 shapes take the 128-tile / pre kernel in fp32x; the two 1/4-resolution
 64-channel shapes take the 64-tile kernels (64 -> 128 in fp32x: the 128-tile).  DRNMI_LIB selects
@@ -26,14 +26,14 @@ SHAPES = [  # name, cin, cout, ks, dil, h, w
     ("layer4 conv1 64->128 3x3", 64, 128, 3, 1, 256, 192),
 ]
 ap = argparse.ArgumentParser()
-ap.add_argument("--precision", choices=["fp32", "fp32x", "both"], default="fp32x")
+ap.add_argument("--precision", choices=["fp32", "fp32x", "fp32x2", "both"], default="fp32x")
 ap.add_argument("--repeats", type=int, default=5)
 opt = ap.parse_args()
 lib = _lib.load()
 n = 2
 for precision in (["fp32", "fp32x"] if opt.precision == "both" else [opt.precision]):
-    x6 = precision == "fp32x"
-    fn = lib.drnmi_conv_wgrad_f32x3 if x6 else lib.drnmi_conv_wgrad_f32
+    x6 = precision != "fp32"       # fp32x2: the pre route on two planes, every other route as fp32x
+    fn = {"fp32": lib.drnmi_conv_wgrad_f32, "fp32x": lib.drnmi_conv_wgrad_f32x3, "fp32x2": lib.drnmi_conv_wgrad_f32x2}[precision]
     for name, cin, cout, ks, dil, h, w in SHAPES:
         pad = dil * (ks // 2)
         x = torch.randn(n * h * w, cin, device="cuda")
@@ -60,5 +60,5 @@ for precision in (["fp32", "fp32x"] if opt.precision == "both" else [opt.precisi
         torch.cuda.synchronize()
         us = statistics.median(ev[i].elapsed_time(ev[i + 1]) for i in range(opt.repeats)) * 1e3
         fl = 2.0 * n * h * w * cout * cin * ks * ks
-        print(f"{precision:5s} {name:32s} {us:8.1f} us/call at the median of {opt.repeats} (incl. reduce) "
+        print(f"{precision:6s} {name:32s} {us:8.1f} us/call at the median of {opt.repeats} (incl. reduce) "
               f"{fl / us / 1e6:6.1f} TF  ws {nb / 2**20:.0f} MiB  {kernel}", flush=True)

@@ -32,73 +32,24 @@
 // Every variant runs each accumulator through the same sequence (sub-steps in K order, mfma_x3's
 // order inside one), so all variants are bit-identical, and a split-K partition starts on a
 // sub-step boundary whatever SUB is.
-#include "common.h"
-#include "kernels.h"
+#include "conv_xsplit.h"
 
 namespace drnmi {
 namespace {
 
-typedef __attribute__((address_space(3))) void lds_void_t;
-typedef __attribute__((address_space(1))) const void g_void_t;
-
-__device__ uint4 g_x3_zero[64];   // zero-initialised: the source of padded taps / rows
-
-constexpr int kBK = 32;     // input channels per sub-step
-
-__device__ __forceinline__ void glds16(const void* src, char* lds_wave_base) {
-  __builtin_amdgcn_global_load_lds((g_void_t*)src, (lds_void_t*)lds_wave_base, 16, 0, 0);
-}
-
-__device__ __forceinline__ int xcd_remap(int bid, int nwg) {
-  const int q = nwg / 8, r = nwg % 8;
-  const int xcd = bid % 8;
-  return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + bid / 8;
-}
-
-// swz64 (bf16 A rows, 64 B) is common.h's
-__device__ __forceinline__ int swz128(int row, int chunk) { return chunk ^ ((row >> 1) & 7); }   // fp32 B rows
-
-template <int CTRL>
-__device__ __forceinline__ double dpp_f64(double x) {
-  const uint64_t u = __builtin_bit_cast(uint64_t, x);
-  const int lo = __builtin_amdgcn_mov_dpp(static_cast<int>(u & 0xffffffffu), CTRL, 0xF, 0xF, false);
-  const int hi = __builtin_amdgcn_mov_dpp(static_cast<int>(u >> 32), CTRL, 0xF, 0xF, false);
-  return __builtin_bit_cast(double, (static_cast<uint64_t>(static_cast<uint32_t>(hi)) << 32) | static_cast<uint32_t>(lo));
-}
-// sum over the 16 lanes of a DPP row, the same in every lane, in conv_x6's fixed order
-__device__ __forceinline__ double row16_sum(double x) {
-  x += dpp_f64<0xB1>(x);    // quad_perm [1, 0, 3, 2]
-  x += dpp_f64<0x4E>(x);    // quad_perm [2, 3, 0, 1]
-  x += dpp_f64<0x141>(x);   // row_half_mirror
-  x += dpp_f64<0x140>(x);   // row_mirror
-  return x;
-}
-
 // Tile = BCO = WCO x WC output channels x BPX = 64 x PS pixels; one wave per (channel column,
 // 64-pixel slice); SUB sub-steps of 32 channels per ring slot.
 template <int WCO, int WC, int PS, int SUB>
-struct X3Cfg {
-  static constexpr int BCO = WCO * WC;
-  static constexpr int BPX = 64 * PS;
-  static constexpr int FM = WCO / 16;
-  static constexpr int FN = 4;
-  static constexpr int NW = PS * WC;
-  static constexpr int THREADS = 64 * NW;
+struct X3Cfg : XCfg<2, WCO, WC, PS> {
+  using B = XCfg<2, WCO, WC, PS>;
   static constexpr int OCC = SUB == 1 ? 2 : 1;      // workgroups per CU the LDS ring is sized for
-  static constexpr int A_PLANE = BCO * 64;          // one bf16 plane: BCO rows x 32 K x 2 B
-  static constexpr int A_BYTES = 2 * A_PLANE;
-  static constexpr int B_BYTES = BPX * 128;         // BPX pixel rows x 32 ch x 4 B
-  static constexpr int SUBST = A_BYTES + B_BYTES;   // one sub-step's operands
+  static constexpr int SUBST = B::A_BYTES + B::B_BYTES;   // one sub-step's operands
   static constexpr int STAGE = SUB * SUBST;
-  static constexpr int A_PW = A_BYTES / 1024 / NW;  // 1-KB DMA pieces per wave per sub-step
-  static constexpr int B_PW = B_BYTES / 1024 / NW;
-  static constexpr int GLDS = A_PW + B_PW;
   static constexpr int NST = (SUB == 1 && 3 * STAGE * OCC <= 160 * 1024) ? 3 : 2;
   static constexpr int LDS = NST * STAGE;
-  static_assert(A_PW * NW * 1024 == A_BYTES && B_PW * NW * 1024 == B_BYTES, "DMA split");
   static_assert(LDS * OCC <= 160 * 1024, "LDS");
   static_assert(SUB == 1 || NST == 2, "a half-full last pair is waited for with vmcnt(0)");
-  static_assert(GLDS * (NST - 1) < 64, "vmcnt");
+  static_assert(B::GLDS * (NST - 1) < 64, "vmcnt");
 };
 
 template <int KS, int WCO, int WC, int PS, int SUB>
@@ -133,10 +84,10 @@ conv_x3_kernel(const drnmi_conv_args p) {
   const int s0 = static_cast<int>(static_cast<int64_t>(ns_all) * blockIdx.y / gridDim.y);
   const int ns = static_cast<int>(static_cast<int64_t>(ns_all) * (blockIdx.y + 1) / gridDim.y) - s0;
   const int nk = (ns + SUB - 1) / SUB;                 // ring steps
-  const char* zero_src = reinterpret_cast<const char*>(g_x3_zero) + lane * 16;
+  const char* zero_src = reinterpret_cast<const char*>(g_xsplit_zero) + lane * 16;
 
   // --- A pieces: 16 rows of 64 B each; linear row R = plane * BCO + r
-  // element offsets < 2^31: 2 planes x cout_pad x k_pad bf16 (x3_route checks)
+  // element offsets < 2^31: 2 planes x cout_pad x k_pad bf16 (conv_route.cpp x6_route checks)
   int32_t a_off[C::A_PW];
 #pragma unroll
   for (int i = 0; i < C::A_PW; ++i) {
@@ -407,17 +358,6 @@ conv_x3_kernel(const drnmi_conv_args p) {
   }
 }
 
-template <int KS, int WCO, int WC, int PS, int SUB>
-hipError_t launch_x3(const drnmi_conv_args& p, int splits, hipStream_t s) {
-  using C = X3Cfg<WCO, WC, PS, SUB>;
-  const int64_t M = static_cast<int64_t>(p.n) * p.ho * p.wo;
-  const int64_t blocks = ((M + C::BPX - 1) / C::BPX) * ((p.cout + C::BCO - 1) / C::BCO);
-  const hipError_t e = launch_lds<&conv_x3_kernel<KS, WCO, WC, PS, SUB>>(dim3(static_cast<unsigned>(blocks), splits),
-                                                                         dim3(C::THREADS), C::LDS, s, p);
-  if (e != hipSuccess || splits == 1) return e;
-  return x6_splitk_finish(p, splits, s);
-}
-
 }  // namespace
 
 // variants: 0 <K, 64, 2, 2, 2> (128 channels x 128 pixels, 4 waves of 64 x 64, 64-channel ring steps,
@@ -427,17 +367,13 @@ hipError_t launch_x3(const drnmi_conv_args& p, int splits, hipStream_t s) {
 // per 32-channel sub-step of one workgroup tile and round of resident workgroups, from the 3x3 512 -> 512
 // launch at 2 x 128 x 96 in an earlier run of scripts/x3_micro.py than the committed one: 445 us / (3 rounds x
 // 144), 369 / (2 x 144), 494 / (3 x 144); profiles/fp32x2/micro_conv.log has 443 / 349 / 475 us, within 6 %.
-static_assert(kBK == kX6BK, "the K step conv_route.cpp plans with");
-#define X3_ROW(...) \
-  ConvKernel { "conv_x3_kernel<" #__VA_ARGS__ ">", &launch_x3<__VA_ARGS__> }
-#define X3_VARIANT(WCO, WC, PS, SUB, STEP)                                                               \
-  {X3Cfg<WCO, WC, PS, SUB>::BCO, X3Cfg<WCO, WC, PS, SUB>::BPX, X3Cfg<WCO, WC, PS, SUB>::OCC, STEP,       \
-   {X3_ROW(1, WCO, WC, PS, SUB), X3_ROW(2, WCO, WC, PS, SUB), X3_ROW(3, WCO, WC, PS, SUB)}}
+#define X3_VARIANT(WCO, WC, PS, SUB, STEP) X_VARIANT(conv_x3_kernel, X3Cfg, STEP, WCO, WC, PS, SUB)
 const X6Variant& x3_variant(int v) {
   static const X6Variant k[kNumX3] = {X3_VARIANT(64, 2, 2, 2, 1.0e-6), X3_VARIANT(64, 2, 2, 1, 1.3e-6),
                                       X3_VARIANT(32, 2, 2, 1, 1.15e-6)};
   return k[v];
 }
+#undef X3_VARIANT
 
 // conv_x6's launch contract under the other dtype code
 bool x3_conv_supported(const drnmi_conv_args& p) {

@@ -26,52 +26,10 @@
 //     XCD-major.
 //   * Epilogue in fp32: v = acc * scale + shift (+ residual), ReLU, fp32 NHWC (or the strided
 //     fp32 NCHW seg logits).
-#include "common.h"
-#include "kernels.h"
+#include "conv_xsplit.h"
 
 namespace drnmi {
 namespace {
-
-typedef __attribute__((address_space(3))) void lds_void_t;
-typedef __attribute__((address_space(1))) const void g_void_t;
-
-__device__ uint4 g_x6_zero[64];   // zero-initialised: the source of padded taps / rows
-
-
-constexpr int kBK = 32;     // input channels per K step
-
-__device__ __forceinline__ void glds16(const void* src, char* lds_wave_base) {
-  __builtin_amdgcn_global_load_lds((g_void_t*)src, (lds_void_t*)lds_wave_base, 16, 0, 0);
-}
-
-__device__ __forceinline__ int xcd_remap(int bid, int nwg) {
-  const int q = nwg / 8, r = nwg % 8;
-  const int xcd = bid % 8;
-  return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + bid / 8;
-}
-
-// swz64 (bf16 A rows, 64 B) is common.h's
-__device__ __forceinline__ int swz128(int row, int chunk) { return chunk ^ ((row >> 1) & 7); }   // fp32 B rows
-
-
-// x from the lane DPP control CTRL selects, as two 32-bit DPP moves
-template <int CTRL>
-__device__ __forceinline__ double dpp_f64(double x) {
-  const uint64_t u = __builtin_bit_cast(uint64_t, x);
-  const int lo = __builtin_amdgcn_mov_dpp(static_cast<int>(u & 0xffffffffu), CTRL, 0xF, 0xF, false);
-  const int hi = __builtin_amdgcn_mov_dpp(static_cast<int>(u >> 32), CTRL, 0xF, 0xF, false);
-  return __builtin_bit_cast(double, (static_cast<uint64_t>(static_cast<uint32_t>(hi)) << 32) | static_cast<uint32_t>(lo));
-}
-// sum over the 16 lanes of a DPP row, the same in every lane: quad_perm xor 1, xor 2, then
-// row_half_mirror (quads 0 <-> 1) and row_mirror (halves) -- a fixed order, ALU only (the
-// ds_bpermute form of __shfl_xor cost the short-K launches ~10 % in their epilogue)
-__device__ __forceinline__ double row16_sum(double x) {
-  x += dpp_f64<0xB1>(x);    // quad_perm [1, 0, 3, 2]
-  x += dpp_f64<0x4E>(x);    // quad_perm [2, 3, 0, 1]
-  x += dpp_f64<0x141>(x);   // row_half_mirror
-  x += dpp_f64<0x140>(x);   // row_mirror
-  return x;
-}
 
 // ds_rd (common.h) reads at LDS byte address base + OFF: smem is the kernel's only LDS object, byte 0
 
@@ -80,24 +38,12 @@ __device__ __forceinline__ double row16_sum(double x) {
 // PS = 2: a 128 x 128 tile of four waves in <= 80 KB, two workgroups per CU (their barriers
 // interleave, and the short-K 1/8-resolution launches get twice the tiles).
 template <int WCO, int WC, int PS>
-struct X6Cfg {
-  static constexpr int BCO = WCO * WC;
-  static constexpr int BPX = 64 * PS;
-  static constexpr int FM = WCO / 16;
-  static constexpr int FN = 4;
-  static constexpr int NW = PS * WC;
-  static constexpr int THREADS = 64 * NW;
+struct X6Cfg : XCfg<3, WCO, WC, PS> {
+  using B = XCfg<3, WCO, WC, PS>;
   static constexpr int OCC = PS == 2 ? 2 : 1;       // workgroups per CU the LDS ring is sized for
-  static constexpr int A_PLANE = BCO * 64;          // one bf16 plane: BCO rows x 32 K x 2 B
-  static constexpr int A_BYTES = 3 * A_PLANE;
-  static constexpr int B_BYTES = BPX * 128;         // BPX pixel rows x 32 ch x 4 B
-  static constexpr int STAGE = A_BYTES + B_BYTES;
-  static constexpr int A_PW = A_BYTES / 1024 / NW;  // 1-KB DMA pieces per wave per step
-  static constexpr int B_PW = B_BYTES / 1024 / NW;
-  static constexpr int GLDS = A_PW + B_PW;
+  static constexpr int STAGE = B::A_BYTES + B::B_BYTES;
   static constexpr int NST = 3 * STAGE * OCC <= 160 * 1024 ? 3 : 2;
   static constexpr int LDS = NST * STAGE;
-  static_assert(A_PW * NW * 1024 == A_BYTES && B_PW * NW * 1024 == B_BYTES, "DMA split");
   static_assert(LDS * OCC <= 160 * 1024, "LDS");
 };
 
@@ -132,10 +78,10 @@ conv_x6_kernel(const drnmi_conv_args p) {
   const int nk_all = p.k_pad / kBK;
   const int kt0 = static_cast<int>(static_cast<int64_t>(nk_all) * blockIdx.y / gridDim.y);
   const int nk = static_cast<int>(static_cast<int64_t>(nk_all) * (blockIdx.y + 1) / gridDim.y) - kt0;
-  const char* zero_src = reinterpret_cast<const char*>(g_x6_zero) + lane * 16;
+  const char* zero_src = reinterpret_cast<const char*>(g_xsplit_zero) + lane * 16;
 
   // --- A pieces: 16 rows of 64 B each; linear row R = plane * BCO + r
-  // element offsets < 2^31: 3 planes x cout_pad x k_pad bf16 (x6_conv_dispatch checks)
+  // element offsets < 2^31: 3 planes x cout_pad x k_pad bf16 (conv_route.cpp x6_route checks)
   int32_t a_off[C::A_PW];
 #pragma unroll
   for (int i = 0; i < C::A_PW; ++i) {
@@ -566,17 +512,6 @@ __global__ void __launch_bounds__(256) x6_splitk_epilogue_kernel(const drnmi_con
   }
 }
 
-template <int KS, int WCO, int WC, int PS>
-hipError_t launch_x6(const drnmi_conv_args& p, int splits, hipStream_t s) {
-  using C = X6Cfg<WCO, WC, PS>;
-  const int64_t M = static_cast<int64_t>(p.n) * p.ho * p.wo;
-  const int64_t blocks = ((M + C::BPX - 1) / C::BPX) * ((p.cout + C::BCO - 1) / C::BCO);
-  const hipError_t e = launch_lds<&conv_x6_kernel<KS, WCO, WC, PS>>(dim3(static_cast<unsigned>(blocks), splits),
-                                                                    dim3(C::THREADS), C::LDS, s, p);
-  if (e != hipSuccess || splits == 1) return e;
-  return x6_splitk_finish(p, splits, s);
-}
-
 }  // namespace
 
 // the second launch of a split-K plan (conv_x6 and conv_x3 write the same [split][m][cout] partials)
@@ -596,17 +531,13 @@ hipError_t x6_splitk_finish(const drnmi_conv_args& p, int splits, hipStream_t s)
 // the fine-tune shapes (profiles/r8_finetune/x6_micro_variants.txt): the 256 x 256 tile ~4.3 us,
 // the 8-wave 128 x 256 ~3.0 us, the two-per-CU 128 x 128 ~2.7 us (its 2.1-3.0 us spread tracks
 // how the two resident workgroups overlap; past two rounds the model under-charges it)
-static_assert(kBK == kX6BK, "the K step conv_route.cpp plans with");
-#define X6_ROW(...) \
-  ConvKernel { "conv_x6_kernel<" #__VA_ARGS__ ">", &launch_x6<__VA_ARGS__> }
-#define X6_VARIANT(WCO, WC, PS, STEP)                                                            \
-  {X6Cfg<WCO, WC, PS>::BCO, X6Cfg<WCO, WC, PS>::BPX, X6Cfg<WCO, WC, PS>::OCC, STEP,             \
-   {X6_ROW(1, WCO, WC, PS), X6_ROW(2, WCO, WC, PS), X6_ROW(3, WCO, WC, PS)}}
+#define X6_VARIANT(WCO, WC, PS, STEP) X_VARIANT(conv_x6_kernel, X6Cfg, STEP, WCO, WC, PS)
 const X6Variant& x6_variant(int v) {
   static const X6Variant k[kNumX6] = {X6_VARIANT(128, 2, 4, 4.3e-6), X6_VARIANT(128, 1, 4, 3.6e-6), X6_VARIANT(64, 1, 4, 2.2e-6),
                                       X6_VARIANT(64, 2, 4, 3.0e-6),  X6_VARIANT(64, 2, 2, 2.7e-6),  X6_VARIANT(32, 2, 2, 2.3e-6)};
   return k[v];
 }
+#undef X6_VARIANT
 
 bool x6_conv_supported(const drnmi_conv_args& p) {
   return p.dtype == DRNMI_F32X3 && p.out_dtype == DRNMI_F32 && p.cin >= kBK && (p.cin & (p.cin - 1)) == 0 &&

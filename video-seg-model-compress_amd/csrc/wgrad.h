@@ -62,7 +62,7 @@ __device__ __forceinline__ void pre_wr(const uint32_t (&w)[4], float v) {
 
 struct WgradPreP {
   WgradP p;
-  const bf16_t* dyt;   // [3][Cp][Mp]
+  const bf16_t* dyt;   // [planes][Cp][Mp]: 3 (drnmi_conv_wgrad_f32x3) or 2 (drnmi_conv_wgrad_f32x2)
   int64_t Mp;
   int Cp;
 };
