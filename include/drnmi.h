@@ -35,7 +35,7 @@ int32_t drnmi_abi_version(void);
 int64_t drnmi_conv_args_size(void);
 
 enum drnmi_dtype { DRNMI_F32 = 0, DRNMI_BF16 = 1, DRNMI_U8 = 2, DRNMI_I64 = 3, DRNMI_I8 = 4, DRNMI_F32X3 = 5,
-                   DRNMI_F8 = 6, DRNMI_BF16_SP24 = 7, DRNMI_I8_SP24 = 8, DRNMI_F32X2 = 9 };
+                   DRNMI_F8 = 6, DRNMI_BF16_SP24 = 7, DRNMI_I8_SP24 = 8, DRNMI_F32X2 = 9, DRNMI_BF16_PSP = 10 };
 /* DRNMI_F32X3 (conv dtype only, the "fp32x" precision mode): x, res and y are fp32 NHWC as in
  * DRNMI_F32, wgt is three bf16 planes [3][cout_pad][k_pad] with w = w1 + w2 + w3 (an exact split
  * of the fp32 weight), and the conv runs fp32-accurate arithmetic on the bf16 MFMA pipe: each
@@ -130,6 +130,25 @@ enum drnmi_sp24_tile { DRNMI_SP24_GATHER = 0, DRNMI_SP24_STRIP = 1 };
  *   B    32 int8 per lane: column fr, bytes 0-15 = k 16 fq .. 16 fq + 15, bytes 16-31 = k 64 + 16 fq ..
  *        + 15 (two v_mfma_i32_16x16x64_i8 B fragments side by side);
  *   D    4 int32 per lane: rows 4 fq .. 4 fq + 3 of column fr, as the dense 16x16 MFMAs. */
+
+/* DRNMI_BF16_PSP (conv dtype only; inference, opt-in: DRNSeg.set_srmb_sparse): a bf16 launch whose weights
+ * carry an SRMBRepMasker mask, run on their live input channels only (csrc/conv_psp.hip, "period-sparse").
+ * Added under ABI version 7 like DRNMI_I8_SP24: a new enum value and two new symbols, drnmi_conv_args
+ * unchanged.  The structure, which drnmi_psp_pack reads off the weights' zeros: output rows fall into
+ * classes of one zero support each, every class a multiple of 16 rows; for a (class, tap) the live input
+ * channels repeat with period P, d per period, one per residue mod d (live channel v of period q is
+ * q P + v + d s_v).  x, res and y are as in a DRNMI_BF16 launch; wgt is the blob drnmi_psp_pack wrote
+ * (the values shrink by d / P); scale must be NULL (folded into the weights before packing).  One
+ * v_mfma_f32_16x16x32_bf16 covers 32 P / d source channels: P / d = 2, 4 or 8 times fewer MFMAs.
+ *   tile     REQUIRED: the (P, d) the blob was packed with (enum drnmi_psp_tile, what drnmi_psp_pack
+ *            returned); DRNMI_TILE_AUTO or another value: no such kernel (DRNMI_ENOTSUP).
+ *   shapes   cin a power of two and a multiple of 32 P / d, ks 1 or 3, stride 1, any pad / dilation, any
+ *            M, cout == cout_pad a multiple of 128, k_pad == k == ks*ks*cin (the dense sizes), out_dtype
+ *            DRNMI_BF16 or DRNMI_F32 at any strides, residual and ReLU.
+ *   refused  DRNMI_ENOTSUP: x2, unit_mask, a non-NULL scale, stride 2, drnmi_conv_stag_seg, DRNMI_ALGO_PATCH
+ *            (DRNMI_EINVAL); and whatever every launch is refused for.
+ * Sums are added in another order than on the dense tiles: outputs agree to fp32 rounding, not bit for bit. */
+enum drnmi_psp_tile { DRNMI_PSP_P32_D16 = 0, DRNMI_PSP_P64_D16 = 1, DRNMI_PSP_P64_D8 = 2, DRNMI_PSP_P32_D8 = 3 };
 
 enum drnmi_status {
   DRNMI_OK = 0,
@@ -441,6 +460,27 @@ int64_t drnmi_sp24_pack_i8_bytes(int32_t rows_pad, int32_t k_pad);
 int drnmi_sp24_pack_i8(const void* dense_i8, int32_t rows_pad, int32_t k_pad, void* out, int32_t* violations,
                        void* stream);
 int drnmi_sp24_mma_probe_i8(const void* a, const void* b, const uint32_t* idx, int32_t* d, void* stream);
+
+/* Packing for DRNMI_BF16_PSP (csrc/conv_psp.hip).  HOST function, no GPU: dense_bf16 are the packed bf16
+ * weights [rows][ks*ks*cin] (k = (kh*ks + kw)*cin + ci, BN scale folded) in HOST memory; rows % 128 == 0, cin a
+ * power of two >= 64, ks 1 or 3 (else DRNMI_EINVAL).  Everything is derived from the weights' zeros (+-0): for
+ * H = 8, 16, 32, 64 (smallest first) the supports of the rows with equal r mod H are OR-ed and residues of equal
+ * support merged into classes; the layer is eligible iff for one (P, d) of enum drnmi_psp_tile every class has a
+ * multiple of 16 rows, every (class, tap) support is P-periodic along cin with exactly one live channel per
+ * residue mod d, and cin % (32 P / d) == 0; of several (H, P, d) that fit, the smallest d / P, then the smallest H,
+ * is taken (a coarser H can fit with the union of several classes' supports).  Eligible: *variant = that enum value, *violations = 0 and, with
+ * out != NULL (host memory of at least drnmi_psp_pack_bytes(rows, cin, ks, *variant) bytes, given in out_bytes),
+ * the blob is written; a live position whose weight is 0 is stored as 0.  out == NULL only analyses.  Not
+ * eligible: *variant = -1, *violations = the failed (class, tap) / class-size / K-step checks of the nearest
+ * attempt (>= 1), nothing written, and the layer stays dense.  Returns DRNMI_OK in both cases.
+ * The blob: int32[16] {0x31505350, rows, cin, ks, P, d, P / d, kc = ks*ks*cin*d/P, 0...}; int32 perm[rows] (row of
+ * the blob -> output channel; every 16 rows are one class); int32 order[rows] (for every 128 rows, their
+ * indices 0..127 sorted by output channel); uint8 s[rows / 16][ks*ks][d] padded to 16 bytes; bf16
+ * values[rows][kc] with values[r][tap*cin*d/P + q*d + v] = w[perm[r]][tap][q*P + v + d*s[r / 16][tap][v]].
+ * drnmi_psp_pack_bytes: the blob's size, -1 for sizes or a variant the pack refuses. */
+int64_t drnmi_psp_pack_bytes(int32_t rows, int32_t cin, int32_t ks, int32_t variant);
+int drnmi_psp_pack(const void* dense_bf16, int32_t rows, int32_t cin, int32_t ks, void* out, int64_t out_bytes,
+                   int32_t* variant, int32_t* violations);
 
 /* W8A8 helpers (BASELINE config C5; csrc/quant.hip).  The reference has no quantisation code
  * (SURVEY.md C5 row): the scheme is ours.  Activations are per-tensor symmetric int8.

@@ -95,6 +95,11 @@ bool big_body_shape_ok(const drnmi_conv_args& p, int min_cin);
 const ConvKernel* sp24_kernel(int dtype, bool tile128, int ks);
 const ConvKernel* sp24_strip_kernel(int dtype);  // 3x3 stride 1, wo % 256 == 0, the 256 x 256 tile (strip_ok)
 
+// conv_psp.hip: the period-sparse tiles (dtype DRNMI_BF16_PSP: SRMB-masked weights on their live channels); rows
+// [tile id = enum drnmi_psp_tile][ks == 3]
+bool psp_conv_supported(const drnmi_conv_args& p);
+const ConvKernel* psp_kernel(int variant, int ks);
+
 // conv_halo.hip: halo-patch 3x3 stride-1 conv, cin / cout 64 or 128
 bool halo_conv_supported(const drnmi_conv_args& p);
 const ConvKernel* halo_kernel(int cin, int cout);

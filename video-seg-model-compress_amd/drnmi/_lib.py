@@ -14,7 +14,9 @@ DRNMI_F32, DRNMI_BF16, DRNMI_U8, DRNMI_I64, DRNMI_I8, DRNMI_F32X3, DRNMI_F8 = 0,
 DRNMI_BF16_SP24 = 7
 DRNMI_I8_SP24 = 8
 DRNMI_F32X2 = 9           # conv dtype: two bf16 weight planes, three products (csrc/conv_x3.hip)
+DRNMI_BF16_PSP = 10       # conv dtype: SRMB-masked weights on their live channels (csrc/conv_psp.hip)
 SP24_GATHER, SP24_STRIP = 0, 1          # include/drnmi.h enum drnmi_sp24_tile
+PSP_VARIANTS = ((32, 16), (64, 16), (64, 8), (32, 8))   # enum drnmi_psp_tile: (P, d) by value
 ALGO_IGEMM, ALGO_PATCH = 0, 1
 # include/drnmi.h enum drnmi_tile: the ids tests and micro-benchmarks force
 TILE_AUTO, TILE_DMA128, TILE_PP256, TILE_HALO, TILE_STRIP, TILE_STAG = -1, 4, 16, 17, 18, 19
@@ -165,6 +167,8 @@ SIGNATURES = {
     "drnmi_sp24_pack_i8_bytes": (ctypes.c_int64, [_I32, _I32]),
     "drnmi_sp24_pack_i8": (ctypes.c_int, [_VP, _I32, _I32, _VP, _VP, _VP]),
     "drnmi_sp24_mma_probe_i8": (ctypes.c_int, [_VP, _VP, _VP, _VP, _VP]),
+    "drnmi_psp_pack_bytes": (ctypes.c_int64, [_I32, _I32, _I32, _I32]),
+    "drnmi_psp_pack": (ctypes.c_int, [_VP, _I32, _I32, _I32, _VP, ctypes.c_int64, _VP, _VP]),
     "drnmi_quantize_i8": (ctypes.c_int, [_VP, _I32, _VP, _I64, _F32, _VP]),
     "drnmi_quantize_f8": (ctypes.c_int, [_VP, _I32, _I64, _F32, _VP, _VP]),
     "drnmi_absmax": (ctypes.c_int, [_VP, _I32, _I64, _VP, _VP]),

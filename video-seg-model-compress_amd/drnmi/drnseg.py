@@ -91,6 +91,7 @@ class DRNSeg(nn.Module):
         self.block_sparse = False    # opt-in: measured slower than dense below ~60 % zero units
         self.sparse24 = False        # opt-in: 2:4-pruned bf16 layers on the sparse MFMA (set_sparse24)
         self.low_latency = False     # opt-in: small grids on the split-K bf16 conv (set_low_latency)
+        self.srmb_sparse = False     # opt-in: SRMB-masked bf16 layers on their live channels (set_srmb_sparse)
         self._graph = lower_drnseg(self.layer, self.seg)
         self._act_scales = None      # int8: per-value activation scales (calibrate_int8)
         self._int8_hists = None      # value -> |x| histogram of the last histogram calibration
@@ -493,6 +494,32 @@ class DRNSeg(nn.Module):
         device = torch.device(device or next(self.parameters()).device)
         return self._packed_net(device).sparse24_layers()
 
+    def set_srmb_sparse(self, enabled: bool) -> "DRNSeg":
+        """bf16 inference: run every stride-1 3x3 / 1x1 conv whose weights carry an SRMBRepMasker mask of the
+        regular kind (is_repetitive, osp 0, collapse_tensor: whole 16-row classes of one support, supports
+        periodic along the input channels with d of P channels live; read off the weights' zeros by
+        drnmi_psp_pack, the pruner's JSON is not consulted) on the period-sparse kernel (include/drnmi.h
+        DRNMI_BF16_PSP, csrc/conv_psp.hip): P / d = 1 / (1 - isp) times fewer MFMAs and weight bytes.  In
+        D-22 masked by the shipped SRMB configurations these are the 512-channel launches (layer6, layer7,
+        layer8).  Layers with a folded downsample, the fused blocks, block-sparse- and 2:4-routed layers and
+        the conv whose epilogue takes the seg classifier stay as they are (PackedNet._pack_psp); layers
+        whose zeros do not have the structure stay dense.  Sums are added in another order: outputs agree
+        with the dense bf16 launch to fp32 rounding, not bit for bit.  Other precisions are untouched.
+        Opt-in, off by default; takes effect at the next pack."""
+        self.srmb_sparse = bool(enabled)
+        for pk in self._packed.values():
+            pk.srmb_sparse = self.srmb_sparse
+        self._pack_key = None
+        return self
+
+    def srmb_sparse_layers(self, device=None) -> list:
+        """Names of the conv nodes the bf16 pack launches on the period-sparse kernel (packs first if
+        needed; [] with the switch off or outside bf16)."""
+        if not getattr(self, "srmb_sparse", False) or self.precision != "bf16":
+            return []
+        device = torch.device(device or next(self.parameters()).device)
+        return self._packed_net(device).srmb_sparse_layers()
+
     def set_low_latency(self, enabled: bool) -> "DRNSeg":
         """bf16 inference on one small frame per call (the seg_video loop: model(img) per 300 x 300
         frame): conv launches whose default tiles would leave most CUs idle run on the split-K kernel
@@ -590,7 +617,8 @@ class DRNSeg(nn.Module):
         pk = self._packed.get(self.precision)
         if pk is None:
             pk = PackedNet(self._graph, self.precision, device, block_sparse=self.block_sparse,
-                           act_scales=self._act_scales, sparse24=getattr(self, "sparse24", False))
+                           act_scales=self._act_scales, sparse24=getattr(self, "sparse24", False),
+                           srmb_sparse=getattr(self, "srmb_sparse", False))
             self._packed[self.precision] = pk
         return pk
 

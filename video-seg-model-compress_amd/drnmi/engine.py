@@ -134,6 +134,10 @@ class ConvNode:
     # 2:4 weight sparsity (bf16, PackedNet.sparse24): the drnmi_sp24_pack blob of wpk; the launch is
     # DRNMI_BF16_SP24 with wgt = wsp (wpk stays: the seg-fused form and keep_all plans read it)
     wsp: torch.Tensor | None = None
+    # SRMB mask on its live channels (bf16, PackedNet.srmb_sparse): the drnmi_psp_pack blob of wpk and the
+    # (P, d) it was packed with (enum drnmi_psp_tile); the launch is DRNMI_BF16_PSP with wgt = wps, tile = psp_tile
+    wps: torch.Tensor | None = None
+    psp_tile: int = -1
 
 
 @dataclass
@@ -289,11 +293,12 @@ class PackedNet:
     any PackedNet stays valid while other precisions are packed."""
 
     def __init__(self, graph: Graph, precision: str, device, block_sparse: bool = True,
-                 act_scales: dict | None = None, sparse24: bool = False):
+                 act_scales: dict | None = None, sparse24: bool = False, srmb_sparse: bool = False):
         self.graph = Graph(nodes=[dataclasses.replace(nd) for nd in graph.nodes],
                            stage_outputs=dict(graph.stage_outputs), channels=dict(graph.channels))
         self.block_sparse = block_sparse
         self.sparse24 = sparse24
+        self.srmb_sparse = srmb_sparse
         # fp32x2 (the fine-tune's validate()): the fp32x plan and buffers, its conv_x6 launches issued
         # as DRNMI_F32X2 on the leading two of the three weight planes
         self.two_plane = precision == "fp32x2"
@@ -408,6 +413,56 @@ class PackedNet:
             self.front_eligible = self._front_shapes_ok()
             self.block_pairs = {c: self._block_pairs(c) for c in (16, 64)}
             self._pack_sp24()
+            self._pack_psp()
+
+    def _pack_psp(self):
+        """bf16 with srmb_sparse on: every stride-1 3x3 / 1x1 conv with a folded BN scale whose weights carry
+        an SRMBRepMasker mask the period-sparse kernel takes (drnmi_psp_pack on the weights' zeros: whole
+        16-row classes, P-periodic supports; include/drnmi.h DRNMI_BF16_PSP) is packed compacted and
+        launched as DRNMI_BF16_PSP.  Fixed precedence, first match wins: a folded downsample (either side)
+        and the fused blocks stay as they are; block-sparse routing (a unit mask); 2:4 routing (wsp); the
+        conv that feeds the 19-class seg classifier in the seg-fused shape (3x3 -> 512, no residual, SEG_FUSE
+        on) stays dense so that segment() keeps the fusion; then this route.  Everything else, and every
+        other precision, stays as it is."""
+        for nd in self.graph.nodes:
+            nd.wps, nd.psp_tile = None, -1
+        if not self.srmb_sparse or self.precision != "bf16":
+            return
+        lib = _lib.load()
+        nodes = self.graph.nodes
+        in_block = {j for pairs in self.block_pairs.values() for i in pairs for j in (i, i + 1)}
+        seg = [nd for nd in nodes if nd.out_fp32_nchw]
+        keep_for_seg = {i for i, nd in enumerate(nodes)
+                        if SEG_FUSE and len(seg) == 1 and nd.dst == seg[0].src and seg[0].conv.out_channels == 19
+                        and seg[0].conv.kernel_size[0] == 1 and nd.conv.kernel_size[0] == 3
+                        and nd.conv.out_channels == 512 and nd.res is None}
+        variant, viol = ctypes.c_int32(-1), ctypes.c_int32(0)
+        for i, nd in enumerate(nodes):
+            c = nd.conv
+            cout, ks = c.out_channels, c.kernel_size[0]
+            if not nd.scale_folded or nd.i8 or nd.x6 or nd.fused or nd.fused_into >= 0 or i in in_block or \
+                    nd.unit_mask is not None or nd.wsp is not None or i in keep_for_seg or nd.out_fp32_nchw or \
+                    ks not in (1, 3) or c.stride[0] != 1 or cout % 128 or cout != nd.cout_pad or nd.cin_stride < 64 or \
+                    nd.k_pad != nd.k:
+                continue
+            host = nd.wpk.view(torch.int16).cpu().contiguous().numpy()
+            args = (host.ctypes.data, cout, nd.cin_stride, ks)
+            _lib.check(lib.drnmi_psp_pack(*args, None, 0, ctypes.byref(variant), ctypes.byref(viol)), f"psp_pack {nd.name}")
+            if variant.value < 0:
+                continue
+            a = _probe_args(nd, nd.cin_stride, nd.k, nd.k_pad)
+            a.dtype, a.tile = _lib.DRNMI_BF16_PSP, variant.value
+            if lib.drnmi_conv_kernel_name(ctypes.byref(a)) is None:
+                continue
+            nbytes = int(lib.drnmi_psp_pack_bytes(cout, nd.cin_stride, ks, variant.value))
+            blob = torch.empty(nbytes, dtype=torch.uint8, pin_memory=True)
+            _lib.check(lib.drnmi_psp_pack(*args, blob.data_ptr(), nbytes, ctypes.byref(variant), ctypes.byref(viol)),
+                       f"psp_pack {nd.name}")
+            nd.wps, nd.psp_tile = blob.to(self.device), variant.value
+
+    def srmb_sparse_layers(self) -> list:
+        """Names of the nodes launched on the period-sparse kernel."""
+        return [nd.name for nd in self.graph.nodes if nd.wps is not None]
 
     def _pack_sp24(self):
         """bf16 with sparse24 on: every conv that has the sparse kernel's shape (asked of the library's
@@ -912,7 +967,8 @@ class Plan:
         sk, unfold = {}, set()
         for i, nd in enumerate(nodes):
             c = nd.conv
-            if nd.i8 or nd.x6 or nd.wsp is not None or nd.unit_mask is not None or nd.out_fp32_nchw or i in in_block or \
+            if nd.i8 or nd.x6 or nd.wsp is not None or nd.wps is not None or nd.unit_mask is not None or nd.out_fp32_nchw or \
+                    i in in_block or \
                     _uses_patch(nd, nd.cin_stride, pk.base):
                 continue
             oh, ow = self.shapes[nd.dst]
@@ -1133,6 +1189,8 @@ class Plan:
         a.unit_mask = nd.unit_mask.data_ptr() if nd.unit_mask is not None else None
         if nd.wsp is not None:                    # 2:4 sparse launch (never a node with a folded downsample)
             a.wgt, a.dtype = nd.wsp.data_ptr(), (_lib.DRNMI_I8_SP24 if nd.i8 else _lib.DRNMI_BF16_SP24)
+        if nd.wps is not None:                    # period-sparse launch: tile names the blob's (P, d)
+            a.wgt, a.dtype, a.tile = nd.wps.data_ptr(), _lib.DRNMI_BF16_PSP, nd.psp_tile
         if fused:
             f = fused
             a.wgt, a.shift, a.res = f["wpk"].data_ptr(), f["shift"].data_ptr(), None
