@@ -35,7 +35,8 @@ int32_t drnmi_abi_version(void);
 int64_t drnmi_conv_args_size(void);
 
 enum drnmi_dtype { DRNMI_F32 = 0, DRNMI_BF16 = 1, DRNMI_U8 = 2, DRNMI_I64 = 3, DRNMI_I8 = 4, DRNMI_F32X3 = 5,
-                   DRNMI_F8 = 6, DRNMI_BF16_SP24 = 7, DRNMI_I8_SP24 = 8, DRNMI_F32X2 = 9, DRNMI_BF16_PSP = 10 };
+                   DRNMI_F8 = 6, DRNMI_BF16_SP24 = 7, DRNMI_I8_SP24 = 8, DRNMI_F32X2 = 9, DRNMI_BF16_PSP = 10,
+                   DRNMI_MXF8 = 11 };
 /* DRNMI_F32X3 (conv dtype only, the "fp32x" precision mode): x, res and y are fp32 NHWC as in
  * DRNMI_F32, wgt is three bf16 planes [3][cout_pad][k_pad] with w = w1 + w2 + w3 (an exact split
  * of the fp32 weight), and the conv runs fp32-accurate arithmetic on the bf16 MFMA pipe: each
@@ -76,6 +77,36 @@ enum drnmi_dtype { DRNMI_F32 = 0, DRNMI_BF16 = 1, DRNMI_U8 = 2, DRNMI_I64 = 3, D
  *              with cin % 256 == 0 and cout % 256 == 0 take the strip-staged conv_f8_stag_kernel
  *              (DRNMI_TILE_STAG forces it).  DRNMI_TILE_W1 / DRNMI_TILE_W1H, drnmi_conv_stag_seg, a
  *              unit mask and a fused second input have no fp8 form: DRNMI_ENOTSUP. */
+
+/* DRNMI_MXF8 (the "mxfp8" precision mode; added under ABI version 7: a new enum value and five new symbols,
+ * drnmi_conv_args unchanged): e4m3 elements with one power-of-two scale per 32 consecutive input channels,
+ * run on the block-scale inputs of v_mfma_scale_f32_16x16x128_f8f6f4 (csrc/conv_mx.hip).  Activation scales
+ * come from the data of every frame, on the GPU: there is no calibration state.  The format, stated once for
+ * the kernels and for tests/mx8_ref.py:
+ *   element    e4m3(v) exactly as DRNMI_F8 defines it.
+ *   block      32 consecutive channels of one pixel (activations), or 32 consecutive packed columns of one
+ *              row (weights): k = (kh*ks + kw)*cin + ci and cin % 32 == 0, so a block never straddles a tap.
+ *   exponent   amax = max |v| over the block, as an fp32 value m * 2^e with m in [1, 2): E = e - 8 if
+ *              m <= 1.75, else e - 7 -- the smallest E with amax * 2^-E <= 448, so nothing saturates; read
+ *              from the float's bits.  The stored byte is E + 127 clamped to [0, 254] (E8M0); an all-zero
+ *              block stores byte 0 and zero elements; byte 255 (NaN) is never produced.
+ *   elements   e4m3(v * 2^-E) (the scaling is exact); the value of a stored element is
+ *              e4m3_value * 2^(byte - 127).  bf16 and fp32 inputs quantise alike: amax and scaling in fp32.
+ *   storage    private to csrc/conv_mx.hip ("image" of an NHWC value, "blob" of packed weights): only
+ *              drnmi_mx8_image_bytes / drnmi_quantize_mx8 / drnmi_dequantize_mx8 / drnmi_mx8_pack_bytes /
+ *              drnmi_mx8_pack below know it.
+ *   launch     dtype = DRNMI_MXF8: x and res are images ([n*h*w][cin], [n*ho*wo][cout]), wgt is the blob;
+ *              scale non-NULL = the BN scale; res_scale and out_scale are unused.
+ *              acc = fp32 sum over 32-blocks of 2^(Ea + Eb) * dot(a32, b32), K in steps of 128 channels of one
+ *              tap; v = acc * scale[co] + shift[co] (fmul then fadd, no contraction); v += value(res); ReLU.
+ *              out_dtype DRNMI_BF16 / DRNMI_F32 store v with the strided forms of the fp8 launches;
+ *              DRNMI_MXF8 quantises v into an image in the epilogue (dense rows: y_sc 1, y_sp cout,
+ *              y_sn ho*wo*cout; cout % 32 == 0).
+ *   kernels    conv_mx_kernel<1> / <3>: cin a power of two >= 128, ks 1 or 3, stride 1, any dilation, any M,
+ *              cout_pad % 128 == 0, k_pad == k; a residual needs cout % 32 == 0.
+ *   refused    DRNMI_ENOTSUP: x2, unit_mask, a NULL scale, stride 2, cin < 128, drnmi_conv_stag_seg and every
+ *              drnmi_tile but DRNMI_TILE_AUTO; DRNMI_EINVAL: another out_dtype and whatever every launch is
+ *              refused for. */
 
 /* DRNMI_BF16_SP24 (conv dtype only; version 7; inference, opt-in: DRNSeg.set_sparse24): a bf16 launch
  * whose weights have at most two non-zeros in every group of four consecutive packed columns (a
@@ -510,6 +541,21 @@ int drnmi_quantize_i8(const void* x, int32_t dtype, int8_t* y, int64_t n, float 
  * inv_scale: DRNMI_EINVAL before any HIP call.  One streaming kernel on the caller's stream, no allocation (graph-capturable). */
 int drnmi_quantize_f8(const void* x, int32_t dtype, int64_t n, float inv_scale, uint8_t* y, void* stream);
 int drnmi_absmax(const void* x, int32_t dtype, int64_t n, float* out, void* stream);
+/* DRNMI_MXF8 images and weight blobs (csrc/conv_mx.hip; the format: DRNMI_MXF8 above).
+ *   drnmi_mx8_image_bytes: bytes of the image of an [m][c] NHWC value (c % 32 == 0; -1 otherwise).
+ *   drnmi_quantize_mx8: x (BF16 or F32, [m][c], 16-B aligned) -> image (16-B aligned); one streaming kernel
+ *     on the caller's stream, no allocation (graph-capturable).
+ *   drnmi_dequantize_mx8: image -> fp32 [m][c] (debug reads, keep_all plans, the tests).
+ *   drnmi_mx8_pack_bytes: bytes of the blob of [cout_pad][k_pad] weights (both multiples of 128; -1 otherwise).
+ *   drnmi_mx8_pack: HOST function, no GPU: fp32 [cout_pad][k_pad] in host memory -> the blob in host memory
+ *     (nbytes >= drnmi_mx8_pack_bytes), per output channel and 32-column block.
+ * Bad arguments: DRNMI_EINVAL before any HIP call. */
+int64_t drnmi_mx8_image_bytes(int64_t m, int32_t c);
+int drnmi_quantize_mx8(const void* x, int32_t dtype, int64_t m, int32_t c, void* image, void* stream);
+int drnmi_dequantize_mx8(const void* image, int64_t m, int32_t c, float* y_f32, void* stream);
+int64_t drnmi_mx8_pack_bytes(int32_t cout_pad, int32_t k_pad);
+int drnmi_mx8_pack(const float* w_f32, int32_t cout_pad, int32_t k_pad, void* blob, int64_t nbytes);
+
 int drnmi_abs_histogram(const void* x, int32_t dtype, int64_t n, int64_t* hist, void* stream);
 
 /* Name of the kernel (template instance) drnmi_conv2d_bn_act would launch for these

@@ -207,6 +207,11 @@ ConvRoute psp_route(const drnmi_conv_args& p) {
   return psp_conv_supported(p) ? take(psp_kernel(p.tile, p.ks)) : refuse(DRNMI_ENOTSUP);
 }
 
+// --- the block-scaled e4m3 tile (DRNMI_MXF8, conv_mx.hip): one kernel per ks, no forced tiles
+ConvRoute mx_route(const drnmi_conv_args& p) {
+  return mx_conv_supported(p) ? take(mx_kernel(p.ks)) : refuse(DRNMI_ENOTSUP);
+}
+
 // --- conv_x6.  A drnmi_conv_args.tile >= 0 forces variant tile % 6 and, when tile >= 6, tile / 6
 // split-K partitions (tests, micro-benchmarks; split-K only with a caller workspace).
 // 128-channel layers take the two-per-CU 128 x 128 tile: D-22 layer4's five launches 1631-1649 ->
@@ -346,7 +351,7 @@ ConvRoute conv_route(const drnmi_conv_args& p) {
                       p.y_sr < 0 || !x_family(p).supported(p)))
     return refuse(DRNMI_EINVAL);
   if (p.algo == DRNMI_ALGO_PATCH) {
-    if (p.dtype == DRNMI_BF16_SP24 || p.dtype == DRNMI_I8_SP24 || p.dtype == DRNMI_BF16_PSP) return refuse(DRNMI_EINVAL);
+    if (p.dtype == DRNMI_BF16_SP24 || p.dtype == DRNMI_I8_SP24 || p.dtype == DRNMI_BF16_PSP || p.dtype == DRNMI_MXF8) return refuse(DRNMI_EINVAL);
     if (p.x2 != nullptr) return refuse(DRNMI_ENOTSUP);     // fused second input: LDS-DMA kernels only
     if (p.n <= 0 || p.h <= 0 || p.w <= 0 || p.cout > p.cout_pad || !conv_geometry(p)) return refuse(DRNMI_EINVAL);
     return take(patch_kernel(p));
@@ -361,7 +366,7 @@ ConvRoute conv_route(const drnmi_conv_args& p) {
   if (p.cout <= 0 || p.cout > p.cout_pad || p.k != p.ks * p.ks * p.cin + (p.x2 != nullptr ? p.cin2 : 0))
     return refuse(DRNMI_EINVAL);
   if (p.k_pad < p.k || p.k_pad % kBK != 0 || p.stride <= 0 || p.dil <= 0 || p.pad < 0) return refuse(DRNMI_EINVAL);
-  if (p.dtype == DRNMI_I8 || p.dtype == DRNMI_F8) {       // 8-bit: the code's own type, bf16 or fp32
+  if (p.dtype == DRNMI_I8 || p.dtype == DRNMI_F8 || p.dtype == DRNMI_MXF8) {       // 8-bit: the code's own type, bf16 or fp32
     if (p.out_dtype != p.dtype && p.out_dtype != DRNMI_BF16 && p.out_dtype != DRNMI_F32) return refuse(DRNMI_EINVAL);
   } else if (p.dtype == DRNMI_I8_SP24) {                  // the int8 route's outputs
     if (p.out_dtype != DRNMI_I8 && p.out_dtype != DRNMI_BF16 && p.out_dtype != DRNMI_F32) return refuse(DRNMI_EINVAL);
@@ -380,6 +385,7 @@ ConvRoute conv_route(const drnmi_conv_args& p) {
   if (p.dtype == DRNMI_F32X2) return x3_route(p);
   if (p.dtype == DRNMI_BF16_SP24 || p.dtype == DRNMI_I8_SP24) return sp24_route(p);
   if (p.dtype == DRNMI_BF16_PSP) return psp_route(p);
+  if (p.dtype == DRNMI_MXF8) return mx_route(p);
   if (p.tile >= DRNMI_TILE_DMA128 || (p.tile < 0 && (big_conv_supported(p) || halo_conv_supported(p)))) return big_route(p);
   if (p.x2 != nullptr) return refuse(DRNMI_ENOTSUP);          // fused second input: LDS-DMA kernels only
   const int tile = p.tile < 0 ? auto_tile(p.cout) : p.tile;
@@ -433,8 +439,8 @@ struct SegRoute {
 // staggered one (the same partial logits, bit for bit: the bit-identity test).
 SegRoute seg_route(const drnmi_conv_args& p) {
   if (p.algo != DRNMI_ALGO_IGEMM || p.src_u8) return {DRNMI_EINVAL, nullptr};
-  if (p.dtype == DRNMI_F8 || p.dtype == DRNMI_BF16_SP24 || p.dtype == DRNMI_I8_SP24 || p.dtype == DRNMI_BF16_PSP)
-    return {DRNMI_ENOTSUP, nullptr};   // no seg-fused fp8 / 2:4 / period-sparse form
+  if (p.dtype == DRNMI_F8 || p.dtype == DRNMI_BF16_SP24 || p.dtype == DRNMI_I8_SP24 || p.dtype == DRNMI_BF16_PSP || p.dtype == DRNMI_MXF8)
+    return {DRNMI_ENOTSUP, nullptr};   // no seg-fused fp8 / 2:4 / period-sparse / block-scaled form
   const bool i8 = p.dtype == DRNMI_I8;
   // int8 nets: the conv's int8 output (out_dtype I8, quantised with out_scale) feeds int8 seg
   // weights; int32 partials

@@ -100,6 +100,10 @@ const ConvKernel* sp24_strip_kernel(int dtype);  // 3x3 stride 1, wo % 256 == 0,
 bool psp_conv_supported(const drnmi_conv_args& p);
 const ConvKernel* psp_kernel(int variant, int ks);
 
+// conv_mx.hip: the block-scaled e4m3 tile (dtype DRNMI_MXF8) on the scaled MFMA; rows by ks
+bool mx_conv_supported(const drnmi_conv_args& p);
+const ConvKernel* mx_kernel(int ks);
+
 // conv_halo.hip: halo-patch 3x3 stride-1 conv, cin / cout 64 or 128
 bool halo_conv_supported(const drnmi_conv_args& p);
 const ConvKernel* halo_kernel(int cin, int cout);

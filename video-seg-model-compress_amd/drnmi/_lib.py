@@ -15,6 +15,7 @@ DRNMI_BF16_SP24 = 7
 DRNMI_I8_SP24 = 8
 DRNMI_F32X2 = 9           # conv dtype: two bf16 weight planes, three products (csrc/conv_x3.hip)
 DRNMI_BF16_PSP = 10       # conv dtype: SRMB-masked weights on their live channels (csrc/conv_psp.hip)
+DRNMI_MXF8 = 11           # block-scaled e4m3 images and weight blobs (csrc/conv_mx.hip)
 SP24_GATHER, SP24_STRIP = 0, 1          # include/drnmi.h enum drnmi_sp24_tile
 PSP_VARIANTS = ((32, 16), (64, 16), (64, 8), (32, 8))   # enum drnmi_psp_tile: (P, d) by value
 ALGO_IGEMM, ALGO_PATCH = 0, 1
@@ -172,6 +173,11 @@ SIGNATURES = {
     "drnmi_quantize_i8": (ctypes.c_int, [_VP, _I32, _VP, _I64, _F32, _VP]),
     "drnmi_quantize_f8": (ctypes.c_int, [_VP, _I32, _I64, _F32, _VP, _VP]),
     "drnmi_absmax": (ctypes.c_int, [_VP, _I32, _I64, _VP, _VP]),
+    "drnmi_mx8_image_bytes": (ctypes.c_int64, [_I64, _I32]),
+    "drnmi_quantize_mx8": (ctypes.c_int, [_VP, _I32, _I64, _I32, _VP, _VP]),
+    "drnmi_dequantize_mx8": (ctypes.c_int, [_VP, _I64, _I32, _VP, _VP]),
+    "drnmi_mx8_pack_bytes": (ctypes.c_int64, [_I32, _I32]),
+    "drnmi_mx8_pack": (ctypes.c_int, [_VP, _I32, _I32, _VP, _I64]),
     "drnmi_abs_histogram": (ctypes.c_int, [_VP, _I32, _I64, _VP, _VP]),
     "drnmi_train_ingest_u8": (ctypes.c_int, [_VP, _VP, _I32, _I32, _I32, _VP, _VP, _I32, _I32, _VP, _VP, _VP, _VP, _VP]),
     "drnmi_pixel_accuracy_f32": (ctypes.c_int, [_VP, _VP, _I32, _I32, _I64, _I64, _VP, _VP]),

@@ -22,7 +22,9 @@ Differences by design:
     bits, csrc/conv_x3.hip), "fp32x" (fp32-accurate arithmetic on the bf16 MFMA pipe: exact 3-way bf16 splits,
     6 products, for every conv with cin >= 32; parity gates as fp32, ~3x faster), "bf16"
     (perf mode, fp32 accumulation), "fp8" (OCP e4m3 weights and activations on the same convs
-    as int8, fp32 accumulation, the int8 calibration's scales; inference only) or "int8" (W8A8 for the cin >= 64 convs,
+    as int8, fp32 accumulation, the int8 calibration's scales; inference only), "mxfp8" (e4m3 with
+    one power-of-two scale per 32 input channels, computed from every frame's data on the GPU: no
+    calibration at all; the stride-1 convs with cin >= 128 among int8's; inference only) or "int8" (W8A8 for the cin >= 64 convs,
     config C5; needs calibrate_int8() or load_int8_state() first — the reference has no
     quantisation, so this mode is ours; DRN-D only) via set_precision().
   * segment(frames_u8) is the fused seg_video path (seg_video_old_no_plot.py:157-169:
@@ -265,11 +267,11 @@ class DRNSeg(nn.Module):
 
     # ----------------------------------------------------------------- configuration
     def set_precision(self, precision: str) -> "DRNSeg":
-        if precision not in ("fp32", "fp32x", "fp32x2", "bf16", "int8", "fp8"):
-            raise ValueError("precision must be 'fp32', 'fp32x', 'fp32x2', 'bf16', 'int8' or 'fp8'")
-        if precision in ("int8", "fp8") and self.arch != "D":
+        if precision not in ("fp32", "fp32x", "fp32x2", "bf16", "int8", "fp8", "mxfp8"):
+            raise ValueError("precision must be 'fp32', 'fp32x', 'fp32x2', 'bf16', 'int8', 'fp8' or 'mxfp8'")
+        if precision in ("int8", "fp8", "mxfp8") and self.arch != "D":
             # the int8 launches are pinned bit for bit by an oracle that restates DRN-D only, and fp8
-            # follows int8's layout
+            # and mxfp8 follow int8's layout
             raise NotImplementedError(f"precision '{precision}' covers the DRN-D family only; {self.model_name} "
                                       "runs in 'fp32', 'fp32x' or 'bf16'")
         if precision != "bf16" and getattr(self, "low_latency", False):

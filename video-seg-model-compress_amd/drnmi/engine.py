@@ -32,17 +32,23 @@ COUT_ALIGN = 128
 
 DTYPES = {"fp32": (torch.float32, _lib.DRNMI_F32), "bf16": (torch.bfloat16, _lib.DRNMI_BF16),
           "fp32x": (torch.float32, _lib.DRNMI_F32),
-          "fp8": (torch.bfloat16, _lib.DRNMI_BF16)}      # fp8: its base (the small-channel layers) is bf16
+          "fp8": (torch.bfloat16, _lib.DRNMI_BF16),      # fp8: its base (the small-channel layers) is bf16
+          "mxfp8": (torch.bfloat16, _lib.DRNMI_BF16)}
 # fp32x: fp32 activations everywhere (the fp32 mode's buffers); the convs with cin >= X6_MIN_CIN
 # and ks 1/3 run fp32-accurate split-bf16 arithmetic (csrc/conv_x6.hip, dtype DRNMI_F32X3), the
 # full-resolution small-channel stem / layer1 / layer2 stay on the exact f32 MFMA kernels.
 X6_MIN_CIN = 32
 TORCH_OF_CODE = {_lib.DRNMI_F32: torch.float32, _lib.DRNMI_BF16: torch.bfloat16, _lib.DRNMI_I8: torch.int8,
-                 _lib.DRNMI_F8: torch.uint8}       # e4m3 values live as raw bytes (.view(torch.float8_e4m3fn) decodes)
+                 _lib.DRNMI_F8: torch.uint8,       # e4m3 values live as raw bytes (.view(torch.float8_e4m3fn) decodes)
+                 _lib.DRNMI_MXF8: torch.uint8}     # an image: elements and scale bytes (drnmi_dequantize_mx8 decodes)
 # The 8-bit precisions: the value code of their 8-bit launches.  Both share the layout rules below
 # (PackedNet._int8_layout), the calibrated activation scales ("clip = 127 s") and the bf16 base.
 # fp8 (include/drnmi.h DRNMI_F8): OCP e4m3, maximum 448; the fp8 scale of a tensor is s * 127 / 448.
-Q8_CODES = {"int8": _lib.DRNMI_I8, "fp8": _lib.DRNMI_F8}
+# mxfp8 (include/drnmi.h DRNMI_MXF8): e4m3 with one power-of-two scale per 32 input channels, taken from the
+# data on the GPU: the same layout rules on the launches conv_mx_kernel takes (MX_MIN_CIN, stride 1), no
+# activation scales at all.
+Q8_CODES = {"int8": _lib.DRNMI_I8, "fp8": _lib.DRNMI_F8, "mxfp8": _lib.DRNMI_MXF8}
+MX_MIN_CIN = 128
 F8_MAX = 448.0
 # W8A8 (config C5): convs whose input channel stride is >= this run on the int8 MFMA kernel
 # (conv_i8_kernel: K steps of 64/128 int8 channels); the full-resolution small-channel layers
@@ -240,13 +246,14 @@ def _fold_bn(bn: nn.BatchNorm2d):
     return scale, shift
 
 
-def int8_layout(graph: Graph, cstride: dict):
+def int8_layout(graph: Graph, cstride: dict, admit=None):
     """The 8-bit layout decision of a graph, from the graph and its channel strides alone (no
     device, no scales): (elig, q8_values, need).  elig: indices of the nodes that launch W8A8;
     q8_values: the values that are 8-bit in HBM (an 8-bit launch produces them and only 8-bit
     launches read them), in elig's order; need: the values some node of elig reads as src or res.
     PackedNet builds its plan on it; quantisation-aware fine-tuning (drnmi.train) fake-quantises
-    exactly the weights of elig and the values of need."""
+    exactly the weights of elig and the values of need.  admit(node), if given, narrows elig (mxfp8:
+    the nodes its kernel refuses stay on the bf16 base)."""
     g = graph
     # (cout >= 128 too: the int8 tiles are 128 channels wide; the 64-channel layer3 convs keep
     # the bf16 halo kernel)
@@ -261,7 +268,8 @@ def int8_layout(graph: Graph, cstride: dict):
         return not (nd.res and nd.res in producer and g.nodes[producer[nd.res]].name.endswith("downsample.0"))
     elig = {i for i, nd in enumerate(g.nodes)
             if cstride[nd.src] >= INT8_MIN_CIN and nd.conv.kernel_size[0] in (1, 3)
-            and (nd.conv.out_channels >= INT8_MIN_COUT or nd.out_fp32_nchw or layer4_shape(nd))}
+            and (nd.conv.out_channels >= INT8_MIN_COUT or nd.out_fp32_nchw or layer4_shape(nd))
+            and (admit is None or admit(nd))}
     readers = {}
     for i, nd in enumerate(g.nodes):
         for v in (nd.src, nd.res):
@@ -326,10 +334,12 @@ class PackedNet:
         launch gets an int8 copy "q:<value>" quantised right after its producer."""
         g = self.graph
         producer = {nd.dst: i for i, nd in enumerate(g.nodes)}
-        elig, q8_values, need = int8_layout(g, self.cstride)
+        mx = self.qcode == _lib.DRNMI_MXF8
+        elig, q8_values, need = int8_layout(
+            g, self.cstride, (lambda nd: self.cstride[nd.src] >= MX_MIN_CIN and nd.conv.stride[0] == 1) if mx else None)
         for v in q8_values:
             self.vcode[v] = self.qcode
-        missing = sorted(v for v in need | set(self.vcode) if v not in self.act_scales)
+        missing = [] if mx else sorted(v for v in need | set(self.vcode) if v not in self.act_scales)
         if missing:
             raise RuntimeError(f"{self.precision}: no calibrated activation scale for {missing} (DRNSeg.calibrate_int8)")
         for v in sorted(need):
@@ -380,7 +390,10 @@ class PackedNet:
                 nd.i8, nd.x_val, nd.r_val, nd.res_scale, nd.out_scale = False, nd.src, nd.res, 0.0, 0.0
                 nd.x6 = False
                 if ni in self.i8_nodes:
-                    self._pack_q8(nd, full, scale, cout)
+                    if self.qcode == _lib.DRNMI_MXF8:
+                        self._pack_mx8(nd, full, scale)
+                    else:
+                        self._pack_q8(nd, full, scale, cout)
                     continue
                 if self.precision == "fp32x" and cs >= X6_MIN_CIN and kh in (1, 3):
                     nd.x6 = True
@@ -665,6 +678,27 @@ class PackedNet:
         nd.wpk = encode(full * inv[:, None]).to(full.device).contiguous()
         self._q8_fields(nd, torch.where(pos, a / qmax, torch.ones_like(a)), bn_scale)
 
+    def _pack_mx8(self, nd: ConvNode, full: torch.Tensor, bn_scale: torch.Tensor):
+        """Block-scaled e4m3 weights (include/drnmi.h DRNMI_MXF8): drnmi_mx8_pack's blob of the fp32 rows, one
+        scale per output channel and 32 packed columns; the epilogue scale is the BN scale alone, and the
+        launch carries no activation scale: the values it reads and writes are images."""
+        lib = _lib.load()
+        w = full.cpu().contiguous()
+        nbytes = int(lib.drnmi_mx8_pack_bytes(nd.cout_pad, nd.k_pad))
+        if nbytes < 0:
+            raise RuntimeError(f"mxfp8: no weight blob for {nd.name} ({nd.cout_pad} x {nd.k_pad})")
+        blob = torch.empty(nbytes, dtype=torch.uint8)
+        _lib.check(lib.drnmi_mx8_pack(w.data_ptr(), nd.cout_pad, nd.k_pad, blob.data_ptr(), nbytes), f"mx8_pack {nd.name}")
+        nd.wpk = blob.to(full.device)
+        nd.scale = bn_scale.float().contiguous()
+        nd.scale_folded = False
+        nd.unit_mask, nd.zero_unit_frac = None, 0.0
+        nd.i8 = True
+        q8 = self.qcode
+        nd.x_val = nd.src if self.vcode.get(nd.src) == q8 else "q:" + nd.src
+        if nd.res:
+            nd.r_val = nd.res if self.vcode.get(nd.res) == q8 else "q:" + nd.res
+
     def _q8_fields(self, nd: ConvNode, sw: torch.Tensor, bn_scale: torch.Tensor):
         """What an 8-bit launch carries besides its weights, for either 8-bit code."""
         q8 = self.qcode
@@ -887,6 +921,9 @@ class Plan:
 
         def alloc(v, numel):
             td = TORCH_OF_CODE[packed.value_code(v)]
+            if packed.value_code(v) == _lib.DRNMI_MXF8:       # an image: the elements and their scale bytes
+                c = packed.cstride[v[2:] if v.startswith("q:") else v]
+                numel = int(lib.drnmi_mx8_image_bytes(numel // c, c))
             lst = pool.get((numel, td))
             self.bufs[v] = lst.pop() if lst else torch.empty(numel, dtype=td, device=dev)
 
@@ -1039,7 +1076,7 @@ class Plan:
         if seg.conv.kernel_size[0] != 1 or not 1 <= classes <= 256:
             return
         wide = classes != 19
-        if wide and pk.precision not in ("bf16", "int8", "fp8"):
+        if wide and pk.precision not in ("bf16", "int8", "fp8", "mxfp8"):
             return                               # fp32 / fp32x plans keep the logits planes
         cs = (classes + 3) // 4 * 4 if wide else self.SEG_NHWC_CS
         lh, lw = self.shapes[seg.dst]
@@ -1049,7 +1086,7 @@ class Plan:
         name = lib.drnmi_conv_kernel_name(ctypes.byref(a))   # (routing does not read a.y)
         if name is None or not name.decode().startswith(("conv_big_kernel", "conv_i8_kernel", "conv_i8_occ2_kernel",
                                                         "conv_x6_kernel", "conv_x3_kernel", "conv_f8_kernel", "conv_f8_occ2_kernel",
-                                                        "conv_sp24_kernel", "conv_sp24_i8_kernel")):
+                                                        "conv_sp24_kernel", "conv_sp24_i8_kernel", "conv_mx_kernel")):
             return
         if "logits_nhwc" not in self.bufs:      # only plans whose seg conv writes the NHWC rows
             self.bufs["logits_nhwc"] = torch.empty(self.n * lh * lw * cs, dtype=torch.float32, device=pk.device)
@@ -1058,8 +1095,8 @@ class Plan:
         self.seg_classes, self.seg_cs = classes, cs
         if wide or not SEG_FUSE or not self.fuse or seg.x_val != seg.src or seg.r_val:
             return
-        if pk.qcode == _lib.DRNMI_F8:
-            return                               # fp8: a separate seg conv feeds the NHWC head (no seg-fused fp8 tile)
+        if pk.qcode in (_lib.DRNMI_F8, _lib.DRNMI_MXF8):
+            return                               # fp8 / mxfp8: a separate seg conv feeds the NHWC head (no seg-fused tile)
         # the launch that writes the seg conv's input, on the labels-only list without this fusion:
         # one that already computes several nodes (front, block, folded downsample) is left alone
         prod = [l for l in self._build_launches("u8" if self.stem_u8 is not None else "nchw", True)
@@ -1252,6 +1289,11 @@ class Plan:
     def _quantize(self, lib, v: str, stream: ctypes.c_void_p):
         """bf16 value -> its 8-bit copy "q:<v>" (include/drnmi.h drnmi_quantize_i8 / drnmi_quantize_f8)."""
         src, dst = self.bufs[v], self.bufs["q:" + v]
+        if self.packed.qcode == _lib.DRNMI_MXF8:
+            c = self.packed.cstride[v]
+            _lib.check(lib.drnmi_quantize_mx8(src.data_ptr(), self.packed.value_code(v), src.numel() // c, c,
+                                              dst.data_ptr(), stream), f"quantize_mx8 {v}")
+            return
         if self.packed.qcode == _lib.DRNMI_F8:
             _lib.check(lib.drnmi_quantize_f8(src.data_ptr(), self.packed.value_code(v), dst.numel(),
                                              1.0 / self.packed.act_scale(v), dst.data_ptr(), stream), f"quantize_f8 {v}")
@@ -1361,6 +1403,12 @@ class Plan:
             cs = self.packed.cstride[value]
             q = self.bufs[value].view(torch.float8_e4m3fn).view(self.n, oh, ow, cs)[..., :c]
             return (q.float() * self.packed.act_scale(value)).permute(0, 3, 1, 2).contiguous()
+        if self.packed.value_code(value) == _lib.DRNMI_MXF8:
+            cs = self.packed.cstride[value]
+            q = torch.empty(self.n, oh, ow, cs, dtype=torch.float32, device=self.packed.device)
+            _lib.check(lib.drnmi_dequantize_mx8(self.bufs[value].data_ptr(), self.n * oh * ow, cs, q.data_ptr(),
+                                                ctypes.c_void_p(_lib.stream_ptr())), "dequantize_mx8")
+            return q[..., :c].permute(0, 3, 1, 2).contiguous()
         out = torch.empty(self.n, c, oh, ow, dtype=torch.float32, device=self.packed.device)
         _lib.check(lib.drnmi_nhwc_to_nchw(self.bufs[value].data_ptr(), out.data_ptr(), self.n, c, oh, ow,
                                           self.packed.cstride[value], self.packed.value_code(value),
