@@ -5,7 +5,8 @@ before Plan.launches existed (its "recorded_from"): every C call of run_backbone
 with the hook indices, kernel names, buffers by name and a hash of every other argument, plus
 launch_work and the plan's public attributes.  Here the same recorder runs on this tree and must
 see the same thing, and the Launch list must describe exactly the calls the recorder saw.  No GPU:
-the launch entry points are answered by the recorder."""
+the launch entry points are answered by the recorder.  launch_plans_q8.json.gz holds the same for
+fp8, mxfp8 and fp32x2, recorded on the commit before the engine's table of 8-bit codes."""
 from __future__ import annotations
 
 import gzip
@@ -22,16 +23,20 @@ import make_launch_plans as G  # noqa: E402
 from drnmi import _lib, engine, roofline  # noqa: E402
 
 KIND_OF = {"conv2d_bn_act": "conv", "stem_layer1": "stem_layer1", "video_front_u8": "front",
-           "basic_block64": "block64", "basic_block16": "block16", "conv_stag_seg": "conv_seg"}
+           "basic_block64": "block64", "basic_block16": "block16", "conv_stag_seg": "conv_seg",
+           "conv_splitk": "conv_sk"}
+QUANTIZE = tuple(e[len("drnmi_"):] for e in G.QUANTIZE)
 MODES = {"nchw/full": ("nchw", False), "u8/full": ("u8", False), "u8/labels": ("u8", True)}
-_DOC = {}
+FIXTURES = {"launch_plans.json.gz": G.groups(), "launch_plans_q8.json.gz": G.groups_q8()}
+FIXTURE_OF = {g: name for name, groups in FIXTURES.items() for g in groups}
+_DOCS = {}
 
 
-def golden():
-    if not _DOC:
-        with gzip.open(os.path.join(GOLDEN, "launch_plans.json.gz"), "rt") as f:
-            _DOC.update(json.load(f))
-    return _DOC
+def golden(name="launch_plans.json.gz"):
+    if name not in _DOCS:
+        with gzip.open(os.path.join(GOLDEN, name), "rt") as f:
+            _DOCS[name] = json.load(f)
+    return _DOCS[name]
 
 
 def resolved(case: dict, table: list) -> dict:
@@ -51,7 +56,7 @@ def check_launch_list(plan, raw: dict):
     nodes = plan.packed.graph.nodes
     for mode, calls in raw.items():
         launches = plan.launches(*MODES[mode])
-        seen = [d for d in calls if d["entry"] != "quantize_i8"]
+        seen = [d for d in calls if d["entry"] not in QUANTIZE]
         assert [(l.row, l.kind) for l in launches] == [(d["index"], KIND_OF[d["entry"]]) for d in seen], mode
         for l, d in zip(launches, seen):
             assert l.kernel_name(lib) == (d["kernel"] or ""), (mode, l.row)
@@ -60,7 +65,7 @@ def check_launch_list(plan, raw: dict):
             assert {bufs[k].data_ptr() for k in l.reads} == {a for a in d["addr"][0] if a in buf_addrs}, (mode, l.row)
             if any(a not in buf_addrs for a in d["addr"][0]):       # the caller's frames
                 assert l.row == 0 and l.reads == () and MODES[mode][0] == "u8"
-        quant = [(d["index"], d["addr"]) for d in calls if d["entry"] == "quantize_i8"]
+        quant = [(d["index"], d["addr"]) for d in calls if d["entry"] in QUANTIZE]
         assert quant == [(l.row, ([bufs[v].data_ptr()], [bufs["q:" + v].data_ptr()])) for l in launches for v in l.quant]
         assert sorted(k for l in launches for k in l.nodes) == list(range(len(nodes))), mode
         for i, nd in enumerate(nodes):
@@ -68,7 +73,7 @@ def check_launch_list(plan, raw: dict):
                 assert [l.row for l in launches if i in l.nodes] == [nd.fused_into]
 
 
-def check_refresh(plan, name: str):
+def check_refresh(plan, name: str, doc: dict):
     """After a repack the plan records as the same case again, on the new weight tensors (the old
     ones are kept alive, so no address can repeat), from rebuilt launch lists."""
     before = {m: plan.launches(*sm) for m, sm in MODES.items()}
@@ -80,7 +85,7 @@ def check_refresh(plan, name: str):
     assert all(a != b for a, b in zip(old_wgt, [a.wgt for a in plan.args if a is not None]))
     table = {}
     case, raw = G.record_plan(plan, engine, _lib, roofline, table)
-    assert resolved(case, list(table)) == resolved(golden()["cases"][name], golden()["launch_table"])
+    assert resolved(case, list(table)) == resolved(doc["cases"][name], doc["launch_table"])
     for m, sm in MODES.items():
         assert plan.launches(*sm) is not before[m]
     check_launch_list(plan, raw)
@@ -105,24 +110,25 @@ def check_live_args(plan):
 
 
 def test_fixture_covers_the_cases():
-    doc = golden()
-    assert doc["recorded_from"]
-    assert list(doc["cases"]) == [spec[0] for specs in G.groups().values() for spec in specs]
+    for name, groups in FIXTURES.items():
+        doc = golden(name)
+        assert doc["recorded_from"]
+        assert list(doc["cases"]) == [spec[0] for specs in groups.values() for spec in specs]
 
 
-@pytest.mark.parametrize("group", list(G.groups()))
+@pytest.mark.parametrize("group", list(FIXTURE_OF))
 def test_launches_equal_the_recorded_plan(group):
-    doc = golden()
+    doc = golden(FIXTURE_OF[group])
     table, seen = {}, []
 
     def on_plan(spec, plan, case, raw):
         check_launch_list(plan, raw)
         if not seen:                              # once per group: the repack and the live arg structs
             check_live_args(plan)
-            check_refresh(plan, spec[0])
+            check_refresh(plan, spec[0], doc)
         seen.append(spec[0])
 
-    cases = G.record_group(G.groups()[group], table, on_plan)
+    cases = G.record_group(FIXTURES[FIXTURE_OF[group]][group], table, on_plan)
     for name, case in cases.items():
         assert resolved(case, list(table)) == resolved(doc["cases"][name], doc["launch_table"]), name
     assert seen == list(cases)

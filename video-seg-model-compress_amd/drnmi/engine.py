@@ -38,16 +38,12 @@ DTYPES = {"fp32": (torch.float32, _lib.DRNMI_F32), "bf16": (torch.bfloat16, _lib
 # and ks 1/3 run fp32-accurate split-bf16 arithmetic (csrc/conv_x6.hip, dtype DRNMI_F32X3), the
 # full-resolution small-channel stem / layer1 / layer2 stay on the exact f32 MFMA kernels.
 X6_MIN_CIN = 32
-TORCH_OF_CODE = {_lib.DRNMI_F32: torch.float32, _lib.DRNMI_BF16: torch.bfloat16, _lib.DRNMI_I8: torch.int8,
-                 _lib.DRNMI_F8: torch.uint8,       # e4m3 values live as raw bytes (.view(torch.float8_e4m3fn) decodes)
-                 _lib.DRNMI_MXF8: torch.uint8}     # an image: elements and scale bytes (drnmi_dequantize_mx8 decodes)
-# The 8-bit precisions: the value code of their 8-bit launches.  Both share the layout rules below
-# (PackedNet._int8_layout), the calibrated activation scales ("clip = 127 s") and the bf16 base.
+# The 8-bit precisions (_Q8_TABLE below says everything else of them): all share the layout rules
+# (PackedNet._int8_layout) and the bf16 base; int8 and fp8 the calibrated activation scales ("clip = 127 s").
 # fp8 (include/drnmi.h DRNMI_F8): OCP e4m3, maximum 448; the fp8 scale of a tensor is s * 127 / 448.
 # mxfp8 (include/drnmi.h DRNMI_MXF8): e4m3 with one power-of-two scale per 32 input channels, taken from the
 # data on the GPU: the same layout rules on the launches conv_mx_kernel takes (MX_MIN_CIN, stride 1), no
 # activation scales at all.
-Q8_CODES = {"int8": _lib.DRNMI_I8, "fp8": _lib.DRNMI_F8, "mxfp8": _lib.DRNMI_MXF8}
 MX_MIN_CIN = 128
 F8_MAX = 448.0
 # W8A8 (config C5): convs whose input channel stride is >= this run on the int8 MFMA kernel
@@ -102,6 +98,83 @@ def _pow2_at_least(c: int, lo: int = 8) -> int:
 
 def _round_up(v: int, a: int) -> int:
     return (v + a - 1) // a * a
+
+
+@dataclass(frozen=True)
+class _Q8:
+    """Everything the engine knows of one 8-bit value code: PackedNet and Plan read their net's record
+    (PackedNet._q8) and compare codes nowhere."""
+    code: int             # value code of its launches, its values and their "q:" copies
+    storage: torch.dtype  # of a buffer that holds such a value
+    act_scale: object     # calibrated s -> scale of the 8-bit value (int8: clip = 127 s); None: the code takes
+                          # its scales from the data, so its net needs no calibration and its launches carry none
+    admit: object         # (node, channel stride of its input) -> its kernel takes this node of int8_layout's elig
+    numel: object         # (lib, m, c) -> storage elements of an [m][c] value
+    pack_rows: object     # (fp32 rows [cout_pad][k_pad], node name) -> (stored weights, s_w of the epilogue scale)
+    quantize: object      # (lib, packed, v, src, dst, stream) -> status: the bf16 value v -> its copy "q:<v>"
+    dequantize: object    # (lib, packed, v, buf, m, c) -> the stored value as fp32 [m, c]
+    seg_fused: bool       # its convs have a seg-fused form (drnmi_conv_stag_seg)
+
+
+def _q8_rows(qmax: float, encode):
+    """pack_rows of a code with per-output-channel symmetric weights of largest magnitude qmax: a =
+    absmax(row), q = encode(w * (qmax / a)), s_w = a / qmax (1 for an all-zero row).  (int8:
+    oracle/int8_oracle.py quantize_weight_rows; e4m3 is converted on the host: one conversion routine
+    for every device)"""
+    def pack(full, name):
+        a = full.abs().amax(dim=1)
+        pos = a > 0
+        inv = torch.where(pos, qmax / torch.where(pos, a, torch.ones_like(a)), torch.ones_like(a))
+        return encode(full * inv[:, None]).to(full.device).contiguous(), torch.where(pos, a / qmax, torch.ones_like(a))
+    return pack
+
+
+def _mx8_rows(full, name):
+    """Block-scaled e4m3 weights (include/drnmi.h DRNMI_MXF8): drnmi_mx8_pack's blob of the fp32 rows, one
+    scale per output channel and 32 packed columns, so s_w = 1: the epilogue scale is the BN scale alone."""
+    lib = _lib.load()
+    rows, kp = full.shape
+    nbytes = int(lib.drnmi_mx8_pack_bytes(rows, kp))
+    if nbytes < 0:
+        raise RuntimeError(f"mxfp8: no weight blob for {name} ({rows} x {kp})")
+    w, blob = full.cpu().contiguous(), torch.empty(nbytes, dtype=torch.uint8)
+    _lib.check(lib.drnmi_mx8_pack(w.data_ptr(), rows, kp, blob.data_ptr(), nbytes), f"mx8_pack {name}")
+    return blob.to(full.device), 1.0
+
+
+def _mx8_dequantize(lib, pk, v, buf, m, c):
+    out = torch.empty(m, c, dtype=torch.float32, device=buf.device)
+    _lib.check(lib.drnmi_dequantize_mx8(buf.data_ptr(), m, c, out.data_ptr(), ctypes.c_void_p(_lib.stream_ptr())),
+               "dequantize_mx8")
+    return out
+
+
+_Q8_TABLE = {
+    "int8": _Q8(
+        code=_lib.DRNMI_I8, storage=torch.int8, act_scale=lambda s: s, admit=lambda nd, cin: True,
+        numel=lambda lib, m, c: m * c, seg_fused=True,
+        pack_rows=_q8_rows(127.0, lambda q: torch.round(q).clamp_(-127, 127).to(torch.int8)),
+        quantize=lambda lib, pk, v, src, dst, stream: lib.drnmi_quantize_i8(
+            src.data_ptr(), pk.value_code(v), dst.data_ptr(), dst.numel(), 1.0 / pk.act_scale(v), stream),
+        dequantize=lambda lib, pk, v, buf, m, c: buf.view(m, c).float() * pk.act_scale(v)),
+    "fp8": _Q8(                 # e4m3 values live as raw bytes (.view(torch.float8_e4m3fn) decodes)
+        code=_lib.DRNMI_F8, storage=torch.uint8, act_scale=lambda s: s * 127.0 / F8_MAX, admit=lambda nd, cin: True,
+        numel=lambda lib, m, c: m * c, seg_fused=False,
+        pack_rows=_q8_rows(F8_MAX, lambda q: q.clamp_(-F8_MAX, F8_MAX).cpu().to(torch.float8_e4m3fn).view(torch.uint8)),
+        quantize=lambda lib, pk, v, src, dst, stream: lib.drnmi_quantize_f8(
+            src.data_ptr(), pk.value_code(v), dst.numel(), 1.0 / pk.act_scale(v), dst.data_ptr(), stream),
+        dequantize=lambda lib, pk, v, buf, m, c: buf.view(torch.float8_e4m3fn).view(m, c).float() * pk.act_scale(v)),
+    "mxfp8": _Q8(               # a value is an image: the elements and their scale bytes
+        code=_lib.DRNMI_MXF8, storage=torch.uint8, act_scale=None,
+        admit=lambda nd, cin: cin >= MX_MIN_CIN and nd.conv.stride[0] == 1,
+        numel=lambda lib, m, c: int(lib.drnmi_mx8_image_bytes(m, c)), seg_fused=False, pack_rows=_mx8_rows,
+        quantize=lambda lib, pk, v, src, dst, stream: lib.drnmi_quantize_mx8(
+            src.data_ptr(), pk.value_code(v), src.numel() // pk.cstride[v], pk.cstride[v], dst.data_ptr(), stream),
+        dequantize=_mx8_dequantize),
+}
+Q8_CODES = {name: q.code for name, q in _Q8_TABLE.items()}
+TORCH_OF_CODE = {_lib.DRNMI_F32: torch.float32, _lib.DRNMI_BF16: torch.bfloat16,
+                 **{q.code: q.storage for q in _Q8_TABLE.values()}}
 
 
 @dataclass
@@ -312,19 +385,17 @@ class PackedNet:
         self.two_plane = precision == "fp32x2"
         self.precision = precision = "fp32x" if self.two_plane else precision
         # int8 / fp8 nets run their small-channel layers in bf16: "base" is that precision
-        self.qcode = Q8_CODES.get(precision)       # the net's 8-bit value code (None: no 8-bit launches)
-        self.base = "bf16" if self.qcode is not None else precision
+        self._q8 = _Q8_TABLE.get(precision)        # the record of the net's 8-bit code (None: no 8-bit launches)
+        self.qcode = self._q8.code if self._q8 is not None else None
+        self.base = "bf16" if self._q8 is not None else precision
         self.tdtype, self.code = DTYPES[self.base]
         self.device = device
-        self.cstride = {"input": 8}
-        for v, c in graph.channels.items():
-            if v != "input":
-                self.cstride[v] = _pow2_at_least(c)
+        self.cstride = channel_strides(graph)
         self.act_scales = dict(act_scales or {})
         self.vcode = {}            # value -> dtype code where it differs from self.code
         self.quant_after = {}      # node index -> values quantised (bf16 -> "q:" int8) after it
         self.i8_nodes = set()
-        if self.qcode is not None:
+        if self._q8 is not None:
             self._int8_layout()
         self.pack()
 
@@ -334,12 +405,11 @@ class PackedNet:
         launch gets an int8 copy "q:<value>" quantised right after its producer."""
         g = self.graph
         producer = {nd.dst: i for i, nd in enumerate(g.nodes)}
-        mx = self.qcode == _lib.DRNMI_MXF8
-        elig, q8_values, need = int8_layout(
-            g, self.cstride, (lambda nd: self.cstride[nd.src] >= MX_MIN_CIN and nd.conv.stride[0] == 1) if mx else None)
+        q = self._q8
+        elig, q8_values, need = int8_layout(g, self.cstride, lambda nd: q.admit(nd, self.cstride[nd.src]))
         for v in q8_values:
             self.vcode[v] = self.qcode
-        missing = [] if mx else sorted(v for v in need | set(self.vcode) if v not in self.act_scales)
+        missing = sorted(v for v in need | set(self.vcode) if v not in self.act_scales) if q.act_scale else []
         if missing:
             raise RuntimeError(f"{self.precision}: no calibrated activation scale for {missing} (DRNSeg.calibrate_int8)")
         for v in sorted(need):
@@ -358,9 +428,17 @@ class PackedNet:
         """Scale of the 8-bit form of value v: the calibrated s (int8: clip = 127 s), or s * 127 / 448
         in an fp8 net (the same clip on e4m3's range)."""
         s = float(self.act_scales[v])
-        return s * 127.0 / F8_MAX if self.qcode == _lib.DRNMI_F8 else s
+        return self._q8.act_scale(s) if self._q8 is not None and self._q8.act_scale else s
 
     def pack(self):
+        # Which launch a node gets is one precedence, first match wins, in the order this code runs: an
+        # 8-bit node (_int8_layout); fp32x's split-bf16 (x6); a patch kernel (its BN scale stays unfolded);
+        # a block-sparse unit mask; a folded 1x1 downsample, on either side (_fuse_downsamples); part of a
+        # fused block (in_block); 2:4 (_pack_sp24); kept dense for the seg fusion, then period-sparse
+        # (_pack_psp); and, in a low-latency plan only, split-K (Plan._route_low_latency, which unfolds a
+        # downsample it routes).  Every claim is cleared first, so each pass sees the claims of the passes
+        # before it and no others (_dense, _free).
+        self.in_block = set()
         with torch.no_grad():
             for ni, nd in enumerate(self.graph.nodes):
                 conv = nd.conv
@@ -389,11 +467,9 @@ class PackedNet:
                 nd.scale, nd.shift = scale.contiguous(), shift.contiguous()
                 nd.i8, nd.x_val, nd.r_val, nd.res_scale, nd.out_scale = False, nd.src, nd.res, 0.0, 0.0
                 nd.x6 = False
+                nd.fused, nd.fused_into, nd.wsp, nd.wps, nd.psp_tile = None, -1, None, None, -1
                 if ni in self.i8_nodes:
-                    if self.qcode == _lib.DRNMI_MXF8:
-                        self._pack_mx8(nd, full, scale)
-                    else:
-                        self._pack_q8(nd, full, scale, cout)
+                    self._pack_q8(nd, full, scale)
                     continue
                 if self.precision == "fp32x" and cs >= X6_MIN_CIN and kh in (1, 3):
                     nd.x6 = True
@@ -425,25 +501,32 @@ class PackedNet:
             self._packs = {}                  # front_pack / block_pack blobs on the device, by key
             self.front_eligible = self._front_shapes_ok()
             self.block_pairs = {c: self._block_pairs(c) for c in (16, 64)}
+            self.in_block = {j for pairs in self.block_pairs.values() for i in pairs for j in (i, i + 1)}
             self._pack_sp24()
             self._pack_psp()
 
+    def _dense(self, nd: ConvNode) -> bool:
+        """nd is a dense launch of the net's base precision: not 8-bit or split-bf16, and no sparse route
+        (unit mask, 2:4, period-sparse) has claimed it."""
+        return not (nd.i8 or nd.x6) and nd.unit_mask is None and nd.wsp is None and nd.wps is None
+
+    def _free(self, i: int) -> bool:
+        """Node i is free for a packing route: a dense launch (_dense) with the BN scale folded into its
+        weights that computes this one node alone (no folded downsample on either side, no fused block).
+        For pack()'s passes only: they set claims and rely on pack() having cleared all of them first."""
+        nd = self.graph.nodes[i]
+        return self._dense(nd) and nd.scale_folded and not nd.fused and nd.fused_into < 0 and i not in self.in_block
+
     def _pack_psp(self):
-        """bf16 with srmb_sparse on: every stride-1 3x3 / 1x1 conv with a folded BN scale whose weights carry
-        an SRMBRepMasker mask the period-sparse kernel takes (drnmi_psp_pack on the weights' zeros: whole
+        """bf16 with srmb_sparse on: every free (_free) stride-1 3x3 / 1x1 conv whose weights carry an
+        SRMBRepMasker mask the period-sparse kernel takes (drnmi_psp_pack on the weights' zeros: whole
         16-row classes, P-periodic supports; include/drnmi.h DRNMI_BF16_PSP) is packed compacted and
-        launched as DRNMI_BF16_PSP.  Fixed precedence, first match wins: a folded downsample (either side)
-        and the fused blocks stay as they are; block-sparse routing (a unit mask); 2:4 routing (wsp); the
-        conv that feeds the 19-class seg classifier in the seg-fused shape (3x3 -> 512, no residual, SEG_FUSE
-        on) stays dense so that segment() keeps the fusion; then this route.  Everything else, and every
-        other precision, stays as it is."""
-        for nd in self.graph.nodes:
-            nd.wps, nd.psp_tile = None, -1
+        launched as DRNMI_BF16_PSP, except the conv that feeds the 19-class seg classifier in the seg-fused
+        shape (3x3 -> 512, no residual, SEG_FUSE on): it stays dense so that segment() keeps the fusion."""
         if not self.srmb_sparse or self.precision != "bf16":
             return
         lib = _lib.load()
         nodes = self.graph.nodes
-        in_block = {j for pairs in self.block_pairs.values() for i in pairs for j in (i, i + 1)}
         seg = [nd for nd in nodes if nd.out_fp32_nchw]
         keep_for_seg = {i for i, nd in enumerate(nodes)
                         if SEG_FUSE and len(seg) == 1 and nd.dst == seg[0].src and seg[0].conv.out_channels == 19
@@ -453,8 +536,7 @@ class PackedNet:
         for i, nd in enumerate(nodes):
             c = nd.conv
             cout, ks = c.out_channels, c.kernel_size[0]
-            if not nd.scale_folded or nd.i8 or nd.x6 or nd.fused or nd.fused_into >= 0 or i in in_block or \
-                    nd.unit_mask is not None or nd.wsp is not None or i in keep_for_seg or nd.out_fp32_nchw or \
+            if not self._free(i) or i in keep_for_seg or nd.out_fp32_nchw or \
                     ks not in (1, 3) or c.stride[0] != 1 or cout % 128 or cout != nd.cout_pad or nd.cin_stride < 64 or \
                     nd.k_pad != nd.k:
                 continue
@@ -463,8 +545,8 @@ class PackedNet:
             _lib.check(lib.drnmi_psp_pack(*args, None, 0, ctypes.byref(variant), ctypes.byref(viol)), f"psp_pack {nd.name}")
             if variant.value < 0:
                 continue
-            a = _probe_args(nd, nd.cin_stride, nd.k, nd.k_pad)
-            a.dtype, a.tile = _lib.DRNMI_BF16_PSP, variant.value
+            a = _probe_args(nd, nd.cin_stride, nd.k, nd.k_pad, dtype=_lib.DRNMI_BF16_PSP)
+            a.tile = variant.value
             if lib.drnmi_conv_kernel_name(ctypes.byref(a)) is None:
                 continue
             nbytes = int(lib.drnmi_psp_pack_bytes(cout, nd.cin_stride, ks, variant.value))
@@ -478,16 +560,13 @@ class PackedNet:
         return [nd.name for nd in self.graph.nodes if nd.wps is not None]
 
     def _pack_sp24(self):
-        """bf16 with sparse24 on: every conv that has the sparse kernel's shape (asked of the library's
-        own route), a folded BN scale, no folded downsample on either side, no part in a fused block
-        and not one group of four input channels with more than two non-zeros is packed 2:4
+        """bf16 with sparse24 on: every free conv (_free) that has the sparse kernel's shape (asked of the
+        library's own route) and not one group of four input channels with more than two non-zeros is packed 2:4
         (include/drnmi.h drnmi_sp24_pack) and launched as DRNMI_BF16_SP24.  Everything else stays dense.
         int8 with sparse24 on: the same for the int8 wpk of every int8 node the sparse int8 route accepts
         (cin >= 128) among the shapes that gain (_sp24_i8_gains), launched as DRNMI_I8_SP24: a masked fp32
         zero quantises to 0, so a 2:4 fp32 mask is still 2:4 after _pack_q8.  The bf16 nodes of an int8
         net and every other precision stay as they are."""
-        for nd in self.graph.nodes:
-            nd.wsp = None
         if not self.sparse24 or self.precision not in ("bf16", "int8"):
             return
         lib = _lib.load()
@@ -507,15 +586,10 @@ class PackedNet:
             for i in self.sp24_i8_candidates():
                 pack(self.graph.nodes[i], lib.drnmi_sp24_pack_i8_bytes, lib.drnmi_sp24_pack_i8, "sp24_pack_i8")
             return
-        in_block = {j for pairs in self.block_pairs.values() for i in pairs for j in (i, i + 1)}
         for i, nd in enumerate(self.graph.nodes):
-            if not nd.scale_folded or nd.i8 or nd.x6 or nd.fused or nd.fused_into >= 0 or i in in_block or \
-                    nd.unit_mask is not None or nd.cin_stride < 64:
+            if not self._free(i) or nd.cin_stride < 64:
                 continue
-            a = _probe_args(nd, nd.cin_stride, nd.k, nd.k_pad)
-            a.dtype = _lib.DRNMI_BF16_SP24
-            if nd.out_fp32_nchw:
-                a.out_dtype, a.y_sp, a.y_sc = _lib.DRNMI_F32, 1, a.ho * a.wo
+            a = _probe_args(nd, nd.cin_stride, nd.k, nd.k_pad, dtype=_lib.DRNMI_BF16_SP24, planes=nd.out_fp32_nchw)
             if lib.drnmi_conv_kernel_name(ctypes.byref(a)) is None:
                 continue
             pack(nd, lib.drnmi_sp24_pack_bytes, lib.drnmi_sp24_pack, "sp24_pack")
@@ -528,10 +602,9 @@ class PackedNet:
         for i, nd in enumerate(self.graph.nodes):
             if self.qcode != _lib.DRNMI_I8 or not nd.i8 or nd.cin_stride < 128 or not _sp24_i8_gains(nd):
                 continue
-            a = _probe_args(nd, nd.cin_stride, nd.k, nd.k_pad)
-            a.dtype, a.scale, a.out_dtype = _lib.DRNMI_I8_SP24, 1, self.value_code(nd.dst)    # (scale: presence only)
-            if nd.out_fp32_nchw:
-                a.out_dtype, a.y_sp, a.y_sc = _lib.DRNMI_F32, 1, a.ho * a.wo
+            a = _probe_args(nd, nd.cin_stride, nd.k, nd.k_pad, dtype=_lib.DRNMI_I8_SP24, out_dtype=self.value_code(nd.dst),
+                            planes=nd.out_fp32_nchw)
+            a.scale = 1                            # (presence only)
             if lib.drnmi_conv_kernel_name(ctypes.byref(a)) is not None:
                 out.append(i)
         return out
@@ -618,8 +691,6 @@ class PackedNet:
         residual read.  Only where the last conv already runs on conv_big (the LDS-DMA kernel
         that takes x2); plans with keep_all (parity taps, calibration) keep the separate launch."""
         g = self.graph
-        for nd in g.nodes:
-            nd.fused, nd.fused_into = None, -1
         if self.base != "bf16" or not FUSE_DOWNSAMPLE:
             return
         producer = {nd.dst: i for i, nd in enumerate(g.nodes)}
@@ -630,8 +701,8 @@ class PackedNet:
                     reads[v] = reads.get(v, 0) + 1
         for i, nd in enumerate(g.nodes):
             j = producer.get(nd.res) if nd.res else None
-            if j is None or nd.i8 or nd.x6 or not nd.scale_folded or nd.unit_mask is not None:
-                continue
+            if j is None or not self._free(i):     # (of _free's terms only the 8-bit, x6, scale and unit-mask ones can
+                continue                           # fail here: no later claim exists yet)
             ds = g.nodes[j]
             if (not ds.name.endswith("downsample.0") or ds.relu or ds.i8 or not ds.scale_folded
                     or ds.conv.kernel_size[0] != 1 or ds.conv.padding[0] != 0 or reads.get(nd.res) != 1):
@@ -658,61 +729,24 @@ class PackedNet:
                         "x2_val": ds.src, "stride2": ds.conv.stride[0], "ds": j}
             ds.fused_into = i
 
-    # per 8-bit code: the largest magnitude, and fp32 weights scaled to that range -> the stored bytes
-    # (int8: oracle/int8_oracle.py quantize_weight_rows; e4m3 is converted on the host: one conversion
-    # routine for every device)
-    _Q8_ENCODE = {
-        _lib.DRNMI_I8: (127.0, lambda q: torch.round(q).clamp_(-127, 127).to(torch.int8)),
-        _lib.DRNMI_F8: (F8_MAX, lambda q: q.clamp_(-F8_MAX, F8_MAX).cpu().to(torch.float8_e4m3fn).view(torch.uint8)),
-    }
-
-    def _pack_q8(self, nd: ConvNode, full: torch.Tensor, bn_scale: torch.Tensor, cout: int):
-        """Per-output-channel symmetric 8-bit weights in the net's code (include/drnmi.h DRNMI_I8 /
-        DRNMI_F8), qmax = 127 / 448: a = absmax(row), q = encode(w * (qmax / a)), s_w = a / qmax (1
-        for an all-zero row); the epilogue scale is s_w * s_x * bn_scale (s_x: the code's activation
-        scale, act_scale()), so acc * scale is the dequantised, BN-scaled conv output."""
-        qmax, encode = self._Q8_ENCODE[self.qcode]
-        a = full.abs().amax(dim=1)
-        pos = a > 0
-        inv = torch.where(pos, qmax / torch.where(pos, a, torch.ones_like(a)), torch.ones_like(a))
-        nd.wpk = encode(full * inv[:, None]).to(full.device).contiguous()
-        self._q8_fields(nd, torch.where(pos, a / qmax, torch.ones_like(a)), bn_scale)
-
-    def _pack_mx8(self, nd: ConvNode, full: torch.Tensor, bn_scale: torch.Tensor):
-        """Block-scaled e4m3 weights (include/drnmi.h DRNMI_MXF8): drnmi_mx8_pack's blob of the fp32 rows, one
-        scale per output channel and 32 packed columns; the epilogue scale is the BN scale alone, and the
-        launch carries no activation scale: the values it reads and writes are images."""
-        lib = _lib.load()
-        w = full.cpu().contiguous()
-        nbytes = int(lib.drnmi_mx8_pack_bytes(nd.cout_pad, nd.k_pad))
-        if nbytes < 0:
-            raise RuntimeError(f"mxfp8: no weight blob for {nd.name} ({nd.cout_pad} x {nd.k_pad})")
-        blob = torch.empty(nbytes, dtype=torch.uint8)
-        _lib.check(lib.drnmi_mx8_pack(w.data_ptr(), nd.cout_pad, nd.k_pad, blob.data_ptr(), nbytes), f"mx8_pack {nd.name}")
-        nd.wpk = blob.to(full.device)
-        nd.scale = bn_scale.float().contiguous()
-        nd.scale_folded = False
+    def _pack_q8(self, nd: ConvNode, full: torch.Tensor, bn_scale: torch.Tensor):
+        """An 8-bit node in the net's code: its weights and what its launch carries besides them.  The epilogue
+        scale is s_w * s_x * bn_scale (s_x: act_scale() of the input), so acc * scale is the dequantised, BN-scaled
+        conv output; a code without calibrated scales has s_x = 1 and no residual or output scale."""
+        q = self._q8
+        stored = lambda v: v if self.vcode.get(v) == q.code else "q:" + v
+        nd.wpk, sw = q.pack_rows(full, nd.name)
+        nd.i8, nd.scale_folded = True, False
         nd.unit_mask, nd.zero_unit_frac = None, 0.0
-        nd.i8 = True
-        q8 = self.qcode
-        nd.x_val = nd.src if self.vcode.get(nd.src) == q8 else "q:" + nd.src
-        if nd.res:
-            nd.r_val = nd.res if self.vcode.get(nd.res) == q8 else "q:" + nd.res
-
-    def _q8_fields(self, nd: ConvNode, sw: torch.Tensor, bn_scale: torch.Tensor):
-        """What an 8-bit launch carries besides its weights, for either 8-bit code."""
-        q8 = self.qcode
-        sx = self.act_scale(nd.src)
+        nd.x_val, nd.r_val = stored(nd.src), stored(nd.res) if nd.res else nd.res
+        sx = 1.0
+        if q.act_scale:
+            sx = self.act_scale(nd.src)
+            if nd.res:
+                nd.res_scale = self.act_scale(nd.res)
+            if self.vcode.get(nd.dst) == q.code:
+                nd.out_scale = 1.0 / self.act_scale(nd.dst)
         nd.scale = (sw * sx * bn_scale).float().contiguous()
-        nd.scale_folded = False
-        nd.unit_mask, nd.zero_unit_frac = None, 0.0
-        nd.i8 = True
-        nd.x_val = nd.src if self.vcode.get(nd.src) == q8 else "q:" + nd.src
-        if nd.res:
-            nd.r_val = nd.res if self.vcode.get(nd.res) == q8 else "q:" + nd.res
-            nd.res_scale = self.act_scale(nd.res)
-        if self.vcode.get(nd.dst) == q8:
-            nd.out_scale = 1.0 / self.act_scale(nd.dst)
 
 
 def split3_bf16(w: torch.Tensor) -> torch.Tensor:
@@ -772,9 +806,11 @@ FUSE_BLOCK64 = True
 FUSE_BLOCK16 = True
 
 
-def _probe_args(nd: ConvNode, cin_stride: int, k: int, k_pad: int) -> _lib.ConvArgs:
-    """drnmi_conv_args of the bf16 auto-routed launch of `nd` on a 16x16 map, data pointers NULL
-    (routing reads neither them nor the size): dense NHWC bf16 output, no scale."""
+def _probe_args(nd: ConvNode, cin_stride: int, k: int, k_pad: int, *, dtype: int = _lib.DRNMI_BF16,
+                out_dtype: int = _lib.DRNMI_BF16, planes: bool = False) -> _lib.ConvArgs:
+    """drnmi_conv_args of the auto-routed launch of `nd` as `dtype` (bf16) on a 16x16 map, data pointers
+    NULL (routing reads neither them nor the size), no scale: dense NHWC output of `out_dtype` (bf16) or,
+    with `planes`, the seg conv's fp32 NCHW planes."""
     c = nd.conv
     a = _lib.ConvArgs()
     a.n, a.h, a.w, a.cin = 1, 16, 16, cin_stride
@@ -782,7 +818,9 @@ def _probe_args(nd: ConvNode, cin_stride: int, k: int, k_pad: int) -> _lib.ConvA
     a.ho = _conv_out(16, a.ks, a.stride, a.pad, a.dil)
     a.wo = a.ho
     a.cout, a.cout_pad, a.k, a.k_pad = c.out_channels, nd.cout_pad, k, k_pad
-    a.dtype, a.out_dtype, a.y_sp, a.y_sc = _lib.DRNMI_BF16, _lib.DRNMI_BF16, c.out_channels, 1
+    a.dtype, a.out_dtype, a.y_sp, a.y_sc = dtype, out_dtype, c.out_channels, 1
+    if planes:
+        a.out_dtype, a.y_sp, a.y_sc = _lib.DRNMI_F32, 1, a.ho * a.wo
     a.tile, a.algo = _lib.TILE_AUTO, _lib.ALGO_IGEMM
     return a
 
@@ -803,9 +841,7 @@ def _fused_init_route(nd: ConvNode, cin_stride: int) -> bool:
     that take scale = NULL and seed the accumulators with shift + residual)."""
     if _uses_patch(nd, cin_stride, "bf16"):
         return False
-    a = _probe_args(nd, cin_stride, nd.k, nd.k_pad)
-    if nd.out_fp32_nchw:
-        a.out_dtype, a.y_sp, a.y_sc = _lib.DRNMI_F32, 1, a.ho * a.wo
+    a = _probe_args(nd, cin_stride, nd.k, nd.k_pad, planes=nd.out_fp32_nchw)
     name = _lib.load().drnmi_conv_kernel_name(ctypes.byref(a))
     return name is not None and name.decode().startswith(("conv_big", "conv_pp", "conv_halo"))
 
@@ -823,6 +859,10 @@ LOW_LATENCY_MIN_KSTEPS_3X3 = 36   # K steps of 64 channels a routed 3x3 has at l
 # (drnmi_conv_stag_seg); tests switch these module flags off to compare with the unfused path
 LABELS_NHWC = True
 SEG_FUSE = True
+# the kernels whose seg conv can write the NHWC logits rows (Plan._setup_seg): conv_big (bf16 input), the
+# int8 tile (int8 nets: store_tile_q8's 16-B fp32 rows) and its fp8 / mxfp8 kin, conv_x6 (fp32x), the 2:4 kernels
+_SEG_NHWC_KERNELS = ("conv_big_kernel", "conv_i8_kernel", "conv_i8_occ2_kernel", "conv_x6_kernel", "conv_x3_kernel",
+                     "conv_f8_kernel", "conv_f8_occ2_kernel", "conv_sp24_kernel", "conv_sp24_i8_kernel", "conv_mx_kernel")
 
 # launch kind -> (C entry point, how many drnmi_conv_args lead its arguments, the library's name
 # query over those structs or, without one, the kernel's fixed name)
@@ -860,6 +900,11 @@ class Launch:
             name = getattr(lib, name)(*self.argv[:structs])
             name = "" if name is None else name.decode()
         return name
+
+
+def _label_code(labels: torch.Tensor | None) -> int:
+    """dtype code of the label maps a head writes: int64 as asked for, uint8 otherwise (or with none to write)."""
+    return _lib.DRNMI_I64 if labels is not None and labels.dtype == torch.int64 else _lib.DRNMI_U8
 
 
 class Plan:
@@ -921,9 +966,9 @@ class Plan:
 
         def alloc(v, numel):
             td = TORCH_OF_CODE[packed.value_code(v)]
-            if packed.value_code(v) == _lib.DRNMI_MXF8:       # an image: the elements and their scale bytes
+            if packed.value_code(v) == packed.qcode:          # an 8-bit value: as many elements as its code stores
                 c = packed.cstride[v[2:] if v.startswith("q:") else v]
-                numel = int(lib.drnmi_mx8_image_bytes(numel // c, c))
+                numel = packed._q8.numel(lib, numel // c, c)
             lst = pool.get((numel, td))
             self.bufs[v] = lst.pop() if lst else torch.empty(numel, dtype=td, device=dev)
 
@@ -1000,13 +1045,12 @@ class Plan:
             raise ValueError(f"the low-latency mode covers precision 'bf16' only, not '{pk.precision}'")
         nodes = pk.graph.nodes
         cus = torch.cuda.get_device_properties(pk.device).multi_processor_count
-        in_block = {j for pairs in pk.block_pairs.values() for i in pairs for j in (i, i + 1)} if self.fuse else set()
+        in_block = pk.in_block if self.fuse else set()
         sk, unfold = {}, set()
         for i, nd in enumerate(nodes):
             c = nd.conv
-            if nd.i8 or nd.x6 or nd.wsp is not None or nd.wps is not None or nd.unit_mask is not None or nd.out_fp32_nchw or \
-                    i in in_block or \
-                    _uses_patch(nd, nd.cin_stride, pk.base):
+            # (not _free: the rule asks for no folded scale, and it unfolds a folded downsample below)
+            if not pk._dense(nd) or nd.out_fp32_nchw or i in in_block or _uses_patch(nd, nd.cin_stride, pk.base):
                 continue
             oh, ow = self.shapes[nd.dst]
             m, cout = self.n * oh * ow, c.out_channels
@@ -1049,8 +1093,7 @@ class Plan:
 
     # labels-only video path: the seg conv writes fp32 NHWC rows of SEG_NHWC_CS floats (16-B
     # stores instead of 19 strided planes) and drnmi_up8_labels_nhwc reads them; same values,
-    # same labels.  Only where the seg conv runs on conv_big (bf16 input), on the int8 tile
-    # (int8 nets: store_tile_q8's 16-B fp32 rows) or on conv_x6 (fp32x) and the 19-class head.
+    # same labels.  Only where the seg conv runs on one of _SEG_NHWC_KERNELS and the 19-class head.
     # Any other class count 1 .. 256 (bf16 and int8 plans): rows of round_up(classes, 4) floats
     # and drnmi_up8_labels_nhwc_wide; the seg classifier is not folded into the last conv there.
     SEG_NHWC_CS = 20
@@ -1076,7 +1119,7 @@ class Plan:
         if seg.conv.kernel_size[0] != 1 or not 1 <= classes <= 256:
             return
         wide = classes != 19
-        if wide and pk.precision not in ("bf16", "int8", "fp8", "mxfp8"):
+        if wide and pk.base != "bf16":
             return                               # fp32 / fp32x plans keep the logits planes
         cs = (classes + 3) // 4 * 4 if wide else self.SEG_NHWC_CS
         lh, lw = self.shapes[seg.dst]
@@ -1084,9 +1127,7 @@ class Plan:
         ctypes.pointer(a)[0] = self.args[i]
         a.y_sn, a.y_sp, a.y_sc = lh * lw * cs, cs, 1
         name = lib.drnmi_conv_kernel_name(ctypes.byref(a))   # (routing does not read a.y)
-        if name is None or not name.decode().startswith(("conv_big_kernel", "conv_i8_kernel", "conv_i8_occ2_kernel",
-                                                        "conv_x6_kernel", "conv_x3_kernel", "conv_f8_kernel", "conv_f8_occ2_kernel",
-                                                        "conv_sp24_kernel", "conv_sp24_i8_kernel", "conv_mx_kernel")):
+        if name is None or not name.decode().startswith(_SEG_NHWC_KERNELS):
             return
         if "logits_nhwc" not in self.bufs:      # only plans whose seg conv writes the NHWC rows
             self.bufs["logits_nhwc"] = torch.empty(self.n * lh * lw * cs, dtype=torch.float32, device=pk.device)
@@ -1095,7 +1136,7 @@ class Plan:
         self.seg_classes, self.seg_cs = classes, cs
         if wide or not SEG_FUSE or not self.fuse or seg.x_val != seg.src or seg.r_val:
             return
-        if pk.qcode in (_lib.DRNMI_F8, _lib.DRNMI_MXF8):
+        if pk._q8 is not None and not pk._q8.seg_fused:
             return                               # fp8 / mxfp8: a separate seg conv feeds the NHWC head (no seg-fused tile)
         # the launch that writes the seg conv's input, on the labels-only list without this fusion:
         # one that already computes several nodes (front, block, folded downsample) is left alone
@@ -1287,19 +1328,9 @@ class Plan:
                 self._quantize(lib, v, stream)
 
     def _quantize(self, lib, v: str, stream: ctypes.c_void_p):
-        """bf16 value -> its 8-bit copy "q:<v>" (include/drnmi.h drnmi_quantize_i8 / drnmi_quantize_f8)."""
-        src, dst = self.bufs[v], self.bufs["q:" + v]
-        if self.packed.qcode == _lib.DRNMI_MXF8:
-            c = self.packed.cstride[v]
-            _lib.check(lib.drnmi_quantize_mx8(src.data_ptr(), self.packed.value_code(v), src.numel() // c, c,
-                                              dst.data_ptr(), stream), f"quantize_mx8 {v}")
-            return
-        if self.packed.qcode == _lib.DRNMI_F8:
-            _lib.check(lib.drnmi_quantize_f8(src.data_ptr(), self.packed.value_code(v), dst.numel(),
-                                             1.0 / self.packed.act_scale(v), dst.data_ptr(), stream), f"quantize_f8 {v}")
-            return
-        _lib.check(lib.drnmi_quantize_i8(src.data_ptr(), self.packed.value_code(v), dst.data_ptr(), dst.numel(),
-                                         1.0 / float(self.packed.act_scales[v]), stream), f"quantize_i8 {v}")
+        """bf16 value -> its 8-bit copy "q:<v>" in the net's code (the drnmi_quantize_* call of its record)."""
+        pk = self.packed
+        _lib.check(pk._q8.quantize(lib, pk, v, self.bufs[v], self.bufs["q:" + v], stream), f"quantize {pk.precision} {v}")
 
     def ingest_nchw(self, x: torch.Tensor, stream: int):
         self.src = "nchw"
@@ -1340,75 +1371,59 @@ class Plan:
         lib = _lib.load()
         logits = self.bufs["logits"]
         n, c, lh, lw = logits.shape
-        lab_dtype = _lib.DRNMI_U8
-        if labels is not None and labels.dtype == torch.int64:
-            lab_dtype = _lib.DRNMI_I64
         _lib.check(lib.drnmi_up8_logsoftmax_argmax(
             logits.data_ptr(), up_w.data_ptr(),
             logprobs.data_ptr() if logprobs is not None else None,
             labels.data_ptr() if labels is not None else None,
-            lab_dtype, n, c, lh, lw, ctypes.c_void_p(stream)), "up8_logsoftmax_argmax")
+            _label_code(labels), n, c, lh, lw, ctypes.c_void_p(stream)), "up8_logsoftmax_argmax")
 
     def head_labels_nhwc(self, up_w: torch.Tensor, stream: int, labels: torch.Tensor):
         """Labels from the NHWC logits run_backbone(labels_only=True) wrote (drnmi_up8_labels_nhwc; any class
         count but 19: drnmi_up8_labels_nhwc_wide)."""
         lh, lw = self.shapes["logits"]
-        lab_dtype = _lib.DRNMI_I64 if labels.dtype == torch.int64 else _lib.DRNMI_U8
         if self.seg_classes != 19:
             _lib.check(_lib.load().drnmi_up8_labels_nhwc_wide(
-                self.bufs["logits_nhwc"].data_ptr(), self.seg_cs, up_w.data_ptr(), labels.data_ptr(), lab_dtype,
+                self.bufs["logits_nhwc"].data_ptr(), self.seg_cs, up_w.data_ptr(), labels.data_ptr(), _label_code(labels),
                 self.n, self.seg_classes, lh, lw, ctypes.c_void_p(stream)), "up8_labels_nhwc_wide")
             return
         _lib.check(_lib.load().drnmi_up8_labels_nhwc(
-            self.bufs["logits_nhwc"].data_ptr(), self.SEG_NHWC_CS, up_w.data_ptr(), labels.data_ptr(), lab_dtype,
+            self.bufs["logits_nhwc"].data_ptr(), self.SEG_NHWC_CS, up_w.data_ptr(), labels.data_ptr(), _label_code(labels),
             self.n, 19, lh, lw, ctypes.c_void_p(stream)), "up8_labels_nhwc")
 
     def head_labels_seg2(self, up_w: torch.Tensor, stream: int, labels: torch.Tensor):
         """Labels from the partial logits run_backbone(labels_only=True) wrote with the seg folded into
         the last conv (drnmi_up8_labels_seg2)."""
         lh, lw = self.shapes["logits"]
-        lab_dtype = _lib.DRNMI_I64 if labels.dtype == torch.int64 else _lib.DRNMI_U8
         sf = self.seg_fused
         if sf["i8"]:
             _lib.check(_lib.load().drnmi_up8_labels_seg2_i8(
                 self.bufs["seg_part"].data_ptr(), self.SEG_NHWC_CS, sf["scale"], sf["bias"], up_w.data_ptr(),
-                labels.data_ptr(), lab_dtype, self.n, 19, lh, lw, ctypes.c_void_p(stream)), "up8_labels_seg2_i8")
+                labels.data_ptr(), _label_code(labels), self.n, 19, lh, lw, ctypes.c_void_p(stream)), "up8_labels_seg2_i8")
             return
         _lib.check(_lib.load().drnmi_up8_labels_seg2(
             self.bufs["seg_part"].data_ptr(), self.SEG_NHWC_CS, sf["bias"], up_w.data_ptr(),
-            labels.data_ptr(), lab_dtype, self.n, 19, lh, lw, ctypes.c_void_p(stream)), "up8_labels_seg2")
+            labels.data_ptr(), _label_code(labels), self.n, 19, lh, lw, ctypes.c_void_p(stream)), "up8_labels_seg2")
 
     def head_bilinear(self, stream: int, logprobs: torch.Tensor | None, labels: torch.Tensor | None):
         """use_torch_up head: UpsamplingBilinear2d(8) + LogSoftmax + argmax (lmodels/drnseg.py:285-287)."""
         lib = _lib.load()
         logits = self.bufs["logits"]
         n, c, lh, lw = logits.shape
-        lab_dtype = _lib.DRNMI_I64 if labels is not None and labels.dtype == torch.int64 else _lib.DRNMI_U8
         _lib.check(lib.drnmi_up8_bilinear_logsoftmax_argmax(
             logits.data_ptr(), logprobs.data_ptr() if logprobs is not None else None,
-            labels.data_ptr() if labels is not None else None, lab_dtype, n, c, lh, lw, ctypes.c_void_p(stream)),
+            labels.data_ptr() if labels is not None else None, _label_code(labels), n, c, lh, lw, ctypes.c_void_p(stream)),
             "up8_bilinear_logsoftmax_argmax")
 
     def stage_nchw(self, value: str) -> torch.Tensor:
         """fp32 NCHW copy of an intermediate activation (parity taps; keep_all plans).  int8
         values come back dequantised (q * scale) -- a test-side view, not a launch."""
         lib = _lib.load()
-        c = self.packed.graph.channels[value]
+        pk = self.packed
+        c, cs = pk.graph.channels[value], pk.cstride[value]
         oh, ow = self.shapes[value]
-        if self.packed.value_code(value) == _lib.DRNMI_I8:
-            cs = self.packed.cstride[value]
-            q = self.bufs[value].view(self.n, oh, ow, cs)[..., :c]
-            return (q.float() * float(self.packed.act_scales[value])).permute(0, 3, 1, 2).contiguous()
-        if self.packed.value_code(value) == _lib.DRNMI_F8:
-            cs = self.packed.cstride[value]
-            q = self.bufs[value].view(torch.float8_e4m3fn).view(self.n, oh, ow, cs)[..., :c]
-            return (q.float() * self.packed.act_scale(value)).permute(0, 3, 1, 2).contiguous()
-        if self.packed.value_code(value) == _lib.DRNMI_MXF8:
-            cs = self.packed.cstride[value]
-            q = torch.empty(self.n, oh, ow, cs, dtype=torch.float32, device=self.packed.device)
-            _lib.check(lib.drnmi_dequantize_mx8(self.bufs[value].data_ptr(), self.n * oh * ow, cs, q.data_ptr(),
-                                                ctypes.c_void_p(_lib.stream_ptr())), "dequantize_mx8")
-            return q[..., :c].permute(0, 3, 1, 2).contiguous()
+        if pk.value_code(value) == pk.qcode:
+            x = pk._q8.dequantize(lib, pk, value, self.bufs[value], self.n * oh * ow, cs)
+            return x.view(self.n, oh, ow, cs)[..., :c].permute(0, 3, 1, 2).contiguous()
         out = torch.empty(self.n, c, oh, ow, dtype=torch.float32, device=self.packed.device)
         _lib.check(lib.drnmi_nhwc_to_nchw(self.bufs[value].data_ptr(), out.data_ptr(), self.n, c, oh, ow,
                                           self.packed.cstride[value], self.packed.value_code(value),
